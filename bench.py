@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training throughput of the ResNet-34 + AAM-softmax hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 without WORLD_SIZE in the environment: this process spawns its N ranks itself (python -m torch.distributed.run
   --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...) BEFORE touching the GPU, relays rank 0's
   JSON line and exits with the children's code - the reference spawns its own ranks too (scripts/train_resnet.py:122-128).
@@ -10,7 +10,19 @@
 A "step" is one full training iteration of BASELINE.json configs[1] on one batch of synthetic input that is
 already resident in HBM: forward (train-mode BN) + AAM margin + cross-entropy + hand-written backward +
 fused SGD (+ overlapped RCCL gradient all-reduce when N > 1; per-GPU batch fixed at 256 = weak scaling).
-Prints ONE JSON line (see the repo contract) with two extra objects:
+Prints ONE JSON line (see the repo contract).  A plain run sets up, warms up, times the K steps and prints it; `ms_per_step`
+is the wall time of one timed step.
+
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): train =
+                 `loss`, `logits`, `rank`, the updated `parameters` arena, the `gradients` arena and `bn_running_stats`; predict
+                 = `embeddings`.  At most 64 MB in all: an array that does not fit is replaced by a fixed, seeded sample of its
+                 flattened elements (the ResNet-34 headline fits whole).  Same arguments, same inputs: two builds compare output
+                 for output.
+
+  --full  also runs every check and measurement that is not the headline figure, after the timed region (never part of
+          `value`): the graph re-pack proof (`graph_replay_repacks_weights`), the objects below, `fp32_operand_mfma` (the same
+          step on the native fp32 matrix instruction), `embedding_cosine_delta_vs_oracle` and the bounded extra legs
+          (`ingest`, `extra.c5`, `extra.c4`).  Without it those fields are null.  The --no-* options switch single legs off.
   roofline     - dominant kernel (by total device time in an instrumented pass of the same steps): its algorithmic
                  FLOPs and bytes per launch / average launch duration measured with HIP events on the launch stream,
                  priced against BOTH ceilings of MI355X_MICROARCH.md - the dense matrix peak of its operand mode (fp16 /
@@ -76,6 +88,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and measurements beside the headline figure (roofline, CPU baseline, EER, "
+                         "fp32 leg, f16 windows, re-pack proof, extra legs)")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="per-GPU batch (256 = the BASELINE config)")
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--mode", choices=["train", "predict"], default="train",
@@ -108,10 +125,12 @@ def parse():
     ap.add_argument("--no-f16-window", action="store_true", help="skip the operand-scale window counters (f16x3 mode)")
     ap.add_argument("--lengths", type=int, default=8, help="distinct chunk lengths of --frames-range (one cached hipGraph each)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the bounded extra legs of the default N = 1 line (after the timed region, never part of `value`): "
+                    help="skip the bounded extra legs of the --full N = 1 line (after the timed region, never part of `value`): "
                          "`ingest` (loader-inclusive step), `extra.c5` (predict bs 512 with its own roofline object), `extra.c4` "
                          "(ResNet-101, S 5994, three cached chunk lengths in [200, 400])")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.config == "c1":
         a.batch, a.frames, a.speakers = 32, 200, 10
     elif a.config == "c4":
@@ -266,6 +285,30 @@ def embedding_parity(dev):
         r = O.embed(O.to_torch_state(npst), torch.from_numpy(x), "mean+std", "resnet34", train=False).numpy().astype(np.float64)
     cos = (e * r).sum(1) / (np.linalg.norm(e, axis=1) * np.linalg.norm(r, axis=1))
     return float((1.0 - cos).max())
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20     # --dump-outputs: under 64 MB (either convention) with room for the .npy headers
+
+
+def dump_outputs(d, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as d/<name>.npy in float32.  If they do not fit the budget together, the smallest are kept
+    whole and the rest share what is left evenly, each as a fixed, seeded sample (sorted indices) of its flattened elements."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left = budget // 4
+    written = {}
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        a = t.detach().float().cpu().numpy()
+        k = min(a.size, left // (len(items) - i))
+        if k < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.size
+        written[name] = list(a.shape)
+    log("dumped outputs to %s: %s" % (d, written))
+    return written
 
 
 def roofline_object(recs, npass):
@@ -501,7 +544,8 @@ def main():
         model.eval()
 
         def step():
-            return model.predict(cur_x()).sum()
+            emb = model.predict(cur_x())
+            return emb.sum(), {"embeddings": emb}
     else:
         step = None
 
@@ -531,17 +575,16 @@ def main():
         return var_x[t]
 
     def train_step():
+        """-> (loss, the step's outputs by name: the graph's static buffers in graph mode, read before the next replay)"""
         xb = cur_x()
         if graphed is not None and PROFILE_OFF():
-            loss, _, _ = graphs[xb.shape[2]](xb, y, red.on_stage_done if red.active else None)
-            red.finish()
-            opt.step()
-            return loss
-        opt.zero_grad(set_to_none=True)
-        loss, _, _ = eng.loss_and_grad(xb, y, red.on_stage_done if red.active else None)
+            loss, logits, rk = graphs[xb.shape[2]](xb, y, red.on_stage_done if red.active else None)
+        else:
+            opt.zero_grad(set_to_none=True)
+            loss, logits, rk = eng.loss_and_grad(xb, y, red.on_stage_done if red.active else None)
         red.finish()
         opt.step()
-        return loss
+        return loss, {"loss": loss, "logits": logits, "rank": rk}
 
     def PROFILE_OFF():
         return ops.PROFILE is None
@@ -551,7 +594,7 @@ def main():
     log("model built, starting warm-up")
     first_loss = None
     for i in range(args.warmup):
-        l0 = step()
+        l0, _ = step()
         torch.cuda.synchronize()
         if first_loss is None:
             first_loss = float(l0)
@@ -562,7 +605,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, outputs = step()
     t_host = time.perf_counter() - t0          # host time to enqueue the K steps (no sync inside)
     torch.cuda.synchronize()
     if world > 1:
@@ -576,8 +619,16 @@ def main():
     lossv = float(loss)
     if first_loss is None:
         first_loss = lossv
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the device: in graph mode the outputs are the graph's static buffers
+        if args.mode == "train":
+            outputs["parameters"] = model.flat_parameters()
+            outputs["gradients"] = model.flat_grads()
+            outputs["bn_running_stats"] = torch.cat([b.reshape(-1) for n, b in model.named_buffers()
+                                                     if n.endswith(("running_mean", "running_var"))])
+        dump_outputs(args.dump_outputs, outputs)
     repack_ok = None
-    if graphed is not None and args.mode == "train":
+    if args.full and graphed is not None and args.mode == "train":
         # Proof that every replay trains on the weights the optimizer just wrote (scripts/train_resnet.py:316-328): the last
         # opt.step() changed the parameter arena; one more replay must leave the packed operands of the convolutions equal to
         # a fresh pack of the CURRENT weights.  A graph that does not contain the re-pack fails here.
@@ -602,7 +653,7 @@ def main():
     log("timed region done: %.3f s for %d steps (host enqueue %.1f ms/step)" % (dt, args.steps, t_host / args.steps * 1e3))
 
     ingest = None
-    want_extra = rank == 0 and world == 1 and headline and not args.no_extra
+    want_extra = args.full and rank == 0 and world == 1 and headline and not args.no_extra
     if (args.ingest or want_extra) and args.mode == "train" and var_x is None:
         # Loader-inclusive step (reference scripts/train_resnet.py:307-313: loader -> pinned H2D -> step): every rank reads
         # its own seeded ark through libspkio (pread of the cropped frames on a thread pool into a pinned ring, guarded by
@@ -666,7 +717,7 @@ def main():
         log("ingest-inclusive: %.1f utt/s (%.3f of the resident-input rate)" % (ingest["value"], ingest["ratio_to_resident_input"]))
 
     f16_window = None
-    if rank == 0 and args.mode == "train" and ops.SPLIT == 3 and not args.no_f16_window:
+    if args.full and rank == 0 and args.mode == "train" and ops.SPLIT == 3 and not args.no_f16_window:
         # one eager step (outside every timed region) with the window counters on: every tensor an f16x3 matrix-core kernel
         # stages is also run through spk_f16_window_count under the scale slot its consumer uses
         eng.window_counts = torch.zeros(4, device=dev, dtype=torch.int64)
@@ -687,7 +738,7 @@ def main():
             raise SystemExit("bench: %d staged values saturate fp16 under their scale slot - an operand-scale bound is wrong" % sat)
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # instrumented pass: same steps, every launch bracketed by HIP events on its launch stream; the side stream
         # for weight gradients is folded into the main stream here so kernels do not overlap while being timed
         eng.use_side_stream = False
@@ -706,7 +757,7 @@ def main():
         eng.use_side_stream = True
         roofline = roofline_object(recs, NPASS)
     native = None
-    if rank == 0 and world == 1 and args.mode == "train" and headline and graphed is not None and ops.SPLIT != 0 \
+    if args.full and rank == 0 and world == 1 and args.mode == "train" and headline and graphed is not None and ops.SPLIT != 0 \
             and not args.no_roofline and not args.no_fp32_leg:
         # the same step on the native fp32 matrix instruction, timed the same way, for comparison (N = 1 only)
         from pytorch_kaldi_resnet_amd.engine import GraphedTrainStep
@@ -731,14 +782,14 @@ def main():
         log("fp32-operand comparison run done: %.1f utt/s" % native["value"])
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train" and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train" and headline:
         log("roofline pass done; timing the CPU oracle (bounded sample)")
         cpu = cpu_baseline(args)
         log("cpu baseline done")
         parity = embedding_parity(dev)
         log("embedding parity vs oracle: max 1-cos = %.3e" % parity)
     eer = None
-    if rank == 0 and world == 1 and not args.no_eer and not args.no_cpu_baseline and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_eer and not args.no_cpu_baseline and headline:
         eer = eer_leg(dev)
         log("EER leg done: hip %.4f vs cpu oracle %.4f (2048 utts, 20 k trials); subset hip %.4f vs cpu oracle %.4f" % (
             eer["hip_2048_utts"], eer["cpu_oracle_2048_utts"], eer["hip_subset"], eer["cpu_oracle_subset"]))
@@ -753,9 +804,9 @@ def main():
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         mf = ["--mfma", mfma_mode]
-        extra = {"c5": extra_leg("c5", ["--config", "c5", "--steps", "10", "--warmup", "3", "--no-extra"] + mf, 240),
+        extra = {"c5": extra_leg("c5", ["--config", "c5", "--steps", "10", "--warmup", "3", "--full", "--no-extra"] + mf, 240),
                  "c4": extra_leg("c4", ["--config", "c4", "--lengths", "3", "--steps", "6", "--warmup", "3", "--no-cpu-baseline",
-                                        "--no-eer", "--no-f16-window", "--no-extra"] + mf, 300)}
+                                        "--no-eer", "--no-f16-window", "--full", "--no-extra"] + mf, 300)}
     if rank == 0:
         gb = args.batch * world
         arch_name = {"resnet34": "ResNet-34", "resnet101": "ResNet-101"}[args.arch]

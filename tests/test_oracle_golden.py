@@ -67,7 +67,10 @@ def test_forward_backward_vs_reference(gold_dir, name):
         assert abs(np.sqrt((gi.astype(np.float64) ** 2).sum()) - ref_norm) <= 1e-4 * ref_norm + 1e-5, n
         idx = np.minimum((W.hash_uniform(77, i, 16) * gi.size).astype(np.int64), gi.size - 1)
         rms = ref_norm / np.sqrt(gi.size)
-        assert np.abs(gi[idx] - g["grad_samples"][i]).max() <= 2e-3 * rms + 1e-6, n
+        # a reference norm under that floor is rounding noise in both codes (fc1.bias in front of the train-mode BatchNorm of
+        # the softmax head: norm ~2e-6); its samples are judged against the same floor, which the norm check already implies
+        tol = 1e-5 if ref_norm < 1e-5 else 2e-3 * rms + 1e-6
+        assert np.abs(gi[idx] - g["grad_samples"][i]).max() <= tol, n
     for key in g.files:
         if key.startswith("rm:"):
             np.testing.assert_allclose(st[key[3:] + ".running_mean"].numpy(), g[key], rtol=1e-5, atol=1e-6)

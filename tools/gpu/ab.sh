@@ -8,7 +8,7 @@ for v in ${AB_VARIANTS:-base}; do
     lib=pytorch-kaldi-resnet_amd/variants/libspkhip_$v.so
     [ "$v" = base ] && lib=pytorch-kaldi-resnet_amd/libspkhip.so
     echo "=== $v $(date +%T)"
-    SPK_LIB=$lib SPK_LABEL_SHAPES=1 timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-eer --no-fp32-leg --no-f16-window --no-extra ${AB_ARGS} > $D/ab_$v.json 2> $D/ab_$v.err
+    SPK_LIB=$lib SPK_LABEL_SHAPES=1 timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-eer --no-fp32-leg --no-f16-window --no-extra ${AB_ARGS} > $D/ab_$v.json 2> $D/ab_$v.err
     rc=$?
     if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT in $v: stopping"; exit 1; fi
     python3 - $D/ab_$v.json "$v" "${AB_GREP:-.}" <<'PY'

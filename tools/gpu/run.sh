@@ -4,7 +4,7 @@
 # Every step logs to gpurun_out/<tag>/<step>.log / .err and a line in progress.log; a step that hits its timeout stops the
 # plan (no further GPU step after a kill).  Steps:
 #   test:<expr>      python -m pytest tests -m gpu -x -q -k '<expr>'        (test:all = the whole -m gpu suite)
-#   bench            default bench line            bench_forced   the same under SPK_FORCE_REDUCER=1 (RCCL, one rank)
+#   bench            full bench line (--full)      bench_forced   the same under SPK_FORCE_REDUCER=1 (RCCL, one rank)
 #   bench_ingest / bench_c4 / bench_c5 / bench_fast (no CPU legs)
 #   smoke            __graft_entry__.smoke()
 #   gpus2_gloo       `python bench.py --gpus 2` spawning its own two ranks, both on GPU 0 over gloo (control-flow rehearsal, not a measurement)
@@ -31,18 +31,18 @@ for step in "$@"; do
     case "$step" in
         test:all)      run test_all 1100 python3 -m pytest tests -m gpu -x -q --durations=25 ;;
         test:*)        run "test_$(echo ${step#test:} | tr -c 'A-Za-z0-9\n' '_')" 900 python3 -m pytest tests -m gpu -x -q -s -k "${step#test:}" ;;
-        bench)         run bench 500 python3 bench.py --steps 20 --warmup 5 ;;
-        bench_fast)    run bench_fast 300 python3 bench.py --steps 20 --warmup 5 $FAST --no-extra ;;
-        bench_forced)  SPK_FORCE_REDUCER=1 run bench_forced 300 python3 bench.py --steps 20 --warmup 5 $FAST --no-extra ;;
-        bench_ingest)  run bench_ingest 300 python3 bench.py --steps 20 --warmup 5 $FAST --no-roofline --ingest --no-extra ;;
-        bench_c4)      run bench_c4 400 python3 bench.py --config c4 --steps 16 --warmup 8 --no-cpu-baseline --no-eer ;;
-        bench_c5)      run bench_c5 300 python3 bench.py --config c5 --steps 20 --warmup 5 ;;
+        bench)         run bench 500 python3 bench.py --steps 20 --warmup 5 --full ;;
+        bench_fast)    run bench_fast 300 python3 bench.py --steps 20 --warmup 5 --full $FAST --no-extra ;;
+        bench_forced)  SPK_FORCE_REDUCER=1 run bench_forced 300 python3 bench.py --steps 20 --warmup 5 --full $FAST --no-extra ;;
+        bench_ingest)  run bench_ingest 300 python3 bench.py --steps 20 --warmup 5 --full $FAST --no-roofline --ingest --no-extra ;;
+        bench_c4)      run bench_c4 400 python3 bench.py --config c4 --steps 16 --warmup 8 --full --no-cpu-baseline --no-eer ;;
+        bench_c5)      run bench_c5 300 python3 bench.py --config c5 --steps 20 --warmup 5 --full ;;
         smoke)         run smoke 200 python3 __graft_entry__.py smoke ;;
-        gpus2_gloo)    SPK_FORCE_DEVICE=0 SPK_DIST_BACKEND=gloo run gpus2_gloo 300 python3 bench.py --gpus 2 --batch 64 --steps 5 --warmup 2 $FAST --no-roofline --no-extra ;;
+        gpus2_gloo)    SPK_FORCE_DEVICE=0 SPK_DIST_BACKEND=gloo run gpus2_gloo 300 python3 bench.py --gpus 2 --batch 64 --steps 5 --warmup 2 --full $FAST --no-roofline --no-extra ;;
         profile)       run profile 600 bash tools/profile_bench.sh $D/prof ;;
         profile_sq)    run profile_sq 400 bash tools/profile_sq.sh $D/sq ;;
         profile_sq2)   run profile_sq2 500 bash tools/profile_sq2.sh $D/sq2 ;;
-        bench_shapes)  SPK_LABEL_SHAPES=1 run bench_shapes 300 python3 bench.py --steps 10 --warmup 3 $FAST --no-extra ;;
+        bench_shapes)  SPK_LABEL_SHAPES=1 run bench_shapes 300 python3 bench.py --steps 10 --warmup 3 --full $FAST --no-extra ;;
         trace_forced)  mkdir -p $D/trace_forced
                        echo "=== trace_forced $(date +%T)" | tee -a $D/progress.log
                        ( cd /tmp && SPK_FORCE_REDUCER=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/$D/trace_forced --output-format csv -- \

@@ -4,7 +4,7 @@
 # WM_AB="name:VAR=val,VAR=val name2:..." overrides the plan.
 D=${1:-gpurun_out/wm_ab}
 mkdir -p $D
-FAST="--steps 20 --warmup 5 --no-cpu-baseline --no-eer --no-fp32-leg --no-f16-window --no-extra"
+FAST="--steps 20 --warmup 5 --full --no-cpu-baseline --no-eer --no-fp32-leg --no-f16-window --no-extra"
 one() {
     local name=$1; shift
     echo "=== $name $(date +%T)"
