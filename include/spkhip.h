@@ -78,6 +78,9 @@ int spk_build_flags(void);
 #define SPK_IN_PRESPLIT (1 << 14)    /* spk_conv_mfma: `in` is an f16 pair tensor scaled by the sigma of *in_amax (plain input only) */
 #define SPK_SIDE_PRESPLIT (1 << 15)  /* spk_conv_mfma + SPK_IN_BNBWD: side_draw leaves as an f16 pair tensor (scale: *in_amax) */
 #define SPK_DY_PRESPLIT (1 << 16)    /* spk_conv_wgrad: `dy` is an f16 pair tensor scaled by the sigma of *dy_amax */
+#define SPK_EPI_WMASK (1 << 24)      /* spk_conv_mfma_len / spk_stem_conv_fwd_len only: an output pixel of image b at width (time)
+                                        x >= wlen[b] is stored as 0 after the whole epilogue and does not enter out_amax / the
+                                        statistics (length-masked eval forward of a padded batch).  Every other entry refuses it */
 
 /* ---- convolutions --------------------------------------------------------------------------------- */
 
@@ -133,6 +136,20 @@ int spk_conv_mfma(const float* in, const float* wpk, float* out, const float* in
                   int ntaps, const int* tap_dy /*host*/, const int* tap_dx /*host*/, const int* tap_w /*host*/, int TH,
                   int TW, int MT, int NT, int kc, int ips, int flags, int split, const unsigned* in_amax, unsigned* out_amax,
                   unsigned* side_amax, void* stream);
+/* spk_conv_mfma with a length mask (length-masked eval forward of a padded batch): same arguments plus wlen, a DEVICE int array [B]
+ * of valid output widths; flags must carry SPK_EPI_WMASK.  Output pixel (y, x) of image b with x >= wlen[b] (physical output column)
+ * is stored as 0 after the whole epilogue (affine, add, ReLU) and stays out of out_amax and the statistics.  Implemented by
+ * conv_mfma_kernel and conv_pipe_kernel (M16 included) with a plain input; IN_BNBWD, EPI_BNBWD, IN_PRESPLIT, SIDE_PRESPLIT and
+ * CONV_WS are refused, as is SPK_EPI_WMASK on spk_conv_mfma (no wlen) or on any other entry. */
+int spk_conv_mfma_len(const float* in, const float* wpk, float* out, const float* in_scale, const float* in_shift,
+                      const float* epi_scale, const float* epi_shift, const float* epi_add, const float* in_raw,
+                      const float* in_act, const float* in_bn4, const float* in_coef, const unsigned* in_mask,
+                      const unsigned* bn_mask, const unsigned* add_mask, float* side_draw, float* side_dz,
+                      const float* bn_raw, const float* bn_act, const float* bn4, float* stats, int B, int IH,
+                      int IW, int Cin, int OH, int OW, int OHf, int OWf, int Cout, int IS, int OS, int ooy, int oox,
+                      int ntaps, const int* tap_dy /*host*/, const int* tap_dx /*host*/, const int* tap_w /*host*/, int TH,
+                      int TW, int MT, int NT, int kc, int ips, int flags, int split, const unsigned* in_amax, unsigned* out_amax,
+                      unsigned* side_amax, const int* wlen /*device [B]*/, void* stream);
 
 /* Weight gradient of a 3x3 (pad 1) or 1x1 (pad 0) conv at stride 1 or 2 (autograd of nn.Conv2d).
  * x: conv input [B][IH][IW][Cin] (optionally raw + fused BN/ReLU via in_scale/in_shift and SPK_IN_AFFINE_RELU),
@@ -183,6 +200,12 @@ int spk_stem_fwd_blocks(int B, int F, int T);
 int spk_stem_conv_fwd(const float* x, const float* w, float* out, float* stats, const float* epi_scale,
                       const float* epi_shift, int B, int F, int T, int flags,
                       unsigned* amax_out /* optional: atomicMax of the float bits of |out| */, void* stream);
+/* the same over a padded batch: image b holds len[b] <= T valid frames (len: DEVICE int array [B]; flags must carry SPK_EPI_WMASK).
+ * Frames t >= len[b] of x are read as 0 whatever they hold (NaN included); outputs at t >= len[b] are stored as 0 and stay out of
+ * amax_out and the statistics: each image's valid outputs equal those of a run at its own length. */
+int spk_stem_conv_fwd_len(const float* x, const float* w, float* out, float* stats, const float* epi_scale,
+                          const float* epi_shift, int B, int F, int T, int flags, unsigned* amax_out, const int* len /*device [B]*/,
+                          void* stream);
 /* its weight gradient; partial: [spk_stem_wgrad_blocks()][32*9] floats */
 int spk_stem_wgrad_blocks(int B, int F, int T);
 int spk_stem_conv_wgrad(const float* x, const float* draw, float* dw, float* partial, int B, int F, int T,
@@ -255,6 +278,9 @@ int spk_affine_estimate(const float* scale, const float* shift, int C, const uns
 /* ---- statistics pooling (StatsPooling, scripts/model.py:435-457; mode 0 = 'mean', 1 = 'mean+std') -------- */
 int spk_stats_pool_fwd(const float* x /*[B][H][W][C]*/, float* out /*[B][C*H*(1+mode)]*/, int B, int H, int W, int C,
                        int mode, void* stream);
+/* per-image widths: row b pools over its first wlen[b] frames (DEVICE int array [B], clamped to [1, W]) with the same two-pass
+ * arithmetic as spk_stats_pool_fwd at that width - 'mean+std' of one frame gives the unbiased variance 0/0 = NaN for that row */
+int spk_stats_pool_fwd_len(const float* x, float* out, const int* wlen, int B, int H, int W, int C, int mode, void* stream);
 int spk_stats_pool_bwd(const float* x, const float* gout, float* dx, int B, int H, int W, int C, int mode,
                        unsigned* amax_out /* optional: atomicMax of the float bits of |dx| */, void* stream);
 

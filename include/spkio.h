@@ -17,6 +17,10 @@ int spk_ark_probe(int n, const char* const* paths, const int64_t* offsets, int32
 /* out[b][f][t] = M_b[starts[b] + t][f], t < T; reads only the cropped frames with pread() on `nthreads` threads */
 int spk_ark_read_crop(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows,
                       const int32_t* starts, int F, int T, float* out, int nthreads);
+/* whole utterances, padded: out[b][f][t] = M_b[t][f] for t < rows[b], 0 for rows[b] <= t < T (1 <= rows[b] <= T) - the input of a
+ * length-masked predict over a length-sorted batch */
+int spk_ark_read_padded(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows, int F, int T,
+                        float* out, int nthreads);
 void spk_ark_close_all(void);
 /* text-ark embedding writer: out <- "key [ v0 v1 ... ]\n" per row of v[n][D], each value printed exactly as numpy's
  * str(np.float32) does - the line format of the reference's scripts/decode.py:199-206.  Returns the bytes written

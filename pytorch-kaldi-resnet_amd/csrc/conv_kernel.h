@@ -87,6 +87,7 @@ struct ConvArgs {
     const unsigned* w_amax;    // header of the fp16-split packed weights: float bits of max|w| -> the weight scale
     unsigned* out_amax;        // optional: atomicMax of |stored output| (float bits) - the next consumer's in_amax
     unsigned* side_amax;       // optional (IN_BNBWD): atomicMax of |side_draw| - the weight gradient's dY scale
+    const int* wlen;           // SPK_EPI_WMASK: [B] valid output width of each image (physical output column x >= wlen[b]: 0)
     int tap_boff[9];  // wave-specialised kernel: float offset of (tap, channel plane 0) in the bf16-split packed weights
     int kc;           // channel planes (of 32) staged per barrier: > 1 only for single-tap (1x1) convolutions, whose K loop
                       // per 32-channel chunk is too short to amortise a staging phase
@@ -193,13 +194,17 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
     float* img_dz = (BNBWD && a.side_dz) ? a.side_dz + img_el : nullptr;
     const int npix_tile = a.TH * a.TW;
     const int n0 = cg * NT * 32;
-    const int flags = FL >= 0 ? (FL & 0xFFFFF) : a.flags;
-    const bool has_add_mask = FL >= 0 ? (FL & SPK_FL_ADDMASK) != 0 : a.add_mask != nullptr;
-    const bool has_bn_mask = FL >= 0 ? (FL & SPK_FL_BNMASK) != 0 : a.bn_mask != nullptr;
-    const bool has_bn_act = FL >= 0 ? false : a.bn_act != nullptr;
-    const bool has_in_mask = FL >= 0 ? (FL & SPK_FL_INMASK) != 0 : a.in_mask != nullptr;
-    const bool has_in_act = FL >= 0 ? false : a.in_act != nullptr;
-    const bool has_side_dz = FL >= 0 ? false : a.side_dz != nullptr;
+    // FL == SPK_EPI_WMASK: the length-masked instantiation - the flag word is read at run time as with FL < 0, and the epilogue
+    // applies the width mask (SPK_EPI_WMASK, below).  Every other instantiation has no trace of the mask.
+    constexpr bool WM = FL >= 0 && (FL & SPK_EPI_WMASK) != 0;
+    constexpr bool FLC = FL >= 0 && !WM;
+    const int flags = FLC ? (FL & 0xFFFFF) : a.flags;
+    const bool has_add_mask = FLC ? (FL & SPK_FL_ADDMASK) != 0 : a.add_mask != nullptr;
+    const bool has_bn_mask = FLC ? (FL & SPK_FL_BNMASK) != 0 : a.bn_mask != nullptr;
+    const bool has_bn_act = FLC ? false : a.bn_act != nullptr;
+    const bool has_in_mask = FLC ? (FL & SPK_FL_INMASK) != 0 : a.in_mask != nullptr;
+    const bool has_in_act = FLC ? false : a.in_act != nullptr;
+    const bool has_side_dz = FLC ? false : a.side_dz != nullptr;
 
     int lbase[M16 ? 2 * MT : MT], obase[MT], opix[MT];      // opix: output pixel index (the masks are addressed per pixel)
 #pragma unroll
@@ -1133,15 +1138,27 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
     // batch costs registers (84 -> 126 on the 32-channel forward kernel: one wave per SIMD less on an HBM-bound kernel,
     // measured +30 % time), and conv_pipe_kernel with conversion while staging sits at its 256-register launch bound.
     constexpr bool EPB = SPK_EPI_BATCH && (PRE || (BNBWD && !PIPE));
+    static_assert(!(WM && (EPB || BNBWD || PRE)), "the length mask is a plain-input forward epilogue");
     if constexpr (!EPB) {
+        // WM (SPK_EPI_WMASK, length-masked eval forward; a plain-input forward form - the C entry refuses the others): a pixel at
+        // output column x >= wlen[b] is stored as 0 after the whole epilogue, so the next convolution sees exactly the zero padding
+        // of a run of that utterance alone; a 0 leaves out_amax and the statistics as they are
+        const int wl = WM ? a.wlen[b] : 0;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             to_slab(i);
+            int wz = 0;              // this lane's row r of m-tile i lies in the masked tail (rows as obase / opix above)
+            if constexpr (WM) {
+                const int q = (wave * MT + i) * 32 + r;
+                const int ly = q / a.TW;
+                wz = (ox0 + q - ly * a.TW) * a.OS + a.oox >= wl;
+            }
             // same-wave LDS traffic is ordered; the compiler inserts the lgkmcnt wait for the reads below
 #pragma unroll
             for (int k = 0; k < 32 / RPP; ++k) {
                 const int row = k * RPP + qr;
                 const int ob = __shfl(obase[i], row, 64);
+                const int wz_row = WM ? __shfl(wz, row, 64) : 0;
                 f32x4 v = *(const f32x4*)(slab + row * LW + qc * 4);
 #ifdef ABL_NO_EPI
                 asm volatile("" ::"v"(v));
@@ -1167,6 +1184,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                         v[2] = fmaxf(v[2], 0.f);
                         v[3] = fmaxf(v[3], 0.f);
                     }
+                    if (wz_row) v = (f32x4){0.f, 0.f, 0.f, 0.f};
                     conv_st(dst, v);
                     out_mx = fmaxf(fmaxf(out_mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
                     if (flags & SPK_EPI_BNBWD) {

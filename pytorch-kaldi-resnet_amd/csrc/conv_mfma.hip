@@ -33,13 +33,15 @@ static int launch_conv(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
     // kernel an occupancy step
     if (a.flags & SPK_IN_BNBWD)
         hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, true, 0>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    else if (a.flags & SPK_EPI_WMASK)          // length-masked eval forward (conv_kernel.h, WM)
+        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, false, 0, SPK_EPI_WMASK>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
     else
         hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, false, 0>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
     SPK_LAUNCH_CHECK("spk_conv_mfma");
     return 0;
 }
 
-extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, const float* in_scale,
+static int conv_mfma_entry(const float* in, const float* wpk, float* out, const float* in_scale,
                              const float* in_shift, const float* epi_scale, const float* epi_shift,
                              const float* epi_add, const float* in_raw, const float* in_act, const float* in_bn4,
                              const float* in_coef, const unsigned* in_mask, const unsigned* bn_mask, const unsigned* add_mask, float* side_draw,
@@ -49,8 +51,15 @@ extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, cons
                              int OW, int OHf, int OWf, int Cout, int IS, int OS, int ooy, int oox, int ntaps,
                              const int* tap_dy, const int* tap_dx, const int* tap_w, int TH, int TW, int MT,
                              int NT, int kc, int ips, int flags, int split, const unsigned* in_amax, unsigned* out_amax,
-                             unsigned* side_amax, void* stream) {
+                             unsigned* side_amax, const int* wlen, void* stream) {
     SPK_REQUIRE(in && wpk && out, "spk_conv_mfma: null pointer");
+    // length mask (spk_conv_mfma_len): implemented in the per-pass epilogue of conv_mfma_kernel and conv_pipe_kernel (plain input,
+    // M16 included); the batched epilogue of the data-gradient forms and the wave-specialised kernel do not have it
+    SPK_REQUIRE(!(flags & SPK_EPI_WMASK) || wlen, "spk_conv_mfma: SPK_EPI_WMASK needs wlen (spk_conv_mfma_len)");
+    SPK_REQUIRE(!wlen || (flags & SPK_EPI_WMASK), "spk_conv_mfma_len: wlen given without SPK_EPI_WMASK");
+    SPK_REQUIRE(!(flags & SPK_EPI_WMASK) || !(flags & (SPK_IN_BNBWD | SPK_EPI_BNBWD | SPK_IN_PRESPLIT | SPK_SIDE_PRESPLIT | SPK_CONV_WS)),
+                "spk_conv_mfma_len: SPK_EPI_WMASK is implemented for the forward forms only (no IN_BNBWD, EPI_BNBWD, IN_PRESPLIT, "
+                "SIDE_PRESPLIT or CONV_WS)");
     SPK_REQUIRE(B > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0, "spk_conv_mfma: empty tensor");
     SPK_REQUIRE(Cin % 32 == 0 && Cin > 0, "spk_conv_mfma: Cin=%d must be a multiple of 32", Cin);
     // wave-specialised kernel: bits 8-9 of flags = log2 of WC, the number of consumer-wave channel groups (1, 2, 4)
@@ -96,6 +105,7 @@ extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, cons
     a.in_mask = in_mask; a.bn_mask = bn_mask; a.add_mask = add_mask;
     a.in_amax = in_amax; a.out_amax = out_amax; a.side_amax = side_amax;
     a.in_sigma = SPK_F16_ACT_SIGMA; a.w_amax = nullptr;
+    a.wlen = wlen;
     if (split == 3) {       // fp16-split packs start with a 16-byte header: the float bits of max|w|
         a.w_amax = (const unsigned*)wpk;
         a.wpk = wpk + 4;
@@ -180,4 +190,36 @@ extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, cons
 #undef CASE
     spk_set_error("spk_conv_mfma: unsupported tile config MT=%d NT=%d", MT, NT);
     return -1;
+}
+
+extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, const float* in_scale,
+                             const float* in_shift, const float* epi_scale, const float* epi_shift,
+                             const float* epi_add, const float* in_raw, const float* in_act, const float* in_bn4,
+                             const float* in_coef, const unsigned* in_mask, const unsigned* bn_mask, const unsigned* add_mask, float* side_draw,
+                             float* side_dz, const float* bn_raw, const float* bn_act, const float* bn4, float* stats, int B, int IH,
+                             int IW, int Cin, int OH, int OW, int OHf, int OWf, int Cout, int IS, int OS, int ooy, int oox, int ntaps,
+                             const int* tap_dy, const int* tap_dx, const int* tap_w, int TH, int TW, int MT,
+                             int NT, int kc, int ips, int flags, int split, const unsigned* in_amax, unsigned* out_amax,
+                             unsigned* side_amax, void* stream) {
+    return conv_mfma_entry(in, wpk, out, in_scale, in_shift, epi_scale, epi_shift, epi_add, in_raw, in_act, in_bn4, in_coef, in_mask,
+                           bn_mask, add_mask, side_draw, side_dz, bn_raw, bn_act, bn4, stats, B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, IS,
+                           OS, ooy, oox, ntaps, tap_dy, tap_dx, tap_w, TH, TW, MT, NT, kc, ips, flags, split, in_amax, out_amax,
+                           side_amax, nullptr, stream);
+}
+
+// the same with the length mask: wlen = device [B] valid output widths, flags must carry SPK_EPI_WMASK
+extern "C" int spk_conv_mfma_len(const float* in, const float* wpk, float* out, const float* in_scale,
+                                 const float* in_shift, const float* epi_scale, const float* epi_shift,
+                                 const float* epi_add, const float* in_raw, const float* in_act, const float* in_bn4,
+                                 const float* in_coef, const unsigned* in_mask, const unsigned* bn_mask, const unsigned* add_mask,
+                                 float* side_draw, float* side_dz, const float* bn_raw, const float* bn_act, const float* bn4,
+                                 float* stats, int B, int IH, int IW, int Cin, int OH, int OW, int OHf, int OWf, int Cout, int IS,
+                                 int OS, int ooy, int oox, int ntaps, const int* tap_dy, const int* tap_dx, const int* tap_w, int TH,
+                                 int TW, int MT, int NT, int kc, int ips, int flags, int split, const unsigned* in_amax,
+                                 unsigned* out_amax, unsigned* side_amax, const int* wlen, void* stream) {
+    SPK_REQUIRE(wlen && (flags & SPK_EPI_WMASK), "spk_conv_mfma_len: needs wlen and SPK_EPI_WMASK");
+    return conv_mfma_entry(in, wpk, out, in_scale, in_shift, epi_scale, epi_shift, epi_add, in_raw, in_act, in_bn4, in_coef, in_mask,
+                           bn_mask, add_mask, side_draw, side_dz, bn_raw, bn_act, bn4, stats, B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, IS,
+                           OS, ooy, oox, ntaps, tap_dy, tap_dx, tap_w, TH, TW, MT, NT, kc, ips, flags, split, in_amax, out_amax,
+                           side_amax, wlen, stream);
 }

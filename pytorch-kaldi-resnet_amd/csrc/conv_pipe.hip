@@ -28,6 +28,11 @@ static int launch_pipe(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
             // else (eval-mode epilogues, activation tensors as masks): the generic instantiation
             const int var = b.flags | (b.add_mask ? SPK_FL_ADDMASK : 0) | (b.bn_mask ? SPK_FL_BNMASK : 0) | (b.bn_act ? (1 << 30) : 0);
 #define LP(PREV, VV) hipLaunchKernelGGL((conv_pipe_kernel<MT, NT, false, false, PREV, true, VV>), dim3(a.nblocks), dim3(256), lds_bytes, st, b)
+            if (b.flags & SPK_EPI_WMASK) {     // length-masked eval forward (plain input)
+                LP(false, SPK_EPI_WMASK);
+                SPK_LAUNCH_CHECK("spk_conv_mfma(pipe)");
+                return 0;
+            }
 #ifdef SPK_NO_FL_VARIANTS
             if (a.flags & SPK_IN_PRESPLIT) LP(true, -1); else LP(false, -1);
 #else
@@ -51,7 +56,9 @@ static int launch_pipe(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
             spk_set_error("spk_conv_mfma: no 16x16x32 pipelined kernel for MT=%d NT=%d", MT, NT);
             return -1;
         }
-    } else if (a.flags & SPK_IN_PRESPLIT)        // f16 pair input: staging by plain copy
+    } else if (a.flags & SPK_EPI_WMASK)          // length-masked eval forward (conv_kernel.h, WM)
+        hipLaunchKernelGGL((conv_pipe_kernel<MT, NT, false, false, false, false, SPK_EPI_WMASK>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    else if (a.flags & SPK_IN_PRESPLIT)        // f16 pair input: staging by plain copy
         hipLaunchKernelGGL((conv_pipe_kernel<MT, NT, false, false, true>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
     else
         hipLaunchKernelGGL((conv_pipe_kernel<MT, NT, false>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);

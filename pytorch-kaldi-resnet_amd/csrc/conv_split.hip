@@ -24,6 +24,8 @@ static int launch_split(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
         }
 #endif
         hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, true, SPLIT>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    } else if (a.flags & SPK_EPI_WMASK) {      // length-masked eval forward (conv_kernel.h, WM)
+        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, false, SPLIT, SPK_EPI_WMASK>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
     } else {
 #ifndef SPK_NO_FL_VARIANTS
         // the forward launches of the training step as compile-time flag variants (conv_kernel.h, FL), f16x3 mode

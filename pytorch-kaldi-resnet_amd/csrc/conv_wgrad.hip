@@ -277,6 +277,7 @@ extern "C" int spk_conv_wgrad(const float* x, const float* dy, float* dw, float*
                               int ksize, int stride, int TH, int TW, int WN, int nsplit, int flags, int accumulate,
                               int split, const unsigned* dy_amax, const unsigned* x_amax, void* stream) {
     SPK_REQUIRE(x && dy && dw && partial, "spk_conv_wgrad: null pointer");
+    SPK_REQUIRE(!(flags & SPK_EPI_WMASK), "spk_conv_wgrad: SPK_EPI_WMASK is a forward-epilogue flag (spk_conv_mfma_len)");
     SPK_REQUIRE(ksize == 1 || ksize == 3, "spk_conv_wgrad: ksize=%d unsupported", ksize);
     SPK_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, "spk_conv_wgrad: channels (%d,%d) must be multiples of 32", Cin, Cout);
     SPK_REQUIRE(WN == 1 || WN == 2 || WN == 4, "spk_conv_wgrad: WN=%d", WN);

@@ -8,8 +8,12 @@
 // The output index order is nn.Flatten(1,-1) of the reference's [B,C,2H] / [B,C,H,1] tensors (:352).
 #include "spk_common.h"
 
+// LEN (spk_stats_pool_fwd_len): image b has wlen[b] valid frames (clamped to [1, W]); the statistics of a row are those of its
+// valid frames alone, in the same two-pass order as a run at that width (for wlen[b] == 1 the unbiased variance is 0/0 = NaN,
+// as torch.var_mean of one frame; that row only)
+template <bool LEN>
 __global__ __launch_bounds__(256) void stats_pool_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int B,
-                                                             int H, int W, int C, int mode) {
+                                                             int H, int Wp, int C, int mode, const int* __restrict__ wlen) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)B * H * C;
     if (idx >= total) return;
@@ -17,7 +21,8 @@ __global__ __launch_bounds__(256) void stats_pool_fwd_kernel(const float* __rest
     const long long bh = idx / C;
     const int h = (int)(bh % H);
     const int b = (int)(bh / H);
-    const float* p = x + (size_t)bh * W * C + c;
+    const float* p = x + (size_t)bh * Wp * C + c;
+    const int W = LEN ? max(1, min(wlen[b], Wp)) : Wp;
     float s = 0.f;
     for (int w = 0; w < W; ++w) s += p[(size_t)w * C];
     const float mean = s / (float)W;
@@ -79,9 +84,21 @@ extern "C" int spk_stats_pool_fwd(const float* x, float* out, int B, int H, int 
     SPK_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "spk_stats_pool_fwd: empty input");
     SPK_REQUIRE(mode == 0 || mode == 1, "spk_stats_pool_fwd: mode=%d", mode);
     const long long total = (long long)B * H * C;
-    hipLaunchKernelGGL(stats_pool_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out,
-                       B, H, W, C, mode);
+    hipLaunchKernelGGL(stats_pool_fwd_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                       out, B, H, W, C, mode, nullptr);
     SPK_LAUNCH_CHECK("spk_stats_pool_fwd");
+    return 0;
+}
+
+extern "C" int spk_stats_pool_fwd_len(const float* x, float* out, const int* wlen, int B, int H, int W, int C, int mode,
+                                      void* stream) {
+    SPK_REQUIRE(x && out && wlen, "spk_stats_pool_fwd_len: null pointer");
+    SPK_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "spk_stats_pool_fwd_len: empty input");
+    SPK_REQUIRE(mode == 0 || mode == 1, "spk_stats_pool_fwd_len: mode=%d", mode);
+    const long long total = (long long)B * H * C;
+    hipLaunchKernelGGL(stats_pool_fwd_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                       out, B, H, W, C, mode, wlen);
+    SPK_LAUNCH_CHECK("spk_stats_pool_fwd_len");
     return 0;
 }
 

@@ -7,11 +7,14 @@
 
 #define STEM_C 32
 
+// LEN (spk_stem_conv_fwd_len): image b is an utterance of len[b] <= T frames padded to T - frames t >= len[b] are read as 0 (the
+// padding may hold anything, NaN included) and the outputs there are stored as 0, outside the absmax and the statistics
+template <bool LEN>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        float* __restrict__ out, float* __restrict__ stats,
                                                        const float* __restrict__ epi_scale,
                                                        const float* __restrict__ epi_shift, int B, int F, int T,
-                                                       int flags, unsigned* __restrict__ amax_out) {
+                                                       int flags, unsigned* __restrict__ amax_out, const int* __restrict__ len) {
     __shared__ float red[4][STEM_C][2];
     float mx = 0.f;
     const int tid = threadIdx.x, cg = tid & 3, pl = tid >> 2;
@@ -35,14 +38,16 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
         const int rem = (int)(p - (long long)b * FT);
         const int f = rem / T, t0 = rem - f * T;
         const float* xb = x + (size_t)b * FT;
+        const int Tb = LEN ? min(len[b], T) : T;          // frames of this utterance
         float xv[9];
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int ff = f + kh - 1, tt = t0 + kw - 1;
-                xv[kh * 3 + kw] = (ff >= 0 && ff < F && tt >= 0 && tt < T) ? xb[ff * T + tt] : 0.f;
+                xv[kh * 3 + kw] = (ff >= 0 && ff < F && tt >= 0 && tt < Tb) ? xb[ff * T + tt] : 0.f;
             }
+        const bool tail = LEN && t0 >= Tb;
         float o[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -51,6 +56,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
             for (int t = 0; t < 9; ++t) v = fmaf(xv[t], wr[t][c], v);
             if (flags & SPK_EPI_AFFINE) v = v * es[c] + eh[c];
             if (flags & SPK_EPI_RELU) v = fmaxf(v, 0.f);
+            if (tail) v = 0.f;
             o[c] = v;
             mx = fmaxf(mx, fabsf(v));
             ssum[c] += v;
@@ -104,9 +110,24 @@ extern "C" int spk_stem_conv_fwd(const float* x, const float* w, float* out, flo
     SPK_REQUIRE(B > 0 && F > 0 && T > 0, "spk_stem_conv_fwd: empty input");
     SPK_REQUIRE(!(flags & SPK_EPI_STATS) || stats, "spk_stem_conv_fwd: EPI_STATS needs a stats buffer");
     SPK_REQUIRE(!(flags & SPK_EPI_AFFINE) || (epi_scale && epi_shift), "spk_stem_conv_fwd: EPI_AFFINE needs scale/shift");
-    hipLaunchKernelGGL(stem_fwd_kernel, dim3(spk_stem_fwd_blocks(B, F, T)), dim3(256), 0, (hipStream_t)stream, x, w, out,
-                       stats, epi_scale, epi_shift, B, F, T, flags, amax_out);
+    SPK_REQUIRE(!(flags & SPK_EPI_WMASK), "spk_stem_conv_fwd: SPK_EPI_WMASK needs the lengths (spk_stem_conv_fwd_len)");
+    hipLaunchKernelGGL(stem_fwd_kernel<false>, dim3(spk_stem_fwd_blocks(B, F, T)), dim3(256), 0, (hipStream_t)stream, x, w, out,
+                       stats, epi_scale, epi_shift, B, F, T, flags, amax_out, nullptr);
     SPK_LAUNCH_CHECK("spk_stem_conv_fwd");
+    return 0;
+}
+
+extern "C" int spk_stem_conv_fwd_len(const float* x, const float* w, float* out, float* stats, const float* epi_scale,
+                                     const float* epi_shift, int B, int F, int T, int flags, unsigned* amax_out, const int* len,
+                                     void* stream) {
+    SPK_REQUIRE(x && w && out && len, "spk_stem_conv_fwd_len: null pointer");
+    SPK_REQUIRE(B > 0 && F > 0 && T > 0, "spk_stem_conv_fwd_len: empty input");
+    SPK_REQUIRE(flags & SPK_EPI_WMASK, "spk_stem_conv_fwd_len: flags must carry SPK_EPI_WMASK");
+    SPK_REQUIRE(!(flags & SPK_EPI_STATS) || stats, "spk_stem_conv_fwd_len: EPI_STATS needs a stats buffer");
+    SPK_REQUIRE(!(flags & SPK_EPI_AFFINE) || (epi_scale && epi_shift), "spk_stem_conv_fwd_len: EPI_AFFINE needs scale/shift");
+    hipLaunchKernelGGL(stem_fwd_kernel<true>, dim3(spk_stem_fwd_blocks(B, F, T)), dim3(256), 0, (hipStream_t)stream, x, w, out,
+                       stats, epi_scale, epi_shift, B, F, T, flags, amax_out, len);
+    SPK_LAUNCH_CHECK("spk_stem_conv_fwd_len");
     return 0;
 }
 

@@ -171,4 +171,62 @@ extern "C" int spk_ark_read_crop(int B, const char* const* paths, const int64_t*
     return fail.load() ? -8 : 0;
 }
 
+// whole utterances of up to T frames into [B][F][T], the frames past rows[b] zero-filled (a length-sorted padded batch for the
+// length-masked predict; the lengths go to the model separately)
+extern "C" int spk_ark_read_padded(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows, int F, int T,
+                                   float* out, int nthreads) {
+    if (B <= 0 || F <= 0 || T <= 0 || !out) {
+        set_err("spk_ark_read_padded: bad arguments");
+        return -1;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (rows[b] < 1 || rows[b] > T) {
+            set_err("spk_ark_read_padded: utterance %d has %d frames, outside [1, T=%d]", b, rows[b], T);
+            return -7;
+        }
+    }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > B) nthreads = B;
+    std::atomic<int> next(0), fail(0);
+    auto work = [&]() {
+        std::vector<float> tmp((size_t)T * F);
+        for (;;) {
+            const int b = next.fetch_add(1);
+            if (b >= B || fail.load()) break;
+            int fd = get_fd(paths[b]);
+            if (fd < 0) {
+                set_err("cannot open %s", paths[b]);
+                fail.store(1);
+                break;
+            }
+            const int R = rows[b];
+            if (!pread_all(fd, tmp.data(), (size_t)R * F * sizeof(float), data_offsets[b])) {
+                set_err("%s: short read of %d frames", paths[b], R);
+                fail.store(1);
+                break;
+            }
+            float* dst = out + (size_t)b * F * T;     // [F][T], time innermost; the same blocked transpose as spk_ark_read_crop
+            constexpr int TB = 16;
+            for (int t0 = 0; t0 < R; t0 += TB) {
+                const int t1 = t0 + TB < R ? t0 + TB : R;
+                for (int f0 = 0; f0 < F; f0 += TB) {
+                    const int f1 = f0 + TB < F ? f0 + TB : F;
+                    for (int f = f0; f < f1; ++f) {
+                        float* d = dst + (size_t)f * T;
+                        const float* sp = tmp.data() + f;
+                        for (int t = t0; t < t1; ++t) d[t] = sp[(size_t)t * F];
+                    }
+                }
+            }
+            if (R < T)
+                for (int f = 0; f < F; ++f) memset(dst + (size_t)f * T + R, 0, (size_t)(T - R) * sizeof(float));
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int i = 1; i < nthreads; ++i) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return fail.load() ? -8 : 0;
+}
+
 extern "C" int spk_io_version(void) { return 100; }

@@ -221,14 +221,20 @@ class Engine:
         if self.window_counts is not None and slot is not None:
             ops.f16_window_count(x, slot, self.window_counts, affine=affine, pairs=pairs)
 
-    def trunk_eval(self, x):
+    def trunk_eval(self, x, wl=None):
+        """wl: None, or int32 device [4][B] valid widths per stage (stage_widths): the length-masked forward of a padded batch.
+        Every convolution whose output another convolution or the pooling reads is masked to its stage width (the stem, and each
+        block's convolutions - the last one after the residual add); the downsample branch is not: its output only meets the
+        residual add, which the block's last convolution masks."""
         self._repack(False)
         pool = self._fwd_pool(x.device)
         take = (lambda: pool.take()) if pool is not None else (lambda: None)
         f16 = ops.split_for(3) == 3
         e = self.stem_bn.eval_coeffs()
         a_amax = take()
-        a, _ = ops.stem_fwd(x, self.stem_conv.h.weight.data, epi_affine=(e[0], e[1]), relu=True, amax_out=a_amax)
+        a, _ = ops.stem_fwd(x, self.stem_conv.h.weight.data, epi_affine=(e[0], e[1]), relu=True, amax_out=a_amax,
+                            wlen=None if wl is None else wl[0])
+        stage = 0               # log2 of the trunk's stride so far: row of wl
         for b in self.blocks:
             evs = [bn.eval_coeffs() for bn in b.bns]
             if b.ds is not None:
@@ -242,23 +248,59 @@ class Engine:
             for i, (c, ev) in enumerate(zip(b.convs, evs)):
                 last = i == n - 1
                 o_amax = take()
+                if c.stride == 2:
+                    stage += 1
                 h, _ = ops.conv_fwd(h, c.wpk, c.cout, c.k, c.stride, epi_affine=(ev[0], ev[1]),
                                     epi_add=res if last else None, relu=True,
-                                    in_amax=h_amax if ops.split_for(c.k) == 3 else None, out_amax=o_amax)
+                                    in_amax=h_amax if ops.split_for(c.k) == 3 else None, out_amax=o_amax,
+                                    wlen=None if wl is None else wl[stage])
                 h_amax = o_amax
             a, a_amax = h, h_amax
         return a
 
-    def embed_eval(self, x):
-        feat = self.trunk_eval(x)
-        pooled = ops.stats_pool_fwd(feat, self.pool_mode)
+    def embed_eval(self, x, wl=None):
+        feat = self.trunk_eval(x, wl)
+        pooled = ops.stats_pool_fwd(feat, self.pool_mode, wlen=None if wl is None else wl[3])
         return ops.linear_fwd(pooled, self.m.fc1.weight.data, self.m.fc1.bias.data)
 
-    def predict(self, x):
+    @staticmethod
+    def stage_widths(lengths, B, T, device):
+        """Validated per-utterance lengths -> int32 [4][B] on `device`: the valid widths of the stem and layer 1 (L), then of the
+        three stride-2 stages, W' = ceil(W / 2) each (the output width of a 3x3 pad-1 and of a 1x1 convolution at stride 2), so the
+        pooled width is ceil(L / 8).  `lengths`: a sequence of ints or an integer tensor on any device, 1 <= L[b] <= T."""
+        if isinstance(lengths, torch.Tensor):
+            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+                raise TypeError("lengths must be integers, got a %s tensor" % lengths.dtype)
+            L = lengths.detach().to("cpu", torch.int64).reshape(-1)
+            if lengths.dim() != 1:
+                raise ValueError("lengths must be one-dimensional [B], got shape %s" % (tuple(lengths.shape),))
+        else:
+            vals = list(lengths)
+            if not all(isinstance(v, int) or (hasattr(v, "__index__") and not isinstance(v, (bool, float))) for v in vals) \
+                    or any(isinstance(v, bool) for v in vals):
+                raise TypeError("lengths must be integers")
+            L = torch.tensor([int(v) for v in vals], dtype=torch.int64)
+        if L.numel() != B:
+            raise ValueError("lengths has %d entries for a batch of %d utterances" % (L.numel(), B))
+        if B and (int(L.min()) < 1 or int(L.max()) > T):
+            raise ValueError("lengths must lie in [1, T=%d], got min %d max %d" % (T, int(L.min()), int(L.max())))
+        w = [L]
+        for _ in range(3):
+            w.append((w[-1] + 1) // 2)
+        return torch.stack(w).to(torch.int32).to(device)
+
+    def predict(self, x, lengths=None):
         """scripts/model.py:402-409.  Uses BN batch statistics when the module is in train mode, exactly like
-        the reference would; decode.py always calls it under model.eval()."""
+        the reference would; decode.py always calls it under model.eval().
+        lengths (eval mode only): per-utterance frame counts of a padded batch x [B, F, T] - row b is the embedding of
+        x[b, :, :lengths[b]] alone, whatever the padding holds (length-masked stem, convolutions and pooling)."""
         x = self._check_input(x)
         with torch.no_grad():
+            if lengths is not None:
+                if self.m.training:
+                    raise RuntimeError("predict(lengths=...) needs eval mode: with BatchNorm batch statistics a padded batch has "
+                                       "no per-utterance meaning (call model.eval() first)")
+                return self.embed_eval(x, self.stage_widths(lengths, x.shape[0], x.shape[2], x.device))
             if self.m.training:
                 emb, _ = self._embed_train(x, save=False)
                 return emb

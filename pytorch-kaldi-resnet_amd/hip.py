@@ -15,6 +15,7 @@ IN_PRESPLIT, SIDE_PRESPLIT, DY_PRESPLIT = 1 << 14, 1 << 15, 1 << 16     # f16 pa
 CONV_M16 = 1 << 17      # 16x16x32 form of the pipelined convolution
 WGRAD_NOSHIFT = 1 << 18  # 3x3 grouped weight gradient: plain K loop instead of the shifted-window form (A/B)
 WGRAD_M16 = 1 << 19      # 3x3 grouped weight gradient on 16x16x32 with dy (a pair tensor) staged by LDS DMA
+EPI_WMASK = 1 << 24     # length-masked epilogue: outputs at width x >= wlen[b] stored as 0 (spk_conv_mfma_len, spk_stem_conv_fwd_len)
 MASK_NONE, MASK_ACT, MASK_RAW, MASK_BITS = 0, 1, 2, 3
 
 _P = ctypes.c_void_p
@@ -31,6 +32,7 @@ _SIGS = {
     "spk_build_flags": [],
     "spk_pack_conv_weights_batched": [_P, _I, _I, _I, _P],
     "spk_conv_mfma": [_P] * 21 + [_I] * 14 + [_IP, _IP, _IP] + [_I] * 8 + [_P, _P, _P, _P],
+    "spk_conv_mfma_len": [_P] * 21 + [_I] * 14 + [_IP, _IP, _IP] + [_I] * 8 + [_P, _P, _P, _P, _P],
     "spk_conv3x3_c32_stream": [_P] * 6 + [_I] * 4 + [_P, _P, _I, _P],
     "spk_conv1x1_stream": [_P] * 11 + [_L, _I, _I, _P, _P, _I, _P],
     "spk_conv1x1_stream_rows": [_I, _I],
@@ -39,6 +41,7 @@ _SIGS = {
     "spk_wgrad_reduce": [_P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stem_fwd_blocks": [_I, _I, _I],
     "spk_stem_conv_fwd": [_P] * 6 + [_I] * 4 + [_P, _P],
+    "spk_stem_conv_fwd_len": [_P] * 6 + [_I] * 4 + [_P, _P, _P],
     "spk_stem_wgrad_blocks": [_I, _I, _I],
     "spk_stem_conv_wgrad": [_P] * 4 + [_I] * 4 + [_P],
     "spk_bn_stats_blocks": [_L, _I],
@@ -54,6 +57,7 @@ _SIGS = {
     "spk_f16_window_count": [_P, _P, _P, _L, _I, _P, _I, _P, _P],
     "spk_affine_estimate": [_P, _P, _I, _P, _P, _P],
     "spk_stats_pool_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "spk_stats_pool_fwd_len": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stats_pool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "spk_gemm_f32": [_P] * 4 + [_I] * 3 + [_L] * 5 + [_F, _I, _P, _P],
     "spk_gemm_splitk": [_I, _I, _I],

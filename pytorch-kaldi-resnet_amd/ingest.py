@@ -31,6 +31,7 @@ def lib():
         l.spk_ark_probe.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, i64p]
         l.spk_ark_read_crop.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_int]
+        l.spk_ark_read_padded.argtypes = [ctypes.c_int, cpp, i64p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         l.spk_text_vectors_bound.argtypes = [ctypes.c_int, ctypes.c_int, cpp]
         l.spk_text_vectors_bound.restype = ctypes.c_int64
         l.spk_format_text_vectors.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, cpp, ctypes.c_char_p, ctypes.c_int64,
@@ -99,6 +100,47 @@ class ArkTable:
                                        st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), F, T, out.data_ptr(), nthreads),
                "spk_ark_read_crop")
         return out
+
+    def read_padded(self, idx, T, out, nthreads=4):
+        """Whole utterances idx (each of 1..T frames) into a contiguous float32 host tensor out [B, F, T] (ideally pinned), the
+        frames past each utterance's length zero-filled; self.rows[idx] are the lengths to pass to predict(x, lengths=...)."""
+        B = len(idx)
+        F = int(self.cols[idx[0]])
+        assert out.is_contiguous() and tuple(out.shape) == (B, F, T) and out.dtype == torch.float32
+        assert (self.cols[idx] == F).all()
+        arr = (ctypes.c_char_p * B)(*[self._cpaths[self.paths[i]].value for i in idx])
+        doff = np.ascontiguousarray(self.data_off[idx])
+        rows = np.ascontiguousarray(self.rows[idx])
+        _check(lib().spk_ark_read_padded(B, arr, doff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), F, T, out.data_ptr(), nthreads),
+               "spk_ark_read_padded")
+        return out
+
+
+def pad_batches(lengths, batch_size, max_pad_ratio=0.1, quantum=8):
+    """Length-sorted padded batches for whole-utterance extraction: a list of (indices, T_pad).  Utterances are taken in order of
+    length (stable) and a batch grows until it holds batch_size of them or one more would make its padded frames
+    len * T_pad exceed (1 + max_pad_ratio) x its real frames; T_pad = the batch's longest utterance rounded up to `quantum`.
+    Every index lands in exactly one batch; a batch of one may exceed the ratio by its rounding."""
+    L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if batch_size < 1 or quantum < 1 or max_pad_ratio < 0:
+        raise ValueError("pad_batches: batch_size >= 1, quantum >= 1, max_pad_ratio >= 0")
+    if L.size and L.min() < 1:
+        raise ValueError("pad_batches: every length must be >= 1")
+    order = np.argsort(L, kind="stable")
+    batches, i, n = [], 0, len(order)
+    while i < n:
+        j, real = i + 1, int(L[order[i]])
+        while j < n and j - i < batch_size:
+            t_pad = -(-int(L[order[j]]) // quantum) * quantum
+            if (j - i + 1) * t_pad > (1.0 + max_pad_ratio) * (real + int(L[order[j]])):
+                break
+            real += int(L[order[j]])
+            j += 1
+        idx = order[i:j]
+        batches.append((idx, -(-int(L[idx[-1]]) // quantum) * quantum))
+        i = j
+    return batches
 
 
 class NativeTrainLoader:

@@ -210,9 +210,12 @@ class NeuralSpeakerModel(nn.Module):
         """Logits [B, spk_num] (scripts/model.py:374-400). Differentiable: loss.backward() fills .grad."""
         return self.engine().forward_logits(x, y)
 
-    def predict(self, x):
-        """Embeddings [B, 256] = fc1 output (scripts/model.py:402-409)."""
-        return self.engine().predict(x)
+    def predict(self, x, lengths=None):
+        """Embeddings [B, 256] = fc1 output (scripts/model.py:402-409).
+        lengths: optional per-utterance frame counts [B] (list or integer tensor, any device, 1 <= L[b] <= T) of a padded batch
+        x [B, F, T], eval mode only: row b is then the embedding of x[b:b+1, :, :lengths[b]] predicted alone - the frames past
+        lengths[b] are ignored whatever they hold.  None: the plain batched predict."""
+        return self.engine().predict(x, lengths)
 
     def loadParameters(self, loaded_state):
         """scripts/model.py:415-432: name match, strip 'module.', skip on shape mismatch, same messages."""

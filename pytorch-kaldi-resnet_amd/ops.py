@@ -7,7 +7,7 @@ import torch
 
 from . import hip, tiling
 from .hip import (CONV_M16, CONV_PIPE, CONV_WS, DY_PRESPLIT, IN_PRESPLIT, SIDE_PRESPLIT, WGRAD_GROUPS, EPI_ADD, EPI_AFFINE, EPI_BNBWD, EPI_RELU,
-                  EPI_STATS, IN_AFFINE_RELU, IN_BNBWD, MASK_ACT, MASK_NONE, MASK_RAW,
+                  EPI_STATS, EPI_WMASK, IN_AFFINE_RELU, IN_BNBWD, MASK_ACT, MASK_NONE, MASK_RAW,
                   call, ptr, stream)
 
 BN_EPS = 1e-5
@@ -311,12 +311,14 @@ def _conv3x3_c32_stream(x, wpk, out, in_affine, in_amax, out_amax):
 
 def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, epi_affine, epi_add, relu, want_stats,
                  bn_bwd=None, in_bnbwd=None, side=None, split=0, add_mask=None, in_amax=None, out_amax=None, side_amax=None,
-                 in_presplit=False, side_presplit=False):
+                 in_presplit=False, side_presplit=False, wlen=None):
     B, IH, IW, Cin = x.shape
     OHf, OWf = out.shape[1], out.shape[2]
+    if wlen is not None:
+        _check_wlen(wlen, B)
     # Streaming 3x3 forward kernel of the 32-channel layer (csrc/conv3x3_c32_stream.hip): 32 -> 32 channels, stride 1, the forward tap
     # order, raw output + statistics, plain or fused-BatchNorm input.  (A data gradient has mirrored taps: general kernel.)
-    if (STREAM_C32 and split == 3 and Cin == 32 and Cout == 32 and IS == 1 and OS == 1 and ooy == 0 and oox == 0
+    if (STREAM_C32 and wlen is None and split == 3 and Cin == 32 and Cout == 32 and IS == 1 and OS == 1 and ooy == 0 and oox == 0
             and (IH, IW) == (OH, OW) == (OHf, OWf) and want_stats and in_bnbwd is None and side is None and epi_affine is None
             and epi_add is None and not relu and bn_bwd is None and not in_presplit and not side_presplit and add_mask is None
             and list(taps) == [(kh - 1, kw - 1, kh * 3 + kw) for kh in range(3) for kw in range(3)] and B * OH * OW * 32 < 2 ** 31 - 65536):
@@ -325,7 +327,7 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
     # (raw output + statistics; data gradients: shortcut add with or without its sign mask, BatchNorm-backward statistics with the
     # mask as sign bits or recomputed from the raw tensor).  Everything else - eval-mode epilogues, strided 1x1, other widths,
     # the fused input BatchNorm backward, an activation tensor as the mask - stays on the general kernel.
-    if (STREAM_1X1 and split == 3 and len(taps) == 1 and taps[0][0] == 0 and taps[0][1] == 0 and IS == 1 and OS == 1 and ooy == 0
+    if (STREAM_1X1 and wlen is None and split == 3 and len(taps) == 1 and taps[0][0] == 0 and taps[0][1] == 0 and IS == 1 and OS == 1 and ooy == 0
             and oox == 0 and Cin == Cout and Cin in (32, 64, 128) and (IH, IW) == (OH, OW) == (OHf, OWf) and in_bnbwd is None
             and side is None and epi_affine is None and not relu and not side_presplit and out is not x
             and (bn_bwd is None or bn_bwd[1] is None or len(bn_bwd) > 3) and B * OH * OW * Cin < 2 ** 31):
@@ -409,11 +411,13 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
         want_stats = True
         flags |= EPI_BNBWD
         assert bn_bwd[0].shape == out.shape and (bn_bwd[1] is None or bn_bwd[1].shape == out.shape)
+    if wlen is not None:
+        flags |= EPI_WMASK
     if want_stats:
         flags |= EPI_STATS
         ntile = (4 // WC) * B * (-(-OH // TH)) * (-(-OW // TW))      # one partial row per wave (per pixel group of waves)
         stats = torch.empty(ntile, Cout, 2, device=x.device, dtype=torch.float32)
-    call("spk_conv_mfma", ptr(x), ptr(wpk), ptr(out),
+    call("spk_conv_mfma" if wlen is None else "spk_conv_mfma_len", ptr(x), ptr(wpk), ptr(out),
          ptr(in_affine[0]) if in_affine else None, ptr(in_affine[1]) if in_affine else None,
          ptr(epi_affine[0]) if epi_affine else None, ptr(epi_affine[1]) if epi_affine else None,
          ptr(epi_add),
@@ -424,7 +428,7 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
          ptr(bn_bwd[0]) if bn_bwd else None, ptr(bn_bwd[1]) if (bn_bwd and bn_mask is None) else None,
          ptr(bn_bwd[2]) if bn_bwd else None, ptr(stats), B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, IS, OS, ooy, oox, len(taps),
          _iarr(dys), _iarr(dxs), _iarr(tws), TH, TW, MT, NT, kc, ips, flags, split, ptr(in_amax), ptr(out_amax), ptr(side_amax),
-         stream(),
+         *(() if wlen is None else (ptr(wlen),)), stream(),
          label=(("conv_ws_kernel<%d,%d,%d,%s,%d>" % (MT, NT, WC, "true" if in_bnbwd is not None else "false", split)) if ws is not None
                 else ("conv_pipe_kernel<%d,%d,false,false%s>" % (MT, NT, (",true,true" if in_presplit else ",false,true") if m16 else (",true" if in_presplit else "")) if in_bnbwd is None
                       else "conv_pipe_kernel<%d,%d,true,true>" % (MT, NT)) if pipe
@@ -440,6 +444,12 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
                        + (x.numel() / 32 if in_mask is not None else 0) + (B * OH * OW * Cout / 32) * ((bn_mask is not None) + (add_mask is not None))
                        + wpk.numel()))
     return stats
+
+
+def _check_wlen(wlen, B):
+    """per-image valid widths of a length-masked launch: a device int32 vector [B]"""
+    if not (wlen.is_cuda and wlen.dtype == torch.int32 and wlen.dim() == 1 and wlen.numel() == B and wlen.is_contiguous()):
+        raise RuntimeError("wlen must be a contiguous int32 device tensor [%d], got %s %s %s" % (B, wlen.dtype, tuple(wlen.shape), wlen.device))
 
 
 def _time_launch(fn, reps=2):
@@ -499,8 +509,10 @@ def _autotune_wgrad(key, x, dy, ksize, stride, in_affine, dy_amax=None, x_amax=N
 
 
 def conv_fwd(x, wpk, Cout, ksize, stride, in_affine=None, epi_affine=None, epi_add=None, relu=False, stats=False,
-             out=None, in_amax=None, out_amax=None):
+             out=None, in_amax=None, out_amax=None, wlen=None):
     """Forward conv on NHWC x with packed weights. Returns (out, stats_partial or None).
+    wlen: int32 device [B] valid output widths (length-masked eval forward): output columns x >= wlen[b] are stored as 0 after the
+    whole epilogue and stay out of out_amax (spk_conv_mfma_len).
     f16x3 operand mode: in_amax = slot with the float bits of the absmax of the STAGED values (x itself, or the
     affine_estimate of relu(x*scale+shift) when in_affine is given); computed here with extra passes when omitted (tests)."""
     B, IH, IW, Cin = x.shape
@@ -514,7 +526,7 @@ def conv_fwd(x, wpk, Cout, ksize, stride, in_affine=None, epi_affine=None, epi_a
     else:
         taps = [(0, 0, 0)]
     st = _conv_launch(x, wpk, out, Cout, taps, stride, 1, 0, 0, OH, OW, in_affine, epi_affine, epi_add, relu, stats,
-                      split=split_for(ksize), in_amax=in_amax, out_amax=out_amax)
+                      split=split_for(ksize), in_amax=in_amax, out_amax=out_amax, wlen=wlen)
     return out, st
 
 
@@ -685,17 +697,22 @@ def conv_wgrad(x, dy, dw, ksize, stride, in_affine=None, accumulate=False, dy_am
     return dw
 
 
-def stem_fwd(x, w, epi_affine=None, relu=False, stats=False, amax_out=None):
-    """x [B][F][T] -> [B][F][T][32] (+ stats partial [nblk][32][2])."""
+def stem_fwd(x, w, epi_affine=None, relu=False, stats=False, amax_out=None, wlen=None):
+    """x [B][F][T] -> [B][F][T][32] (+ stats partial [nblk][32][2]).
+    wlen: int32 device [B] utterance lengths (<= T): frames t >= wlen[b] are read as 0 and stored as 0 (spk_stem_conv_fwd_len)."""
     B, F, T = x.shape
     out = torch.empty(B, F, T, 32, device=x.device, dtype=torch.float32)
     flags = (EPI_AFFINE if epi_affine is not None else 0) | (EPI_RELU if relu else 0) | (EPI_STATS if stats else 0)
     st = None
     if stats:
         st = torch.empty(hip.lib().spk_stem_fwd_blocks(B, F, T), 32, 2, device=x.device, dtype=torch.float32)
-    call("spk_stem_conv_fwd", ptr(x), ptr(w), ptr(out), ptr(st),
-         ptr(epi_affine[0]) if epi_affine else None, ptr(epi_affine[1]) if epi_affine else None, B, F, T, flags, ptr(amax_out),
-         stream())
+    args = (ptr(x), ptr(w), ptr(out), ptr(st), ptr(epi_affine[0]) if epi_affine else None,
+            ptr(epi_affine[1]) if epi_affine else None, B, F, T)
+    if wlen is None:
+        call("spk_stem_conv_fwd", *args, flags, ptr(amax_out), stream())
+    else:
+        _check_wlen(wlen, B)
+        call("spk_stem_conv_fwd_len", *args, flags | EPI_WMASK, ptr(amax_out), ptr(wlen), stream())
     return out, st
 
 
@@ -821,10 +838,15 @@ def bn_bwd_partial(dy, raw, act, bn4, mask_mode, chan_amax=None):
     return part
 
 
-def stats_pool_fwd(x, mode):
+def stats_pool_fwd(x, mode, wlen=None):
+    """wlen: int32 device [B] valid widths: row b pools over its first wlen[b] frames only (spk_stats_pool_fwd_len)"""
     B, H, W, C = x.shape
     out = torch.empty(B, C * H * (2 if mode else 1), device=x.device, dtype=torch.float32)
-    call("spk_stats_pool_fwd", ptr(x), ptr(out), B, H, W, C, mode, stream())
+    if wlen is None:
+        call("spk_stats_pool_fwd", ptr(x), ptr(out), B, H, W, C, mode, stream())
+    else:
+        _check_wlen(wlen, B)
+        call("spk_stats_pool_fwd_len", ptr(x), ptr(out), ptr(wlen), B, H, W, C, mode, stream())
     return out
 
 

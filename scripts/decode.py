@@ -41,6 +41,10 @@ parser.add_argument("--multiprocessing-distributed", action="store_true")
 parser.add_argument("--native-reader", action="store_true",
                     help="read whole utterances with the C++ ark reader, bucketed by length so that any --batch-size works "
                          "with variable-length utterances (the reference is limited to per-process batch 1)")
+parser.add_argument("--pad-batches", action="store_true",
+                    help="with --native-reader and --chunk-size -1: length-sorted batches of up to --batch-size utterances padded to a "
+                         "common length (at most 10%% padded frames, T rounded up to 8) and run through the length-masked "
+                         "predict(x, lengths=...): each embedding is that of its utterance alone")
 parser.add_argument("--out-format", default="text", choices=["text", "fv"],
                     help="text = the reference's 'utt [ v0 ... ]' lines (str(np.float32), ~0.2 ms/utt of Python formatting); "
                          "fv = binary Kaldi float-vector ark, read by the same scoring scripts")
@@ -48,6 +52,10 @@ parser.add_argument("--out-format", default="text", choices=["text", "fv"],
 
 def main():
     args = parser.parse_args()
+    if args.pad_batches and not args.native_reader:
+        parser.error("--pad-batches needs --native-reader")
+    if args.pad_batches and args.chunk_size >= 0:
+        parser.error("--pad-batches extracts whole utterances: use --chunk-size -1")
     if args.dist_url == "env://" and args.world_size == -1:
         args.world_size = int(os.environ["WORLD_SIZE"])
     args.distributed = args.world_size > 1 or args.multiprocessing_distributed
@@ -134,7 +142,9 @@ def sequence_generator(loader, model, out_path, args):
 def native_generator(model, args):
     """Length-bucketed extraction through libspkio: utterances of equal frame count share a batch (whole utterance when
     --chunk-size -1, else the first chunk-size frames... the reference crops at random; extraction of a fixed window is
-    deterministic here), each rank takes every world-th batch."""
+    deterministic here), each rank takes every world-th batch.  --pad-batches: length-sorted batches of unequal lengths padded
+    to a common T (ingest.pad_batches) and the length-masked predict instead of equal-length buckets."""
+    from pytorch_kaldi_resnet_amd import ingest
     from pytorch_kaldi_resnet_amd.ingest import ArkTable
     tab = [l.rstrip().split(None, 1) for l in open(args.decode_scp)]
     utts = [u for u, _ in tab]
@@ -143,14 +153,21 @@ def native_generator(model, args):
     T_of = table.rows if args.chunk_size < 0 else np.minimum(table.rows, args.chunk_size)
     if args.chunk_size >= 0:
         assert (table.rows >= args.chunk_size).all(), "utterance shorter than --chunk-size"
-    order = np.argsort(T_of, kind="stable")
-    batches, i = [], 0
-    while i < len(order):
-        j = i
-        while j < len(order) and j - i < args.batch_size and T_of[order[j]] == T_of[order[i]]:
-            j += 1
-        batches.append(order[i:j])
-        i = j
+    if args.pad_batches:
+        # length-sorted batches padded to a common T_pad, each utterance masked to its own length inside the model
+        batches = ingest.pad_batches(table.rows, args.batch_size)
+        real = int(table.rows.sum())
+        print("=> {} padded batches, padding overhead {:.3f} (padded / real frames)".format(
+            len(batches), sum(len(b) * T for b, T in batches) / max(real, 1)))
+    else:
+        order = np.argsort(T_of, kind="stable")
+        batches, i = [], 0
+        while i < len(order):
+            j = i
+            while j < len(order) and j - i < args.batch_size and T_of[order[j]] == T_of[order[i]]:
+                j += 1
+            batches.append((order[i:j], int(T_of[order[i]])))
+            i = j
     rank, world = (max(args.rank, 0), max(args.world_size, 1)) if args.distributed else (0, 1)
     model.eval()
     name = str(args.gpu) if args.distributed else "alone"
@@ -160,19 +177,21 @@ def native_generator(model, args):
     # and a writer thread formats the previous batch's embeddings (natively, byte-identical to the reference's
     # str(np.float32) text) while the GPU works on the current one
     from concurrent.futures import ThreadPoolExecutor
-    from pytorch_kaldi_resnet_amd import ingest, kaldi_io
+    from pytorch_kaldi_resnet_amd import kaldi_io
     pinned = {}
 
     def load(n):
-        b = mine[n]
-        T = int(T_of[b[0]])
+        b, T = mine[n]
         key = (n & 1, len(b), T)
         buf = pinned.get(key)
         if buf is None:
             for k in [k for k in pinned if k[0] == key[0]]:
                 del pinned[k]                    # one live buffer per parity: its previous batch has been consumed
             buf = pinned[key] = torch.empty(len(b), F, T).pin_memory()
-        table.read_crop(b, [0] * len(b), T, buf, max(1, args.workers))
+        if args.pad_batches:
+            table.read_padded(b, T, buf, max(1, args.workers))
+        else:
+            table.read_crop(b, [0] * len(b), T, buf, max(1, args.workers))
         return buf
 
     def emit(f, keys, pred):
@@ -187,10 +206,11 @@ def native_generator(model, args):
         nxt = rd.submit(load, 0) if mine else None
         pending = None
         t0, done = time.time(), 0
-        for n, b in enumerate(mine):
+        for n, (b, _) in enumerate(mine):
             buf = nxt.result()
             nxt = rd.submit(load, n + 1) if n + 1 < len(mine) else None
-            pred = model.predict(buf.cuda(args.gpu, non_blocking=True)).cpu().numpy()
+            lengths = table.rows[b] if args.pad_batches else None
+            pred = model.predict(buf.cuda(args.gpu, non_blocking=True), lengths=lengths).cpu().numpy()
             if pending is not None:
                 pending.result()
             pending = wr.submit(emit, f, [utts[k] for k in b], pred)
