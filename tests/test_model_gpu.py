@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import spk_oracle as O  # noqa: E402
 from oracle import weights as W  # noqa: E402
+from helpers import assert_samemask_parity, hip_step_with_masks, oracle_reference  # noqa: E402
 
 def loss_curve_tol(gold_dir, name):
     """|loss - recorded reference loss| budget per SGD step of the recorded 5-step curves.  SURVEY.md section 8c asks for
@@ -118,27 +119,6 @@ def test_forward_parity(P, gold_dir, name):
             np.testing.assert_allclose(sd[key[3:] + ".running_var"].cpu().numpy(), g[key], rtol=1e-4, atol=1e-5)
         if key.startswith("nbt:"):
             assert int(sd[key[4:] + ".num_batches_tracked"]) == int(g[key])
-
-
-def hip_step_with_masks(m, xg, yg):
-    """forward + CE + backward through the engine, also returning the ReLU masks the HIP forward chose, in the call
-    order of the reference forward (scripts/model.py:250, 48-64 / 115-135 per block, head :361-363): the masks the
-    backward kernels differentiate with.  Inner masks come from the same fused multiply-add the kernels use
-    (spk_bn_apply); block-output masks from the stored block outputs."""
-    from pytorch_kaldi_resnet_amd import ops
-    eng = m.engine()
-    m.attach_grads()
-    for p in m.parameters():
-        p.grad = None
-    from helpers import hip_relu_masks
-    with torch.no_grad():
-        logits, saved = eng.forward_train(xg.contiguous(), yg)
-        masks = hip_relu_masks(eng, saved)
-        loss_row, dl, _ = ops.softmax_ce(logits, yg, grad_scale=1.0 / logits.shape[0])
-        loss = float(ops.mean(loss_row))
-    eng.backward(saved, dl)
-    torch.cuda.synchronize()
-    return loss, {n: p.grad.detach().cpu().double() for n, p in m.named_parameters()}, masks
 
 
 @pytest.mark.parametrize("name", ["c1_r34_aam", "r34_softmax_mean_f40", "r34_aamv1_f40", "r101_aam", "r34_aam_t300"])
@@ -383,6 +363,21 @@ def test_odd_shapes_against_oracle(P, arch, F, T, B, pooling, loss):
         assert srel(lg.detach().cpu().numpy(), lo.detach().numpy()) < 2e-4
         torch.nn.functional.cross_entropy(lg, torch.from_numpy(y).cuda()).backward()
         assert all(torch.isfinite(p.grad).all() for p in m.parameters())
+        # the backward of these shapes against the fp64 oracle under the HIP forward's own masks (test_backward_parity's
+        # yardstick; 4x for the head with a BatchNorm1d over the batch, as there).  x4 where mean+std pooling sees a last stage
+        # of <= 5 frames (resnet18 F30 T37: 4 x 5 features per channel): the pooled sqrt(row mean) has derivative 1/(2 sqrt(mean)),
+        # so the few rows with a mean near 0 carry most of the gradient and turn the forward's absolute rounding error there into
+        # a relative error of the whole gradient.  Measured per tensor (f32 operands): one common factor 8.5-14.8x the CPU fp32
+        # path's from the head-most tensor (layer4.1.bn2) to the stem - the head and pooling kernels are the same in every operand
+        # mode, only the forward convolutions' rounding differs (f16x3: 2.5x, bf16x6: 5.9x, f32: 10.6x overall), and the
+        # last-stage features themselves stay within 1.6x of the CPU path's rms error against fp64 (3.3e-6 vs 2.1e-6)
+        bound = 4.0 if loss in ("softmax", "AAM-v1") else 3.0
+        if pooling == "mean+std" and -(-T // 8) <= 5:
+            bound *= 4.0
+        _, hip, masks_hip = hip_step_with_masks(m, torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda())
+        ref = oracle_reference(npst, x, y, pooling, loss, arch)
+        assert_samemask_parity(ref, npst, x, y, pooling, loss, arch, hip, masks_hip, bound=bound,
+                               tag="%s F%d T%d B%d" % (arch, F, T, B))
 
 
 def test_cpu_input_is_refused(P):
