@@ -328,6 +328,36 @@ int spk_trial_cosine(const float* en /*[n_en][D]*/, const float* te /*[n_te][D]*
  * (scripts/compute_topk_mean_std.py:18-21: scores.topk(300), torch.std_mean) */
 int spk_topk_mean_std(const float* scores, float* mean_out, float* std_out, int N, int M, int k, long long ld, void* stream);
 
+/* ---- feature front end (csrc/frontend.hip; DESIGN.md "Feature front end") ------------------------------------------------
+ * Replaces the Kaldi binaries of stage 1 of the reference's feature_pre.sh:77-104 (compute-fbank-feats with conf/fbank.conf,
+ * compute-vad with conf/vad.conf) and local/nnet3/xvector/prepare_feats_for_egs.sh:68-70 (apply-cmvn-sliding --norm-vars=false
+ * --center=true --cmn-window=300 | select-voiced-frames); the fbank as restated in the reference's kaldi.py:42-188,363-527. */
+/* frames per workgroup tile of spk_fbank_fwd for these sizes (0: they do not fit the LDS tile) */
+int spk_fbank_tile_frames(int L, int S, int P, int F);
+/* wave [B][Nmax] (int16-scale samples), nsamp[B] (device): log-mel feats [B][F][Tcap] (time innermost, 0 for t >= T[b]), raw log
+ * energies log_energy [B][Tcap] (0 past T[b]) and T_out[b] = the frame count (frames >= Tcap are not computed: Tcap >= max T).
+ * window [L], twiddle [P/2][2] = exp(-2 pi i k / P), mel_w / mel_lo [F] / mel_off [F+1] (filter m: weights mel_w[mel_off[m] ..
+ * mel_off[m+1]) on FFT bins mel_lo[m] ..) are device tables built by the host in fp64.  P: power of two <= 1024, L <= P.
+ * dither != 0 draws N(0,1) noise keyed by (seed, utt_ids[b], frame, position); energy_floor == 0: no floor. */
+int spk_fbank_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax, const float* window,
+                  const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P, int F,
+                  int snip_edges, float dither, float preemph, int remove_dc, float energy_floor, unsigned long long seed,
+                  float* feats, float* log_energy, int* T_out, int Tcap, void* stream);
+/* out[f][j] = the N(0,1) draw spk_fbank_fwd adds (times dither) at position j of frame frame0 + f of utterance utt_id */
+int spk_fbank_dither_noise(float* out /*[nframes][L]*/, long long utt_id, unsigned long long seed, int frame0, int nframes, int L,
+                           void* stream);
+/* compute-vad over log_energy [B][Tcap] (T[b] frames): vad[b][t] in {0, 1} (0 past T), idx[b][0 .. count[b]) = the voiced
+ * frames in order, count[b].  thr = energy_threshold + mean_scale * mean(log E) (fp64); voiced iff #{t2 in the clipped context
+ * window : logE > thr} >= proportion * #window */
+int spk_vad_count(const float* log_energy, const int* T, int B, int Tcap, double energy_threshold, double mean_scale,
+                  int frames_context, double proportion, int* vad /*[B][Tcap]*/, int* idx /*[B][Tcap]*/, int* count /*[B]*/,
+                  void* stream);
+/* centred sliding CMN (window cmn_window, fp64 sums; 0 = none) of x [B][F][Tcap] over T[b] frames, then the frames idx[b][0 ..
+ * count[b]) (idx and count NULL: all T[b] frames) compacted into out [B][F][Tout] with zero tails.  prefix: fp64 workspace of
+ * B * F * (Tcap + 1) doubles (may be NULL when cmn_window == 0). */
+int spk_cmn_select(const float* x, const int* T, const int* idx, const int* count, double* prefix, float* out, int B, int F,
+                   int Tcap, int Tout, int cmn_window, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

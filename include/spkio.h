@@ -35,6 +35,14 @@ int64_t spk_format_text_vectors(int n, int D, const float* v, const char* const*
 int spk_vec_ark_load(const char* path, int nthreads, int64_t* n, int32_t* D, double** data, char** keys, int64_t* keys_bytes);
 void spk_vec_ark_free(double* data, char* keys);
 void spk_io_set_error(const char* msg);
+/* WAV ingest for the feature front end (csrc_io/wav_reader.cpp; the wav.scp files that the reference's feature_pre.sh:77-104 gives
+ * to compute-fbank-feats): RIFF/WAVE, PCM 16-bit mono (also as WAVE_FORMAT_EXTENSIBLE), chunks other than 'fmt ' / 'data' skipped.
+ * Probe: per file the sample rate, the sample count and the byte offset of the samples; other widths, channel counts, formats and
+ * (expect_rate > 0) sample rates are refused with an error naming the file. */
+int spk_wav_probe(int n, const char* const* paths, int expect_rate, int32_t* rate, int64_t* nsamp, int64_t* data_offsets);
+/* out[b][s] = sample s of file b at int16 scale for s < nsamp[b], 0 up to Nmax; pread() on `nthreads` threads */
+int spk_wav_read_padded(int B, const char* const* paths, const int64_t* data_offsets, const int64_t* nsamp, int64_t Nmax, float* out,
+                        int nthreads);
 #ifdef __cplusplus
 }
 #endif

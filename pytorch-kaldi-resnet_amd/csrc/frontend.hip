@@ -1,0 +1,384 @@
+// Kaldi-compatible feature front end (compute-fbank-feats, compute-vad, apply-cmvn-sliding --norm-vars=false --center=true,
+// select-voiced-frames; reference: feature_pre.sh:77-104 and local/nnet3/xvector/prepare_feats_for_egs.sh:68-70, the fbank as
+// restated in kaldi.py:42-188,363-527).  Semantics: DESIGN.md section "Feature front end".
+//
+// spk_fbank_fwd: one workgroup of 4 waves per (utterance, tile of FT consecutive frames).  The tile's waveform span is staged
+// once in LDS (frames overlap by L - S samples; the reflection of snip_edges=false is applied on load).  Each wave takes one frame
+// per round: dither, explicit fp32 DC removal, raw log energy, pre-emphasis, window, zero pad to P, a complex radix-2 FFT of
+// M = P/2 points of the even/odd samples plus the real-split post-pass, power, sparse mel sum, log.  The log-mel values of the
+// tile are transposed through LDS and stored as runs of FT frames per mel row ([B][F][Tcap], time innermost).
+// The host builds the window, the twiddles exp(-2 pi i k / P) and the mel weights in fp64 and passes them rounded to fp32.
+#include "spk_common.h"
+
+namespace {
+
+constexpr int FE_THREADS = 256;   // 4 waves, one frame each per round
+constexpr int FE_WAVES = 4;
+constexpr float FE_FLT_EPS = 1.1920928955078125e-07f;
+constexpr float FE_LOG_EPS = -15.942385152878742f;     // log(FLT_EPSILON), correctly rounded (logf may be 1 ulp off)
+
+__device__ inline float fe_log_floor_eps(float v) { return v > FE_FLT_EPS ? logf(v) : FE_LOG_EPS; }
+
+// counter-based N(0,1) draw keyed by (seed, utt_id, frame, position): splitmix64 finaliser + Box-Muller
+__host__ __device__ inline unsigned long long fe_mix64(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    return z ^ (z >> 31);
+}
+__device__ inline unsigned long long fe_utt_key(unsigned long long seed, long long utt_id) {
+    return fe_mix64(seed * 0x9e3779b97f4a7c15ULL ^ fe_mix64((unsigned long long)utt_id + 0x632be59bd9b4e019ULL));
+}
+__device__ inline float fe_gauss(unsigned long long key, int t, int j) {
+    const unsigned long long ctr = ((unsigned long long)(unsigned)t << 20) | (unsigned)j;     // j < P <= 1024
+    const unsigned long long h = fe_mix64(key + ctr * 0xd1b54a32d192ed03ULL);
+    const float u1 = (float)((unsigned)(h >> 40) + 1u) * 0x1p-24f;                           // (0, 1]
+    const float u2 = (float)((unsigned)(h >> 8) & 0xffffffu) * 0x1p-24f;                      // [0, 1)
+    return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// the frame buffers fb / z belong to one wave: its lanes exchange data through LDS with a wave-local barrier (LDS operations of a
+// wave complete in order; the fences keep the compiler from moving LDS accesses across it), not a workgroup barrier
+__device__ inline void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ inline float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ inline int fe_frames(long long N, int L, int S, int snip) {
+    if (snip) return N < L ? 0 : (int)(1 + (N - L) / S);
+    return (int)((N + S / 2) / S);
+}
+
+struct FbankArgs {
+    const float* wave;
+    const int* nsamp;
+    const long long* utt_ids;
+    long long Nmax;
+    const float* window;      // [L]
+    const float* twiddle;     // [M][2] exp(-2 pi i k / P)
+    const float* mel_w;       // concatenated weights of the filters
+    const int* mel_lo;        // [F] first FFT bin of filter m
+    const int* mel_off;       // [F + 1] offsets into mel_w (filter m covers bins mel_lo[m] .. + mel_off[m+1]-mel_off[m])
+    int L, S, P, logM, F, snip, FT, span;
+    float dither, preemph, log_floor;   // log_floor: -inf when energy_floor == 0
+    int remove_dc;
+    unsigned long long seed;
+    float* feats;     // [B][F][Tcap]
+    float* loge;      // [B][Tcap]
+    int* T_out;       // [B]
+    int Tcap;
+};
+
+__global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
+    extern __shared__ float fe_lds[];
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.x * a.FT;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long long N = min((long long)a.nsamp[b], a.Nmax);
+    const int T = N > 0 ? fe_frames(N, a.L, a.S, a.snip) : 0;
+    if (blockIdx.x == 0 && tid == 0) a.T_out[b] = T;
+    float* frow = a.feats + (size_t)b * a.F * a.Tcap;
+    const int nt = min(a.FT, a.Tcap - t0);
+    if (t0 >= T) {        // tile entirely past the utterance: zeros only (block-uniform)
+        for (int i = tid; i < a.F * nt; i += FE_THREADS) frow[(size_t)(i / nt) * a.Tcap + t0 + i % nt] = 0.f;
+        for (int i = tid; i < nt; i += FE_THREADS) a.loge[(size_t)b * a.Tcap + t0 + i] = 0.f;
+        return;
+    }
+    const int M = a.P >> 1;
+    // LDS: the float2 FFT buffers first (8-byte aligned whatever the span length), then the per-wave frame buffers, the span
+    float2* zbuf = (float2*)fe_lds;                         // [4][M]   FFT
+    float* fbuf = (float*)(zbuf + FE_WAVES * M);            // [4][P]   frame samples, then power spectrum
+    float* span = fbuf + FE_WAVES * a.P;                    // [span]
+    float* otile = span + a.span;                           // [F + 1][FT]: log-mel rows, then the log energies
+    const float* wv = a.wave + (size_t)b * a.Nmax;
+    const long long s0 = (long long)t0 * a.S - (a.snip ? 0 : (a.L / 2 - a.S / 2));
+    for (int i = tid; i < a.span; i += FE_THREADS) {
+        long long s = s0 + i;
+        if (s < 0) s = -s - 1;                      // reflected once (snip_edges = false)
+        if (s >= N) s = 2 * N - 1 - s;
+        s = s < 0 ? 0 : (s >= N ? N - 1 : s);       // only reached for N < L, which the API refuses: stay in bounds
+        span[i] = wv[s];
+    }
+    const unsigned long long key = a.dither != 0.f ? fe_utt_key(a.seed, a.utt_ids[b]) : 0ull;
+    float* fb = fbuf + w * a.P;
+    float2* z = zbuf + w * M;
+    __syncthreads();
+    for (int r = 0; r < a.FT; r += FE_WAVES) {
+        const int tl = r + w;                       // frame within the tile
+        const int t = t0 + tl;
+        if (t >= T) break;                          // wave-uniform: frames past the utterance are not computed (stored as 0)
+        const float* x0 = span + tl * a.S;
+        // 1-2. dither, frame mean (explicit fp32 subtraction: DESIGN.md "Feature front end")
+        float sum = 0.f;
+        for (int j = lane; j < a.L; j += 64) {
+            float v = x0[j];
+            if (a.dither != 0.f) v = fmaf(a.dither, fe_gauss(key, t, j), v);
+            fb[j] = v;
+            sum += v;
+        }
+        const float mean = a.remove_dc ? wave_sum(sum) / (float)a.L : 0.f;
+        // 3. raw log energy
+        float e = 0.f;
+        for (int j = lane; j < a.L; j += 64) {
+            const float v = fb[j] - mean;
+            fb[j] = v;
+            e = fmaf(v, v, e);
+        }
+        e = wave_sum(e);
+        wave_lds_sync();
+        // 4-6. pre-emphasis, window, zero pad; z[n] = y[2n] + i y[2n+1], stored bit-reversed for the in-place radix-2 FFT
+        for (int n = lane; n < M; n += 64) {
+            float y[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int j = 2 * n + q;
+                y[q] = 0.f;
+                if (j < a.L) y[q] = (fb[j] - a.preemph * fb[j > 0 ? j - 1 : 0]) * a.window[j];
+            }
+            const int br = (int)(__brev((unsigned)n) >> (32 - a.logM));
+            z[br] = make_float2(y[0], y[1]);
+        }
+        wave_lds_sync();
+        // 7. FFT of M points (decimation in time), then the real split: X[k] = E[k] + W_P^k O[k]
+        for (int st = 0; st < a.logM; ++st) {
+            const int half = 1 << st;
+            for (int k = lane; k < (M >> 1); k += 64) {
+                const int pos = k & (half - 1);
+                const int i0 = ((k >> st) << (st + 1)) + pos, i1 = i0 + half;
+                const float2 tw = ((const float2*)a.twiddle)[pos << (a.logM - st)];
+                const float2 u = z[i0], v = z[i1];
+                const float2 bv = make_float2(v.x * tw.x - v.y * tw.y, v.x * tw.y + v.y * tw.x);
+                z[i0] = make_float2(u.x + bv.x, u.y + bv.y);
+                z[i1] = make_float2(u.x - bv.x, u.y - bv.y);
+            }
+            wave_lds_sync();
+        }
+        for (int k = lane; k < M; k += 64) {
+            const float2 zk = z[k], zc = z[(M - k) & (M - 1)];
+            const float er = 0.5f * (zk.x + zc.x), ei = 0.5f * (zk.y - zc.y);     // (Z[k] + conj Z[M-k]) / 2
+            const float orr = 0.5f * (zk.y + zc.y), oi = -0.5f * (zk.x - zc.x);   // (Z[k] - conj Z[M-k]) / 2i
+            const float2 tw = ((const float2*)a.twiddle)[k];
+            const float xr = er + (orr * tw.x - oi * tw.y), xi = ei + (orr * tw.y + oi * tw.x);
+            fb[k] = xr * xr + xi * xi;
+        }
+        wave_lds_sync();
+        // mel filterbank (sparse: each filter's bin range), log
+        for (int m = lane; m < a.F; m += 64) {
+            const int lo = a.mel_lo[m], o0 = a.mel_off[m], cnt = a.mel_off[m + 1] - o0;
+            float s = 0.f;
+            for (int q = 0; q < cnt; ++q) s = fmaf(a.mel_w[o0 + q], fb[lo + q], s);
+            otile[m * a.FT + tl] = fe_log_floor_eps(s);
+        }
+        if (lane == 0) otile[a.F * a.FT + tl] = fmaxf(fe_log_floor_eps(e), a.log_floor);
+        wave_lds_sync();
+    }
+    __syncthreads();                                // the otile columns of every wave are complete
+    // transposed store: each mel row gets a run of nt consecutive frames; zeros past T
+    for (int i = tid; i < (a.F + 1) * nt; i += FE_THREADS) {
+        const int m = i / nt, tl = i - m * nt, t = t0 + tl;
+        const float v = t < T ? otile[m * a.FT + tl] : 0.f;
+        if (m < a.F) frow[(size_t)m * a.Tcap + t] = v;
+        else a.loge[(size_t)b * a.Tcap + t] = v;
+    }
+}
+
+// the noise fbank_kernel adds (before scaling by dither) to frames frame0 .. frame0 + nframes - 1 of utterance utt_id
+__global__ __launch_bounds__(256) void dither_noise_kernel(float* out, long long utt_id, unsigned long long seed, int frame0,
+                                                           int nframes, int L) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nframes * L) return;
+    const int f = (int)(i / L), j = (int)(i % L);
+    out[i] = fe_gauss(fe_utt_key(seed, utt_id), frame0 + f, j);
+}
+
+// compute-vad: one wave per utterance.  Mean log energy in fp64, decisions over the clipped context window, and the compaction
+// list of voiced frames (ballot + prefix popcount, in frame order)
+__global__ __launch_bounds__(64) void vad_kernel(const float* __restrict__ loge, const int* __restrict__ Tv, int Tcap, double thr0,
+                                                 double mean_scale, int ctx, double prop, int* __restrict__ vad,
+                                                 int* __restrict__ idx, int* __restrict__ count) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int T = min(max(Tv[b], 0), Tcap);
+    const float* e = loge + (size_t)b * Tcap;
+    double s = 0.0;
+    for (int t = lane; t < T; t += 64) s += (double)e[t];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const double thr = thr0 + (T > 0 ? mean_scale * (s / (double)T) : 0.0);
+    int carry = 0;
+    for (int t0 = 0; t0 < Tcap; t0 += 64) {
+        const int t = t0 + lane;
+        bool v = false;
+        if (t < T) {
+            int num = 0, den = 0;
+            for (int t2 = max(t - ctx, 0); t2 <= min(t + ctx, T - 1); ++t2) {
+                ++den;
+                num += (double)e[t2] > thr;
+            }
+            v = (double)num >= (double)den * prop;
+        }
+        if (t < Tcap) vad[(size_t)b * Tcap + t] = v ? 1 : 0;
+        const unsigned long long mask = __ballot(v);
+        const int pos = carry + __popcll(mask & ((1ull << lane) - 1ull));
+        if (v) idx[(size_t)b * Tcap + pos] = t;
+        carry += __popcll(mask);
+    }
+    if (lane == 0) count[b] = carry;
+}
+
+// fp64 prefix sums of every (b, m) row over its T[b] frames: pre[row][0] = 0, pre[row][t + 1] = sum x[0..t]; one wave per row
+__global__ __launch_bounds__(256) void cmn_prefix_kernel(const float* __restrict__ x, const int* __restrict__ Tv, int B, int F,
+                                                         int Tcap, double* __restrict__ pre) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B * F) return;
+    const int T = min(max(Tv[row / F], 0), Tcap);
+    const float* xr = x + (size_t)row * Tcap;
+    double* pr = pre + (size_t)row * (Tcap + 1);
+    if (lane == 0) pr[0] = 0.0;
+    double carry = 0.0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        double v = t < T ? (double)xr[t] : 0.0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double u = __shfl_up(v, off, 64);
+            if (lane >= off) v += u;
+        }
+        if (t < T) pr[t + 1] = carry + v;
+        carry += __shfl(v, 63, 64);
+    }
+}
+
+// out[b][m][j] = x[b][m][t] - mean of the centred sliding window around t (W > 0; W == 0: no CMN), t = idx[b][j] (the j-th voiced
+// frame; idx NULL: t = j), for j < count[b] (count NULL: T[b]); zero for count[b] <= j < Tout
+__global__ __launch_bounds__(256) void cmn_select_kernel(const float* __restrict__ x, const int* __restrict__ Tv,
+                                                         const int* __restrict__ idx, const int* __restrict__ count,
+                                                         const double* __restrict__ pre, float* __restrict__ out, int F, int Tcap,
+                                                         int Tout, int W, int nj) {
+    const int row = blockIdx.x / nj;       // b * F + m
+    const int j = (blockIdx.x - row * nj) * 256 + threadIdx.x;
+    const int b = row / F;
+    if (j >= Tout) return;
+    const int T = min(max(Tv[b], 0), Tcap);
+    const int n = count ? min(count[b], T) : T;
+    float v = 0.f;
+    if (j < n) {
+        const int t = idx ? idx[(size_t)b * Tcap + j] : j;
+        const float xv = x[(size_t)row * Tcap + t];
+        if (W > 0) {
+            int start = t - W / 2, end = start + W;
+            if (start < 0) {
+                end -= start;
+                start = 0;
+            }
+            if (end > T) {
+                start -= end - T;
+                end = T;
+                start = max(start, 0);
+            }
+            const double* pr = pre + (size_t)row * (Tcap + 1);
+            const double mean = (pr[end] - pr[start]) / (double)(end - start);
+            v = (float)((double)xv - mean);
+        } else {
+            v = xv;
+        }
+    }
+    out[(size_t)row * Tout + j] = v;
+}
+
+int fe_lds_bytes(int FT, int L, int S, int P, int F) {
+    const int span = (FT - 1) * S + L;
+    return (FE_WAVES * P /* z */ + FE_WAVES * P /* fb */ + span + (F + 1) * FT) * 4;
+}
+
+}  // namespace
+
+constexpr int FE_LDS_LIMIT = 64 * 1024;
+
+// ---- exports (include/spkhip.h) ----
+extern "C" int spk_fbank_tile_frames(int L, int S, int P, int F) {
+    for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
+        if (fe_lds_bytes(FT, L, S, P, F) <= FE_LDS_LIMIT) return FT;
+    return 0;
+}
+
+extern "C" int spk_fbank_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax,
+                             const float* window, const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off,
+                             int L, int S, int P, int F, int snip_edges, float dither, float preemph, int remove_dc,
+                             float energy_floor, unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap,
+                             void* stream) {
+    SPK_REQUIRE(wave && nsamp && window && twiddle && mel_w && mel_lo && mel_off && feats && log_energy && T_out,
+                "spk_fbank_fwd: null pointer");
+    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_fbank_fwd: dither != 0 needs utt_ids");
+    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_fbank_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
+    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_fbank_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
+    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_fbank_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
+    SPK_REQUIRE(F >= 1 && F <= 1024, "spk_fbank_fwd: num_mel_bins F=%d", F);
+    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
+                "spk_fbank_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
+    const int FT = spk_fbank_tile_frames(L, S, P, F);
+    SPK_REQUIRE(FT > 0, "spk_fbank_fwd: L=%d S=%d P=%d F=%d do not fit the LDS tile", L, S, P, F);
+    FbankArgs a;
+    a.wave = wave; a.nsamp = nsamp; a.utt_ids = utt_ids; a.Nmax = Nmax;
+    a.window = window; a.twiddle = twiddle; a.mel_w = mel_w; a.mel_lo = mel_lo; a.mel_off = mel_off;
+    a.L = L; a.S = S; a.P = P; a.F = F; a.snip = snip_edges ? 1 : 0; a.FT = FT; a.span = (FT - 1) * S + L;
+    int lg = 0;
+    while ((1 << lg) < P / 2) ++lg;
+    a.logM = lg;
+    a.dither = dither; a.preemph = preemph; a.remove_dc = remove_dc ? 1 : 0;
+    a.log_floor = energy_floor > 0.f ? logf(energy_floor) : -__builtin_inff();
+    a.seed = seed; a.feats = feats; a.loge = log_energy; a.T_out = T_out; a.Tcap = Tcap;
+    const int lds = fe_lds_bytes(FT, L, S, P, F);
+    hipLaunchKernelGGL(fbank_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds, (hipStream_t)stream, a);
+    SPK_LAUNCH_CHECK("spk_fbank_fwd");
+    return 0;
+}
+
+extern "C" int spk_fbank_dither_noise(float* out, long long utt_id, unsigned long long seed, int frame0, int nframes, int L,
+                                      void* stream) {
+    SPK_REQUIRE(out, "spk_fbank_dither_noise: null pointer");
+    SPK_REQUIRE(frame0 >= 0 && nframes > 0 && L >= 1 && L <= 1024, "spk_fbank_dither_noise: frame0=%d nframes=%d L=%d", frame0,
+                nframes, L);
+    const long long n = (long long)nframes * L;
+    hipLaunchKernelGGL(dither_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, utt_id, seed,
+                       frame0, nframes, L);
+    SPK_LAUNCH_CHECK("spk_fbank_dither_noise");
+    return 0;
+}
+
+extern "C" int spk_vad_count(const float* log_energy, const int* T, int B, int Tcap, double energy_threshold, double mean_scale,
+                             int frames_context, double proportion, int* vad, int* idx, int* count, void* stream) {
+    SPK_REQUIRE(log_energy && T && vad && idx && count, "spk_vad_count: null pointer");
+    SPK_REQUIRE(B > 0 && Tcap > 0, "spk_vad_count: B=%d Tcap=%d", B, Tcap);
+    SPK_REQUIRE(frames_context >= 0 && mean_scale >= 0.0, "spk_vad_count: frames_context=%d mean_scale=%g", frames_context, mean_scale);
+    hipLaunchKernelGGL(vad_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, log_energy, T, Tcap, energy_threshold,
+                       mean_scale, frames_context, proportion, vad, idx, count);
+    SPK_LAUNCH_CHECK("spk_vad_count");
+    return 0;
+}
+
+extern "C" int spk_cmn_select(const float* x, const int* T, const int* idx, const int* count, double* prefix, float* out, int B,
+                              int F, int Tcap, int Tout, int cmn_window, void* stream) {
+    SPK_REQUIRE(x && T && out, "spk_cmn_select: null pointer");
+    SPK_REQUIRE(cmn_window == 0 || prefix, "spk_cmn_select: cmn_window > 0 needs the prefix workspace");
+    SPK_REQUIRE((idx == nullptr) == (count == nullptr), "spk_cmn_select: idx and count go together");
+    SPK_REQUIRE(B > 0 && F > 0 && Tcap > 0 && Tout > 0 && cmn_window >= 0, "spk_cmn_select: B=%d F=%d Tcap=%d Tout=%d W=%d", B, F,
+                Tcap, Tout, cmn_window);
+    SPK_REQUIRE((long long)B * F * spk_ceil_div(Tout, 256) < (1ll << 31), "spk_cmn_select: B=%d F=%d Tout=%d exceed the grid", B, F, Tout);
+    SPK_REQUIRE(Tout <= Tcap, "spk_cmn_select: Tout=%d > Tcap=%d", Tout, Tcap);
+    if (cmn_window > 0) {
+        hipLaunchKernelGGL(cmn_prefix_kernel, dim3((unsigned)spk_ceil_div(B * F, 4)), dim3(256), 0, (hipStream_t)stream, x, T, B, F,
+                           Tcap, prefix);
+        SPK_LAUNCH_CHECK("spk_cmn_select");
+    }
+    const int nj = spk_ceil_div(Tout, 256);
+    hipLaunchKernelGGL(cmn_select_kernel, dim3((unsigned)(B * F * nj)), dim3(256), 0, (hipStream_t)stream, x, T, idx, count, prefix,
+                       out, F, Tcap, Tout, cmn_window, nj);
+    SPK_LAUNCH_CHECK("spk_cmn_select");
+    return 0;
+}

@@ -32,6 +32,8 @@ def lib():
         l.spk_ark_read_crop.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_int]
         l.spk_ark_read_padded.argtypes = [ctypes.c_int, cpp, i64p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        l.spk_wav_probe.argtypes = [ctypes.c_int, cpp, ctypes.c_int, i32p, i64p, i64p]
+        l.spk_wav_read_padded.argtypes = [ctypes.c_int, cpp, i64p, i64p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int]
         l.spk_text_vectors_bound.argtypes = [ctypes.c_int, ctypes.c_int, cpp]
         l.spk_text_vectors_bound.restype = ctypes.c_int64
         l.spk_format_text_vectors.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, cpp, ctypes.c_char_p, ctypes.c_int64,
@@ -114,6 +116,39 @@ class ArkTable:
         _check(lib().spk_ark_read_padded(B, arr, doff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                          rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), F, T, out.data_ptr(), nthreads),
                "spk_ark_read_padded")
+        return out
+
+
+class WavTable:
+    """Parsed wav.scp entries (file paths; Kaldi pipe entries 'cmd |' are refused): per file the sample count and the offset of the
+    samples, probed once.  PCM 16-bit mono only, at `sample_rate` (0: any) - everything else is refused naming the file."""
+
+    def __init__(self, paths, sample_rate=0):
+        for p in paths:
+            if p.rstrip().endswith("|"):
+                raise ValueError("wav.scp pipe entries are not supported: %r" % p)
+        self.paths = list(paths)
+        n = len(self.paths)
+        self._cpaths = [ctypes.c_char_p(p.encode()) for p in self.paths]
+        self.rate = np.zeros(n, dtype=np.int32)
+        self.nsamp = np.zeros(n, dtype=np.int64)
+        self.data_off = np.zeros(n, dtype=np.int64)
+        arr = (ctypes.c_char_p * max(n, 1))(*[c.value for c in self._cpaths])
+        _check(lib().spk_wav_probe(n, arr, int(sample_rate), self.rate.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   self.nsamp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                   self.data_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), "spk_wav_probe")
+
+    def read_padded(self, idx, Nmax, out, nthreads=4):
+        """Files idx into a contiguous float32 host tensor out [B, Nmax] (ideally pinned) at int16 scale, zero past each file's
+        sample count self.nsamp[idx] (each <= Nmax)."""
+        B = len(idx)
+        assert out.is_contiguous() and tuple(out.shape) == (B, Nmax) and out.dtype == torch.float32
+        arr = (ctypes.c_char_p * B)(*[self._cpaths[i].value for i in idx])
+        doff = np.ascontiguousarray(self.data_off[idx])
+        ns = np.ascontiguousarray(self.nsamp[idx])
+        _check(lib().spk_wav_read_padded(B, arr, doff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), int(Nmax), out.data_ptr(), nthreads),
+               "spk_wav_read_padded")
         return out
 
 

@@ -45,6 +45,12 @@ parser.add_argument("--pad-batches", action="store_true",
                     help="with --native-reader and --chunk-size -1: length-sorted batches of up to --batch-size utterances padded to a "
                          "common length (at most 10%% padded frames, T rounded up to 8) and run through the length-masked "
                          "predict(x, lengths=...): each embedding is that of its utterance alone")
+parser.add_argument("--wav-scp", help="extract from audio: a wav.scp of PCM 16-bit mono files (instead of --decode-scp); the "
+                    "Kaldi fbank (+ sliding CMN, + energy VAD frame selection) runs on the GPU (pytorch_kaldi_resnet_amd.features)")
+parser.add_argument("--fbank-config", help="with --wav-scp: Kaldi compute-fbank-feats config (conf/fbank.conf)")
+parser.add_argument("--vad-config", help="with --wav-scp: Kaldi compute-vad config (conf/vad.conf): keep voiced frames only")
+parser.add_argument("--cmn-window", type=int, default=0,
+                    help="with --wav-scp: apply-cmvn-sliding --norm-vars=false --center=true window (0: none; the recipe uses 300)")
 parser.add_argument("--out-format", default="text", choices=["text", "fv"],
                     help="text = the reference's 'utt [ v0 ... ]' lines (str(np.float32), ~0.2 ms/utt of Python formatting); "
                          "fv = binary Kaldi float-vector ark, read by the same scoring scripts")
@@ -52,6 +58,10 @@ parser.add_argument("--out-format", default="text", choices=["text", "fv"],
 
 def main():
     args = parser.parse_args()
+    if args.wav_scp and args.decode_scp:
+        parser.error("--wav-scp and --decode-scp are mutually exclusive")
+    if (args.fbank_config or args.vad_config or args.cmn_window) and not args.wav_scp:
+        parser.error("--fbank-config / --vad-config / --cmn-window need --wav-scp")
     if args.pad_batches and not args.native_reader:
         parser.error("--pad-batches needs --native-reader")
     if args.pad_batches and args.chunk_size >= 0:
@@ -102,6 +112,11 @@ def main_worker(gpu, ngpus_per_node, args):
     print("=> loaded checkpoint '{}' (epoch {})".format(args.model_path, ckpt.get("epoch")))
     model.cuda(args.gpu)
     os.makedirs(args.out_path, exist_ok=True)
+    if args.wav_scp:
+        wav_generator(model, args)
+        if args.distributed:
+            dist.destroy_process_group()
+        return
     if args.native_reader:
         native_generator(model, args)
         if args.distributed:
@@ -219,6 +234,66 @@ def native_generator(model, args):
             pending.result()
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + predict + write)".format(done, dt, done / max(dt, 1e-9)))
+
+
+def wav_generator(model, args):
+    """--wav-scp: batches of utterances sorted by sample count (at most 10 % padded samples) read by the native WAV reader into
+    pinned memory - the next batch while the GPU runs the front end and the length-masked predict of the current one.  Output
+    format as native_generator; utterances shorter than one frame or without voiced frames are reported and skipped."""
+    from concurrent.futures import ThreadPoolExecutor
+    from pytorch_kaldi_resnet_amd import features, ingest, kaldi_io
+    fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window)
+    frontend = features.Frontend(fb, vad_opts, cmn)
+    keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size)
+    print("Totally " + str(len(keys)) + " samples")
+    for i in short:
+        print("=> skipping {}: {} samples, shorter than one frame".format(keys[i], int(table.nsamp[i])))
+    rank, world = (max(args.rank, 0), max(args.world_size, 1)) if args.distributed else (0, 1)
+    mine = batches[rank::world]
+    seed = 0 if args.seed is None else args.seed
+    model.eval()
+    name = str(args.gpu) if args.distributed else "alone"
+
+    def load(n):
+        b, nmax = mine[n]
+        buf = torch.empty(len(b), nmax).pin_memory()
+        table.read_padded(b, nmax, buf, max(1, args.workers))
+        return buf
+
+    def emit(f, ks, pred):
+        if args.out_format == "text":
+            f.write(ingest.format_text_vectors(ks, pred, max(1, args.workers)))
+        else:
+            for i in range(pred.shape[0]):
+                kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=ks[i])
+
+    with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
+            ThreadPoolExecutor(1) as wr:
+        nxt = rd.submit(load, 0) if mine else None
+        pending = None
+        t0, done = time.time(), 0
+        for n, (b, _) in enumerate(mine):
+            buf = nxt.result()
+            nxt = rd.submit(load, n + 1) if n + 1 < len(mine) else None
+            wave = buf.cuda(args.gpu, non_blocking=True)
+            feats, lengths = frontend(wave, table.nsamp[b], [features.utt_id(keys[i]) for i in b], seed)
+            keep = np.nonzero(lengths > 0)[0]
+            for r in np.nonzero(lengths == 0)[0]:
+                print("=> skipping {}: no voiced frames".format(keys[b[r]]))
+            if keep.size == 0:
+                continue
+            if keep.size < len(b):
+                feats = feats[torch.from_numpy(keep).to(feats.device)].contiguous()
+            pred = model.predict(feats, lengths=lengths[keep]).cpu().numpy()
+            if pending is not None:
+                pending.result()
+            pending = wr.submit(emit, f, [keys[b[r]] for r in keep], pred)
+            done += keep.size
+        if pending is not None:
+            pending.result()
+        dt = time.time() - t0
+        print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + front end + predict + write)".format(
+            done, dt, done / max(dt, 1e-9)))
 
 
 if __name__ == "__main__":
