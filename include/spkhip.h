@@ -358,6 +358,22 @@ int spk_vad_count(const float* log_energy, const int* T, int B, int Tcap, double
 int spk_cmn_select(const float* x, const int* T, const int* idx, const int* count, double* prefix, float* out, int B, int F,
                    int Tcap, int Tout, int cmn_window, void* stream);
 
+/* ---- resampling (csrc/resample.hip; DESIGN.md "Feature front end", "Resampling") -------------------------------------------
+ * Replaces the reference's kaldi.py: resample_waveform (Kaldi's LinearResample / ResampleWaveform, what compute-fbank-feats
+ * --allow-downsample / --allow-upsample runs), and with fi = speed x rate the resampling half of
+ * local/perturb_data_dir_speed.sh.  g = gcd(fi, fo), iu = fi / g, ou = fo / g. */
+/* outputs per workgroup tile of spk_resample_fwd for a table of ou phases x K taps (0: table + span do not fit its LDS) */
+int spk_resample_tile(int iu, int ou, int K);
+/* wave_in [B][Nmax_in] (int16-scale samples), nsamp_in[B] (device) -> wave_out [B][Nmax_out], nsamp_out[b] =
+ * ceil(nsamp_in[b] * ou / iu) (LinearResample::GetNumOutputSamples; Nmax_out must hold the longest row), zeros past it:
+ *     wave_out[b][j] = sum_{k < K} w[j % ou][k] * wave_in[b][first[j % ou] + (j / ou) * iu + k],  0 outside [0, nsamp_in[b])
+ * summed in fp32 in tap order.  first [ou] and the windowed-sinc weights are device tables built by the host in fp64; the weights
+ * come as pairs of consecutive taps, phase running fastest: wq [ceil(K / 2)][ou][2], wq[m][p] = (w[p][2m], w[p][2m + 1]), with a
+ * zero for the tap an odd K lacks.  Refused before any launch: fi == fo, and a table beyond the LDS budget (the message names
+ * fi -> fo). */
+int spk_resample_fwd(const float* wave_in, const int* nsamp_in, int B, long long Nmax_in, const int* first, const float* wq,
+                     int fi, int fo, int K, float* wave_out, int* nsamp_out, long long Nmax_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

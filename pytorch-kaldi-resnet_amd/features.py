@@ -2,12 +2,14 @@
 (apply-cmvn-sliding --norm-vars=false --center=true) and voiced-frame selection (select-voiced-frames) - the Kaldi binaries of
 stage 1 of the reference's feature_pre.sh:77-104 and of local/nnet3/xvector/prepare_feats_for_egs.sh:68-70.
 
-The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_vad_count, spk_cmn_select); this module parses Kaldi config
-files, builds the window / twiddle / mel tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
+The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_vad_count, spk_cmn_select) and csrc/resample.hip
+(spk_resample_fwd: Kaldi's LinearResample, for audio at another sample rate and for speed perturbation); this module parses Kaldi
+config files, builds the window / twiddle / mel / resampling tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
 The one deliberate difference from Kaldi: dither is a counter-based N(0,1) draw keyed by (seed, utt_id, frame, position), and the VAD
 sees the same dithered frames as the fbank (Kaldi draws a second dither for its MFCC pass).
 """
 import dataclasses
+import fractions
 import hashlib
 import math
 
@@ -238,6 +240,140 @@ def _host_ints(v, dtype=np.int64):
     return np.asarray(v, dtype=dtype).reshape(-1)
 
 
+# ---- resampling (Kaldi's LinearResample; csrc/resample.hip) ----
+LOWPASS_FILTER_WIDTH = 6        # zero crossings of the windowed sinc (Kaldi's ResampleWaveform)
+
+
+def _int_rate(v, what):
+    r = int(round(float(v)))
+    if r <= 0 or r != float(v):
+        raise ValueError("%s: sample rate %r must be a positive whole number of Hz" % (what, v))
+    return r
+
+
+def num_resampled(n, fi, fo):
+    """LinearResample::GetNumOutputSamples: the number of outputs j with j / fo < n / fi (n: an int or an integer array)"""
+    fi, fo = _int_rate(fi, "num_resampled"), _int_rate(fo, "num_resampled")
+    g = math.gcd(fi, fo)
+    iu, ou = fi // g, fo // g
+    if isinstance(n, (int, np.integer)):
+        return max(-((-int(n) * ou) // iu), 0)
+    n = np.maximum(np.asarray(n, dtype=np.int64), 0)
+    return -((-n * ou) // iu)
+
+
+def _resample_first(fi, fo):
+    """(iu, ou, K, first [ou], window width ww, cutoff fc): the cheap part of the table (no [ou][K] array yet)"""
+    g = math.gcd(fi, fo)
+    iu, ou = fi // g, fo // g
+    fc = 0.99 * 0.5 * min(fi, fo)
+    ww = LOWPASS_FILTER_WIDTH / (2.0 * fc)
+    t = np.arange(ou, dtype=np.float64) / fo
+    first = np.ceil((t - ww) * fi)
+    last = np.floor((t + ww) * fi)
+    return iu, ou, int((last - first + 1).max()), first, ww, fc
+
+
+def _resample_tables(fi, fo):
+    iu, ou, K, first, ww, fc = _resample_first(fi, fo)
+    t = np.arange(ou, dtype=np.float64) / fo
+    dt = (first[:, None] + np.arange(K, dtype=np.float64)[None, :]) / fi - t[:, None]
+    w = np.where(np.abs(dt) < ww, 0.5 * (1 + np.cos(2 * math.pi * fc / LOWPASS_FILTER_WIDTH * dt)), 0.0)
+    zero = dt == 0.0
+    w = w * np.where(zero, 2 * fc, np.sin(2 * math.pi * fc * dt) / (math.pi * np.where(zero, 1.0, dt)))
+    return iu, ou, K, first.astype(np.int64), w / fi
+
+
+class _ResampleTables:
+    def __init__(self, fi, fo, device):
+        self.iu, self.ou, self.K, self.first, self.w = _resample_tables(fi, fo)
+        self.first_dev = self.wq_dev = None
+        if device is not None:
+            # the kernel reads the weights as pairs of consecutive taps, the phase running fastest ([ceil(K / 2)][ou][2], an odd
+            # K padded with a zero tap): consecutive outputs, consecutive LDS banks
+            K2 = (self.K + 1) // 2
+            wp = np.zeros((self.ou, 2 * K2), dtype=np.float32)
+            wp[:, :self.K] = self.w.astype(np.float32)
+            self.first_dev = torch.from_numpy(self.first.astype(np.int32)).to(device)
+            self.wq_dev = torch.from_numpy(np.ascontiguousarray(wp.reshape(self.ou, K2, 2).transpose(1, 0, 2))).to(device)
+
+
+_RESAMPLE_TABLES = {}
+
+
+def _resample_cached(fi, fo, device):
+    key = (fi, fo, None if device is None else str(device))
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        t = _RESAMPLE_TABLES[key] = _ResampleTables(fi, fo, device)
+    return t
+
+
+def resample_tables(fi, fo, device=None):
+    """(iu, ou, K, first [ou] int64, w [ou][K] fp64) of Kaldi's LinearResample from fi to fo Hz: output j of a signal x is
+    sum_k w[j % ou][k] * x[first[j % ou] + (j // ou) * iu + k].  Cached per (fi, fo, device); with a device the fp32 copies the
+    kernel reads are cached next to them."""
+    fi, fo = _int_rate(fi, "resample_tables"), _int_rate(fo, "resample_tables")
+    t = _resample_cached(fi, fo, device)
+    return t.iu, t.ou, t.K, t.first, t.w
+
+
+def speed_rates(speed, rate, input_rate=None):
+    """Speed perturbation by `speed` (a decimal string such as "0.9", or a Fraction) of audio that the front end reads at `rate` Hz,
+    recorded at input_rate (default: rate): the (fi, fo) of the one resampling that does it, fi = input_rate * speed -> fo = rate.
+    Read at fo, the result is 1 / speed times as long.  speed == 1 and a fractional fi are refused."""
+    if isinstance(speed, float):
+        raise ValueError("speed: pass the factor as a decimal string or a Fraction, not the float %r" % speed)
+    try:
+        f = fractions.Fraction(speed)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise ValueError("speed: %r is not a decimal factor such as '0.9'" % (speed,))
+    if f <= 0:
+        raise ValueError("speed: factor %s must be positive" % f)
+    if f == 1:
+        raise ValueError("speed: factor 1 is no perturbation")
+    fo = _int_rate(rate, "speed")
+    fi = _int_rate(fo if input_rate is None else input_rate, "speed") * f
+    if fi.denominator != 1:
+        raise ValueError("speed: %s x %s Hz = %s is not a whole number of Hz" % (f, fo if input_rate is None else input_rate, fi))
+    return int(fi), fo
+
+
+def resample(wave, nsamp, fi, fo):
+    """Kaldi's ResampleWaveform on the GPU.  wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or
+    device ints, each in [1, Nmax]), fi -> fo: whole rates in Hz.  Returns (wave_out [B, max n_out] cuda, zeros past each row's
+    count; nsamp_out int64 host array = num_resampled(nsamp, fi, fo)).  fi == fo returns (wave, nsamp) as they came."""
+    fi, fo = _int_rate(fi, "resample"), _int_rate(fo, "resample")
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+        raise ValueError("resample: wave must be a float32 cuda tensor [B, Nmax]")
+    B, Nmax = wave.shape
+    n = _host_ints(nsamp)
+    if n.size != B:
+        raise ValueError("resample: %d sample counts for %d rows" % (n.size, B))
+    if B == 0 or Nmax == 0:
+        raise ValueError("resample: empty batch [%d, %d]" % (B, Nmax))
+    if (n < 1).any() or (n > Nmax).any():
+        bad = int(np.nonzero((n < 1) | (n > Nmax))[0][0])
+        raise ValueError("resample: row %d has %d samples, outside [1, Nmax %d]" % (bad, int(n[bad]), Nmax))
+    if fi == fo:
+        return wave, nsamp
+    iu, ou, K = _resample_first(fi, fo)[:3]
+    if hip.lib().spk_resample_tile(iu, ou, K) == 0:      # before the table is built and before any launch
+        raise ValueError("resample: %d -> %d Hz needs a filter table of %d phases x %d taps, beyond the LDS budget of the kernel "
+                         "(rates with a larger common divisor have fewer phases)" % (fi, fo, ou, K))
+    wave = wave.contiguous()
+    dev = wave.device
+    tab = _resample_cached(fi, fo, dev)
+    n_out = num_resampled(n, fi, fo)
+    Nout = int(n_out.max())
+    ns = torch.from_numpy(n.astype(np.int32)).to(dev)
+    out = torch.empty(B, Nout, device=dev)
+    nd = torch.empty(B, dtype=torch.int32, device=dev)
+    hip.call("spk_resample_fwd", hip.ptr(wave), hip.ptr(ns), B, Nmax, hip.ptr(tab.first_dev), hip.ptr(tab.wq_dev), fi, fo, tab.K,
+             hip.ptr(out), hip.ptr(nd), Nout, hip.stream())
+    return out, n_out
+
+
 # ---- functional API ----
 def fbank(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None):
     """wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or device ints, each >= frame length).
@@ -324,15 +460,33 @@ def select_voiced(x, T, idx, count, cmn=None):
 
 
 class Frontend:
-    """wav -> model input: fbank, then (optional) sliding CMN over all frames and voiced-frame selection, as the recipe's
-    prepare_feats_for_egs.sh.  Frontend(fbank_opts, vad=None, cmn=None)(wave [B, Nmax] cuda, nsamp, utt_ids, seed) ->
-    (feats [B, F, T] cuda, lengths int64 host array): the input predict(x, lengths=...) takes.  A row without voiced frames has
-    length 0 (its column block is all zero): the caller reports and skips it."""
+    """wav -> model input: (optional) resampling, fbank, then (optional) sliding CMN over all frames and voiced-frame selection, as the
+    recipe's prepare_feats_for_egs.sh.  Frontend(fbank_opts, vad=None, cmn=None, input_rate=None, speed=None)(wave [B, Nmax] cuda,
+    nsamp, utt_ids, seed, input_rate=None) -> (feats [B, F, T] cuda, lengths int64 host array): the input predict(x, lengths=...)
+    takes.  A row without voiced frames has length 0 (its column block is all zero): the caller reports and skips it.
 
-    def __init__(self, fbank_opts, vad=None, cmn=None):
+    input_rate: the rate of the samples handed in (one rate per batch; the call's input_rate overrides the constructor's), resampled
+    to fbank_opts.sample_frequency first.  speed: a decimal string or Fraction ("0.9"): the audio is played `speed` times as fast,
+    i.e. resampled from input_rate * speed to sample_frequency - one resampling for both.  Every row must still hold a frame after it."""
+
+    def __init__(self, fbank_opts, vad=None, cmn=None, input_rate=None, speed=None):
         self.fbank_opts, self.vad_opts, self.cmn_opts = fbank_opts, vad, cmn
+        self.input_rate = None if input_rate is None else _int_rate(input_rate, "Frontend")
+        self.speed = speed
+        self.rates(self.input_rate)     # refuse a bad speed / rate pair here, not at the first batch
 
-    def __call__(self, wave, nsamp, utt_ids=None, seed=0):
+    def rates(self, input_rate=None):
+        """(fi, fo) of the resampling in front of the fbank for samples at input_rate (None: the constructor's, else the fbank's)"""
+        fo = _int_rate(self.fbank_opts.sample_frequency, "Frontend") if (input_rate or self.input_rate or self.speed) else None
+        fi = input_rate or self.input_rate or fo
+        if self.speed is not None:
+            return speed_rates(self.speed, fo, fi)
+        return (None, None) if fo is None else (_int_rate(fi, "Frontend"), fo)
+
+    def __call__(self, wave, nsamp, utt_ids=None, seed=0, input_rate=None):
+        fi, fo = self.rates(input_rate)
+        if fi != fo:
+            wave, nsamp = resample(wave, nsamp, fi, fo)
         feats, T, loge = fbank(wave, nsamp, self.fbank_opts, utt_ids, seed)
         if self.vad_opts is None:
             if self.cmn_opts is not None:
@@ -351,14 +505,51 @@ def options_from_configs(fbank_config=None, vad_config=None, cmn_window=0):
     return fb, vad_opts, cmn
 
 
-def wav_scp_batches(wav_scp, fb, batch_size):
+def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsample=False, speed=None):
     """(keys, ingest.WavTable, batches [(indices, Nmax)], indices shorter than one frame) of a wav.scp ('key path' lines; pipe
-    entries are refused): length-sorted by sample count, at most 10 % padded samples per batch"""
+    entries are refused): length-sorted by sample count, at most 10 % padded samples per batch.
+
+    A file whose header rate is above / below fb.sample_frequency is refused, naming it, unless allow_downsample / allow_upsample
+    is set (compute-fbank-feats' flags).  With them every batch holds files of ONE rate, table.rate[indices[0]]: files are grouped
+    by rate, then sorted and padded within a rate.  `short` is judged on the length after resampling (and after `speed`)."""
     from . import ingest
     tab = [l.rstrip().split(None, 1) for l in open(wav_scp) if l.strip()]
     keys = [k for k, _ in tab]
-    table = ingest.WavTable([p for _, p in tab], int(fb.sample_frequency))
-    ok = np.nonzero(table.nsamp >= fb.frame_len)[0]
-    short = np.nonzero(table.nsamp < fb.frame_len)[0]
-    batches = [(ok[b], int(n)) for b, n in ingest.pad_batches(table.nsamp[ok], batch_size, quantum=1)] if ok.size else []
+    table = ingest.WavTable([p for _, p in tab], 0)
+    fo = _int_rate(fb.sample_frequency, "wav_scp_batches")
+    for i in np.nonzero(table.rate != fo)[0]:
+        r = int(table.rate[i])
+        if r > fo and not allow_downsample:
+            raise ValueError("%s: sample rate %d is above sample_frequency %d (--allow-downsample resamples it)" % (table.paths[i], r, fo))
+        if r < fo and not allow_upsample:
+            raise ValueError("%s: sample rate %d is below sample_frequency %d (--allow-upsample resamples it)" % (table.paths[i], r, fo))
+    n_eff = np.zeros(len(keys), dtype=np.int64)
+    for r in np.unique(table.rate):
+        sel = table.rate == r
+        fi = speed_rates(speed, fo, int(r))[0] if speed is not None else int(r)
+        n_eff[sel] = num_resampled(table.nsamp[sel], fi, fo)
+    good = n_eff >= fb.frame_len
+    short = np.nonzero(~good)[0]
+    batches = []
+    for r in np.unique(table.rate[good]):
+        ok = np.nonzero(good & (table.rate == r))[0]
+        batches += [(ok[b], int(n)) for b, n in ingest.pad_batches(table.nsamp[ok], batch_size, quantum=1)]
     return keys, table, batches, short
+
+
+def speed_key(speed, name):
+    """sp<F>-<name>: the key / speaker prefix of local/perturb_data_dir_speed.sh"""
+    return "sp%s-%s" % (speed, name)
+
+
+def speed_side_files(speed, keys, utt2spk=None):
+    """the text of the utt2spk and utt2uniq files perturb_data_dir_speed.sh makes for the copies sp<F>-<utt> of `keys` (original
+    keys, in order): (utt2spk text or None without a speaker map, utt2uniq text).  utt2spk: {utt: spk}; a key without a speaker
+    is an error."""
+    u2s = None
+    if utt2spk is not None:
+        missing = [k for k in keys if k not in utt2spk]
+        if missing:
+            raise ValueError("utt2spk has no speaker for %s" % missing[0])
+        u2s = "".join("%s %s\n" % (speed_key(speed, k), speed_key(speed, utt2spk[k])) for k in keys)
+    return u2s, "".join("%s %s\n" % (speed_key(speed, k), k) for k in keys)

@@ -8,7 +8,15 @@ Writes <out-dir>/feats.ark + feats.scp ([T, F] float32 matrices that train_resne
 voiced frames are reported and skipped.  Dither noise is keyed by (--seed, a stable hash of the utterance key): the features of an
 utterance do not depend on its batch.
 
+Files at another sample rate than --sample-frequency of the fbank config are an error unless --allow-downsample / --allow-upsample
+(compute-fbank-feats' flags) is given; they are then resampled on the GPU with Kaldi's LinearResample.  --speed F writes the
+speed-perturbed copy of the set as the reference's local/perturb_data_dir_speed.sh lays it out: keys sp<F>-<utt>, and with --utt2spk
+the files utt2spk (sp<F>-<utt> sp<F>-<spk>) and utt2uniq (sp<F>-<utt> <utt>); one factor per run.  The audio is resampled from
+F x rate to rate (LinearResample, where the shell script runs `sox speed`), the VAD sees the perturbed audio, and the dither is keyed
+by the written key, so the copies of an utterance get different noise.
+
     python scripts/compute_fbank.py data/train/wav.scp out --fbank-config conf/fbank.conf --vad-config conf/vad.conf --egs
+    python scripts/compute_fbank.py data/train/wav.scp out_sp0.9 --speed 0.9 --utt2spk data/train/utt2spk --fbank-config ...
 """
 import argparse
 import os
@@ -31,19 +39,40 @@ parser.add_argument("--batch-size", type=int, default=128)
 parser.add_argument("--seed", type=int, default=0, help="dither seed")
 parser.add_argument("--threads", type=int, default=4, help="WAV reader threads")
 parser.add_argument("--gpu", type=int, default=0)
+parser.add_argument("--allow-downsample", action="store_true", help="resample files above --sample-frequency instead of refusing them")
+parser.add_argument("--allow-upsample", action="store_true", help="resample files below --sample-frequency instead of refusing them")
+parser.add_argument("--speed", help="speed perturbation factor as a decimal, e.g. 0.9 or 1.1: keys become sp<F>-<utt>")
+parser.add_argument("--utt2spk", help="with --speed: 'utt spk' lines; writes <out-dir>/utt2spk and <out-dir>/utt2uniq of the copies")
 
 
 def main():
     args = parser.parse_args()
     if args.egs and not args.vad_config:
         parser.error("--egs needs --vad-config")
+    if args.utt2spk and not args.speed:
+        parser.error("--utt2spk needs --speed")
     import pytorch_kaldi_resnet_amd  # noqa: F401
     from pytorch_kaldi_resnet_amd import features, kaldi_io
     torch.cuda.set_device(args.gpu)
     fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window if args.egs else 0)
-    keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size)
+    fo = int(fb.sample_frequency)
+    try:
+        if args.speed:
+            features.speed_rates(args.speed, fo)
+        keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size, args.allow_downsample,
+                                                               args.allow_upsample, args.speed)
+    except ValueError as e:
+        parser.error(str(e))
+    utt2spk = dict(l.split()[:2] for l in open(args.utt2spk) if l.strip()) if args.utt2spk else None
+    if args.speed:              # the written keys; the dither stream of a copy is keyed by its own key
+        orig = keys
+        keys = [features.speed_key(args.speed, k) for k in orig]
+
+    def rate_in(r):             # the rate a file of header rate r is resampled FROM (to fo)
+        return features.speed_rates(args.speed, fo, int(r))[0] if args.speed else int(r)
     for i in short:
-        print("compute_fbank: skipping %s: %d samples, shorter than one frame (%d)" % (keys[i], table.nsamp[i], fb.frame_len))
+        print("compute_fbank: skipping %s: %d samples at %d Hz, shorter than one frame (%d)" % (
+            keys[i], features.num_resampled(int(table.nsamp[i]), rate_in(table.rate[i]), fo), fo, fb.frame_len))
     os.makedirs(args.out_dir, exist_ok=True)
     ark = os.path.abspath(os.path.join(args.out_dir, "feats.ark"))
     vark = os.path.abspath(os.path.join(args.out_dir, "vad.ark"))
@@ -58,7 +87,8 @@ def main():
             table.read_padded(idx, nmax, buf, args.threads)
             wave = buf.cuda(non_blocking=True)
             ids = [features.utt_id(keys[i]) for i in idx]
-            feats, T, loge = features.fbank(wave, table.nsamp[idx], fb, ids, args.seed)
+            wave, nsamp = features.resample(wave, table.nsamp[idx], rate_in(table.rate[idx[0]]), fo)     # one rate per batch
+            feats, T, loge = features.fbank(wave, nsamp, fb, ids, args.seed)
             v = None
             if vad_opts is not None:
                 v, vidx, cnt = features.vad(loge, T, vad_opts)
@@ -88,6 +118,12 @@ def main():
             for i, k in enumerate(keys):
                 if i in where:
                     vs.write("%s %s:%d\n" % (k, vark, where[i][2]))
+    if args.speed:
+        done = [k for i, k in enumerate(orig) if i in where]
+        u2s, u2u = features.speed_side_files(args.speed, done, utt2spk)
+        open(os.path.join(args.out_dir, "utt2uniq"), "w").write(u2u)
+        if u2s is not None:
+            open(os.path.join(args.out_dir, "utt2spk"), "w").write(u2s)
     print("compute_fbank: wrote %d of %d utterances to %s" % (len(where), len(keys), args.out_dir))
 
 

@@ -47,6 +47,10 @@ parser.add_argument("--pad-batches", action="store_true",
                          "predict(x, lengths=...): each embedding is that of its utterance alone")
 parser.add_argument("--wav-scp", help="extract from audio: a wav.scp of PCM 16-bit mono files (instead of --decode-scp); the "
                     "Kaldi fbank (+ sliding CMN, + energy VAD frame selection) runs on the GPU (pytorch_kaldi_resnet_amd.features)")
+parser.add_argument("--allow-downsample", action="store_true",
+                    help="with --wav-scp: resample files above the fbank's --sample-frequency on the GPU instead of refusing them")
+parser.add_argument("--allow-upsample", action="store_true",
+                    help="with --wav-scp: resample files below the fbank's --sample-frequency on the GPU instead of refusing them")
 parser.add_argument("--fbank-config", help="with --wav-scp: Kaldi compute-fbank-feats config (conf/fbank.conf)")
 parser.add_argument("--vad-config", help="with --wav-scp: Kaldi compute-vad config (conf/vad.conf): keep voiced frames only")
 parser.add_argument("--cmn-window", type=int, default=0,
@@ -60,8 +64,8 @@ def main():
     args = parser.parse_args()
     if args.wav_scp and args.decode_scp:
         parser.error("--wav-scp and --decode-scp are mutually exclusive")
-    if (args.fbank_config or args.vad_config or args.cmn_window) and not args.wav_scp:
-        parser.error("--fbank-config / --vad-config / --cmn-window need --wav-scp")
+    if (args.fbank_config or args.vad_config or args.cmn_window or args.allow_downsample or args.allow_upsample) and not args.wav_scp:
+        parser.error("--fbank-config / --vad-config / --cmn-window / --allow-downsample / --allow-upsample need --wav-scp")
     if args.pad_batches and not args.native_reader:
         parser.error("--pad-batches needs --native-reader")
     if args.pad_batches and args.chunk_size >= 0:
@@ -237,17 +241,19 @@ def native_generator(model, args):
 
 
 def wav_generator(model, args):
-    """--wav-scp: batches of utterances sorted by sample count (at most 10 % padded samples) read by the native WAV reader into
+    """--wav-scp: batches of utterances of one sample rate sorted by sample count (at most 10 % padded samples; files at another
+    rate than the fbank's are resampled on the GPU, given --allow-downsample / --allow-upsample) read by the native WAV reader into
     pinned memory - the next batch while the GPU runs the front end and the length-masked predict of the current one.  Output
     format as native_generator; utterances shorter than one frame or without voiced frames are reported and skipped."""
     from concurrent.futures import ThreadPoolExecutor
     from pytorch_kaldi_resnet_amd import features, ingest, kaldi_io
     fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window)
     frontend = features.Frontend(fb, vad_opts, cmn)
-    keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size)
+    keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size, args.allow_downsample,
+                                                           args.allow_upsample)
     print("Totally " + str(len(keys)) + " samples")
     for i in short:
-        print("=> skipping {}: {} samples, shorter than one frame".format(keys[i], int(table.nsamp[i])))
+        print("=> skipping {}: {} samples at {} Hz, shorter than one frame".format(keys[i], int(table.nsamp[i]), int(table.rate[i])))
     rank, world = (max(args.rank, 0), max(args.world_size, 1)) if args.distributed else (0, 1)
     mine = batches[rank::world]
     seed = 0 if args.seed is None else args.seed
@@ -276,7 +282,8 @@ def wav_generator(model, args):
             buf = nxt.result()
             nxt = rd.submit(load, n + 1) if n + 1 < len(mine) else None
             wave = buf.cuda(args.gpu, non_blocking=True)
-            feats, lengths = frontend(wave, table.nsamp[b], [features.utt_id(keys[i]) for i in b], seed)
+            feats, lengths = frontend(wave, table.nsamp[b], [features.utt_id(keys[i]) for i in b], seed,
+                                      input_rate=int(table.rate[b[0]]))        # a batch holds files of one rate
             keep = np.nonzero(lengths > 0)[0]
             for r in np.nonzero(lengths == 0)[0]:
                 print("=> skipping {}: no voiced frames".format(keys[b[r]]))
