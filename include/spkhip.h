@@ -374,6 +374,32 @@ int spk_resample_tile(int iu, int ou, int K);
 int spk_resample_fwd(const float* wave_in, const int* nsamp_in, int B, long long Nmax_in, const int* first, const float* wq,
                      int fi, int fo, int K, float* wave_out, int* nsamp_out, long long Nmax_out, void* stream);
 
+/* ---- augmentation (csrc/augment.hip) -------------------------------------------------------------------
+ * Replaces the wav-reverberate commands of stages 2 and 3 of the reference's feature_pre.sh:109-167: the entries that
+ * steps/data/reverberate_data_dir.py:345,365 (--shift-output=true --impulse-response) and steps/data/augment_data_dir.py:112
+ * (--shift-output=true --additive-signals --start-times --snrs; :87-88 the --duration of a background item) write into wav.scp. */
+/* longest impulse response (feature_pre.sh:128 --rir-set-parameter; reverberate_data_dir.py:345 --impulse-response) and longest
+ * early part (int(0.001 fs) + int(0.05 fs) samples) a call takes */
+int spk_augment_max_rir(void);
+int spk_augment_max_early(void);
+/* element counts of the three workspaces of spk_augment_fwd for these maxima: sizes[0] float2 spectra, sizes[1] float y,
+ * sizes[2] double sums.  Rmax / Emax: longest impulse response / early part (0: no row has one), Fmax: longest filled noise,
+ * nd: descriptors.  Refuses Rmax beyond spk_augment_max_rir(). */
+int spk_augment_workspace(int B, long long Nmax, int Rmax, int Emax, long long Fmax, int nd, long long* sizes /*[3]*/);
+/* wave [B][Nmax] (int16-scale samples), nsamp[B] (device) -> out [B][Nmax], zeros past nsamp[b], and clipped[b] += the samples
+ * quantize != 0 (truncation toward zero, then [-32768, 32767]: what a 16-bit WAV pipe carries) clipped; clipped must come zeroed.
+ * Row b: impulse response rir_pool[rir_off[b] .. + R), rir_row[b] = {R (0: none), peak s, early start e0, early length E}
+ * (reverberate_data_dir.py:345 --impulse-response, :365 --shift-output=true: out[j] = g y[j + s]); additive signals
+ * desc_ptr[b] .. desc_ptr[b + 1] in order, descriptor d = noise_pool[desc_off[d] .. + raw), desc_len[d] = {raw length, filled
+ * length D (augment_data_dir.py:87-88 --duration: the signal repeated or cut to D; else D = raw), start sample
+ * (augment_data_dir.py:112 --start-times)}, desc_snr[d] in dB (augment_data_dir.py:112 --snrs).  The formulas: csrc/augment.hip.
+ * twiddle [1024][2] = exp(-2 pi i k / 2048), built by the host in fp64.  All sums of squares in fp64 in a fixed order. */
+int spk_augment_fwd(const float* wave, const int* nsamp, int B, long long Nmax, const float* rir_pool, long long rir_pool_len,
+                    const long long* rir_off, const int* rir_row, int Rmax, int Emax, const float* noise_pool,
+                    long long noise_pool_len, const int* desc_ptr, const long long* desc_off, const int* desc_len,
+                    const double* desc_snr, int nd, long long Fmax, const float* twiddle, float* spectra, float* y, double* work,
+                    int quantize, float* out, unsigned long long* clipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

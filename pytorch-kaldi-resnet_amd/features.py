@@ -3,15 +3,19 @@
 stage 1 of the reference's feature_pre.sh:77-104 and of local/nnet3/xvector/prepare_feats_for_egs.sh:68-70.
 
 The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_vad_count, spk_cmn_select) and csrc/resample.hip
-(spk_resample_fwd: Kaldi's LinearResample, for audio at another sample rate and for speed perturbation); this module parses Kaldi
+(spk_resample_fwd: Kaldi's LinearResample, for audio at another sample rate and for speed perturbation) and csrc/augment.hip
+(spk_augment_fwd: reverberation and additive noise, the wav-reverberate entries of the recipe's augmented wav.scp); this module parses Kaldi
 config files, builds the window / twiddle / mel / resampling tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
 The one deliberate difference from Kaldi: dither is a counter-based N(0,1) draw keyed by (seed, utt_id, frame, position), and the VAD
 sees the same dithered frames as the fbank (Kaldi draws a second dither for its MFCC pass).
 """
 import dataclasses
 import fractions
+import collections
+import ctypes
 import hashlib
 import math
+import shlex
 
 import numpy as np
 import torch
@@ -374,6 +378,294 @@ def resample(wave, nsamp, fi, fo):
     return out, n_out
 
 
+# ---- augmentation (the recipe's wav-reverberate entries; csrc/augment.hip) ----
+AUGMENT_FFT = 2048              # FFT size of the partitioned convolution (blocks of 1024 samples)
+_AUG_TWIDDLE = {}
+
+
+def _aug_twiddle(device):
+    t = _AUG_TWIDDLE.get(str(device))
+    if t is None:
+        k = np.arange(AUGMENT_FFT // 2, dtype=np.float64)
+        tw = np.stack([np.cos(-2 * math.pi * k / AUGMENT_FFT), np.sin(-2 * math.pi * k / AUGMENT_FFT)], 1)
+        t = _AUG_TWIDDLE[str(device)] = torch.from_numpy(tw.astype(np.float32).reshape(-1)).to(device)
+    return t
+
+
+def early_window(h, sample_rate):
+    """(s, e0, e1) of an impulse response h at sample_rate Hz: the peak s (the first maximum of the signed value) and the early
+    part h[e0:e1] = h[max(0, s - int(0.001 fs)) : min(R, s + int(0.05 fs))] whose output power is the signal power of the SNRs"""
+    s = int(np.argmax(h))
+    return s, max(0, s - int(0.001 * sample_rate)), min(len(h), s + int(0.05 * sample_rate))
+
+
+def _aug_samples(v, what):
+    v = np.asarray(v)
+    if v.ndim != 1 or v.dtype != np.float32:
+        raise ValueError("augment: %s must be a one-dimensional float32 array, not %s%s" % (what, v.dtype, list(v.shape)))
+    if v.size == 0:
+        raise ValueError("augment: %s is empty" % what)
+    return v
+
+
+def augment(wave, nsamp, rir=None, noises=None, quantize=False, sample_rate=16000, names=None):
+    """Reverberation and additive noise as Kaldi's `wav-reverberate --shift-output=true` applies them (the contract: DESIGN.md
+    section 6f, restated in tests/augment_ref.py).  wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts.
+    rir: per row a float32 array (the impulse response, any scale) or None.  noises: per row a list of (samples float32 array,
+    duration in seconds or None, start in seconds, snr in dB), added in order; a duration repeats or cuts the samples to
+    int(sample_rate * duration).  quantize: truncate toward zero and clip to [-32768, 32767], what a 16-bit WAV pipe carries.
+    Returns (wave_out [B, Nmax] cuda with zeros past each row's count, clipped int64 host array: the samples quantize clipped per
+    row).  A row with neither an impulse response nor a noise comes back as it went in (quantised, if asked).  names: per row a
+    label (the file) for the error messages.  Everything is refused here, before any launch."""
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+        raise ValueError("augment: wave must be a float32 cuda tensor [B, Nmax]")
+    B, Nmax = wave.shape
+    n = _host_ints(nsamp)
+    if n.size != B:
+        raise ValueError("augment: %d sample counts for %d rows" % (n.size, B))
+    if B == 0 or Nmax == 0:
+        raise ValueError("augment: empty batch [%d, %d]" % (B, Nmax))
+    if (n < 1).any() or (n > Nmax).any():
+        bad = int(np.nonzero((n < 1) | (n > Nmax))[0][0])
+        raise ValueError("augment: row %d has %d samples, outside [1, Nmax %d]" % (bad, int(n[bad]), Nmax))
+    rir = [None] * B if rir is None else list(rir)
+    noises = [[]] * B if noises is None else [list(v) if v is not None else [] for v in noises]
+    if len(rir) != B or len(noises) != B:
+        raise ValueError("augment: %d impulse responses and %d noise lists for %d rows" % (len(rir), len(noises), B))
+    fs = float(sample_rate)
+    if not (math.isfinite(fs) and fs > 0):
+        raise ValueError("augment: sample_rate %r" % (sample_rate,))
+    label = (lambda b: "row %d (%s)" % (b, names[b])) if names is not None else (lambda b: "row %d" % b)
+    lib = hip.lib()
+    max_rir, max_early = lib.spk_augment_max_rir(), lib.spk_augment_max_early()
+    rir_off, rir_row, rir_parts, pos = np.zeros(B, dtype=np.int64), np.zeros((B, 4), dtype=np.int32), [], 0
+    for b, h in enumerate(rir):
+        if h is None:
+            continue
+        h = _aug_samples(h, "the impulse response of %s" % label(b))
+        if h.size > max_rir:
+            raise ValueError("augment: the impulse response of %s has %d samples, more than the %d the kernel is built for"
+                             % (label(b), h.size, max_rir))
+        s, e0, e1 = early_window(h, fs)
+        if not 1 <= e1 - e0 <= max_early:
+            raise ValueError("augment: the early part of the impulse response of %s has %d samples at %g Hz, outside [1, %d]"
+                             % (label(b), e1 - e0, fs, max_early))
+        rir_off[b], rir_row[b] = pos, (h.size, s, e0, e1 - e0)
+        rir_parts.append(h)
+        pos += h.size
+    desc_ptr, d_off, d_len, d_snr, n_parts, npos, seen, nonzero = [0], [], [], [], [], 0, {}, {}
+    for b, lst in enumerate(noises):
+        for item in lst:
+            if len(item) != 4:
+                raise ValueError("augment: a noise of %s is not (samples, duration, start, snr)" % label(b))
+            r, duration, start, snr = item
+            r = _aug_samples(r, "a noise of %s" % label(b))
+            if id(r) not in seen:
+                seen[id(r)] = npos
+                n_parts.append(r)
+                npos += r.size
+            if not (isinstance(snr, (int, float, np.integer, np.floating)) and math.isfinite(snr)):
+                raise ValueError("augment: a noise of %s has the non-finite SNR %r" % (label(b), snr))
+            if not (math.isfinite(start) and start >= 0):
+                raise ValueError("augment: a noise of %s starts at %r s (negative or not finite)" % (label(b), start))
+            fill = r.size if duration is None else int(fs * duration) if math.isfinite(duration) else 0
+            if not 1 <= fill < 2 ** 30 or start * fs >= 2 ** 30:
+                raise ValueError("augment: a noise of %s with duration %r s and start %r s gives %d samples from sample %d"
+                                 % (label(b), duration, start, fill, int(min(start * fs, 2.0 ** 62))))
+            if (id(r), min(fill, r.size)) not in nonzero:       # q_k is the power of what is added: the filled signal
+                nonzero[(id(r), min(fill, r.size))] = bool(np.any(r[:fill]))
+            if not nonzero[(id(r), min(fill, r.size))]:
+                raise ValueError("augment: a noise of %s is all zero over the %d samples that are added (its power scales "
+                                 "the SNR)" % (label(b), min(fill, r.size)))
+            d_off.append(seen[id(r)])
+            d_len.append((r.size, fill, int(start * fs)))
+            d_snr.append(float(snr))
+        desc_ptr.append(len(d_off))
+    nd = len(d_off)
+    if B + nd > 65535:
+        raise ValueError("augment: %d rows with %d noises in one call (at most 65535 together)" % (B, nd))
+    Rmax = int(rir_row[:, 0].max())
+    Emax = int(rir_row[:, 3].max())
+    Fmax = max([v[1] for v in d_len], default=0)
+    sizes = (ctypes.c_longlong * 3)()
+    hip.call("spk_augment_workspace", B, Nmax, Rmax, Emax, Fmax, nd, sizes)
+    wave = wave.contiguous()
+    dev = wave.device
+
+    def dv(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+    ns = dv(n, np.int32)
+    rpool = dv(np.concatenate(rir_parts), np.float32) if rir_parts else None
+    npool = dv(np.concatenate(n_parts), np.float32) if n_parts else None
+    spectra = torch.empty(2 * sizes[0], device=dev) if sizes[0] else None
+    y = torch.empty(max(sizes[1], 1), device=dev)
+    work = torch.empty(max(sizes[2], 1), dtype=torch.float64, device=dev)
+    out = torch.empty(B, Nmax, device=dev)
+    clipped = torch.zeros(B, dtype=torch.int64, device=dev)
+    t_off, t_row, t_ptr = dv(rir_off, np.int64), dv(rir_row, np.int32), dv(desc_ptr, np.int32)
+    t_doff = dv(d_off, np.int64) if nd else None
+    t_dlen = dv(np.asarray(d_len).reshape(-1), np.int32) if nd else None
+    t_dsnr = dv(d_snr, np.float64) if nd else None
+    hip.call("spk_augment_fwd", hip.ptr(wave), hip.ptr(ns), B, Nmax, hip.ptr(rpool), pos, hip.ptr(t_off), hip.ptr(t_row), Rmax, Emax,
+             hip.ptr(npool), npos, hip.ptr(t_ptr), hip.ptr(t_doff), hip.ptr(t_dlen), hip.ptr(t_dsnr), nd, Fmax,
+             hip.ptr(_aug_twiddle(dev)) if Rmax else None, hip.ptr(spectra), hip.ptr(y), hip.ptr(work), int(bool(quantize)),
+             hip.ptr(out), hip.ptr(clipped), hip.stream())
+    return out, clipped.cpu().numpy()
+
+
+WavEntry = collections.namedtuple("WavEntry", "path rir_path noises augmented")
+WavEntry.__doc__ = """one wav.scp entry: the speech file, the impulse-response file or None, the additive signals
+[(path, duration or None, start seconds, snr dB)], and whether anything is applied at all"""
+
+
+def _pipe_error(text, why):
+    return ValueError("wav.scp pipe entry not supported (%s): %r" % (why, text))
+
+
+def _reverberate_options(tokens, text, top):
+    """{name: value} of the --name=value tokens of one wav-reverberate command; `top`: the options of an entry, else of an item"""
+    allowed = ("shift-output", "impulse-response", "additive-signals", "start-times", "snrs") if top else ("duration",)
+    out = {}
+    for t in tokens:
+        if not t.startswith("--") or "=" not in t:
+            raise _pipe_error(text, "expected --name=value, got %r" % t)
+        name, val = t[2:].split("=", 1)
+        if name not in allowed or name in out:
+            raise _pipe_error(text, "option --%s" % name)
+        out[name] = val
+    return out
+
+
+def _floats(val, what, text):
+    try:
+        return [float(v) for v in val.split(",")]
+    except ValueError:
+        raise _pipe_error(text, "%s %r" % (what, val))
+
+
+def parse_wav_entry(text):
+    """The value of a wav.scp line -> WavEntry.  Accepted are a plain path and exactly the commands the recipe's two scripts
+    write (the reference's feature_pre.sh:109-167):
+        cat PATH | wav-reverberate --shift-output=true [--impulse-response="RIR"] [--additive-signals= --start-times= --snrs=] - - |
+                                      (steps/data/reverberate_data_dir.py:345,365; augment_data_dir.py:116 on such a `cat` entry)
+        wav-reverberate --shift-output=true --additive-signals='ITEM,..' --start-times='..' --snrs='..' PATH - |
+                                                                            (steps/data/augment_data_dir.py:112)
+    with ITEM a plain path or `wav-reverberate --duration=D "PATH" - |` (augment_data_dir.py:87-88).  Everything else - another
+    command, another pipe in front, --shift-output=false, a top-level --duration, an impulse response inside an item, an unknown
+    option, lists of unequal length - is a ValueError that says `pipe` and quotes the entry."""
+    text = text.strip()
+    if not text.endswith("|"):
+        return WavEntry(text, None, [], False)
+    try:
+        tok = shlex.split(text)
+    except ValueError as e:
+        raise _pipe_error(text, str(e))
+    if len(tok) >= 7 and tok[0] == "cat" and tok[2] == "|" and tok[3] == "wav-reverberate" and tok[-3:] == ["-", "-", "|"]:
+        path, opts = tok[1], _reverberate_options(tok[4:-3], text, True)
+        if "impulse-response" not in opts and "additive-signals" not in opts:
+            raise _pipe_error(text, "neither --impulse-response nor --additive-signals")
+    elif len(tok) >= 5 and tok[0] == "wav-reverberate" and tok[-2:] == ["-", "|"] and not tok[-3].startswith("-"):
+        path, opts = tok[-3], _reverberate_options(tok[1:-3], text, True)
+        if "impulse-response" in opts or "additive-signals" not in opts:
+            raise _pipe_error(text, "expected --additive-signals and no --impulse-response")
+    else:
+        raise _pipe_error(text, "not one of the wav-reverberate forms of the recipe")
+    if "|" in path or not path:
+        raise _pipe_error(text, "speech file %r" % path)
+    if opts.get("shift-output") != "true":
+        raise _pipe_error(text, "--shift-output=%s" % opts.get("shift-output", "false (the default)"))
+    noises = []
+    if "additive-signals" in opts:
+        if "start-times" not in opts or "snrs" not in opts:
+            raise _pipe_error(text, "--additive-signals needs --start-times and --snrs")
+        items = [v.strip() for v in opts["additive-signals"].split(",")]
+        starts, snrs = _floats(opts["start-times"], "--start-times", text), _floats(opts["snrs"], "--snrs", text)
+        if not len(items) == len(starts) == len(snrs):
+            raise _pipe_error(text, "%d signals, %d start times, %d SNRs" % (len(items), len(starts), len(snrs)))
+        for item, start, snr in zip(items, starts, snrs):
+            duration = None
+            if item.endswith("|"):
+                try:
+                    it = shlex.split(item)
+                except ValueError as e:
+                    raise _pipe_error(text, str(e))
+                if len(it) != 5 or it[0] != "wav-reverberate" or it[3:] != ["-", "|"] or it[2].startswith("-"):
+                    raise _pipe_error(text, "additive signal %r" % item)
+                d = _floats(_reverberate_options(it[1:2], text, False).get("duration", ""), "--duration", text)
+                duration, item = d[0], it[2]
+            if not item or " " in item or "|" in item:
+                raise _pipe_error(text, "additive signal %r" % item)
+            noises.append((item, duration, start, snr))
+    elif "start-times" in opts or "snrs" in opts:
+        raise _pipe_error(text, "--start-times / --snrs without --additive-signals")
+    return WavEntry(path, opts.get("impulse-response"), noises, True)
+
+
+def read_wav_scp(wav_scp):
+    """(keys, [WavEntry]) of a wav.scp"""
+    tab = [l.rstrip().split(None, 1) for l in open(wav_scp) if l.strip()]
+    return [k for k, _ in tab], [parse_wav_entry(p) for _, p in tab]
+
+
+AUX_CACHE_BYTES = 2 << 30       # samples of impulse-response and noise files kept on the host between batches
+
+
+class WavAugmentation:
+    """What an augmented wav.scp adds to the table of its speech files: the parsed entries and ONE table of the distinct
+    impulse-response and noise files (each header probed once per run), whose samples are read once and kept on the host (up to
+    AUX_CACHE_BYTES).  Every such file must have its speech file's rate."""
+
+    def __init__(self, table, entries):
+        from . import ingest
+        self.entries = entries
+        paths = sorted({p for e in entries for p in self.files(e)})
+        self.aux = ingest.WavTable(paths, 0)
+        self.index = {p: i for i, p in enumerate(paths)}
+        self.cache = collections.OrderedDict()
+        self.reads = 0                  # files read so far (a file is read again only after the cache dropped it)
+        for i, e in enumerate(entries):
+            for p in self.files(e):
+                r = int(self.aux.rate[self.index[p]])
+                if r != int(table.rate[i]):
+                    raise ValueError("%s: sample rate %d differs from the %d Hz of the speech file %s it is applied to"
+                                     % (p, r, int(table.rate[i]), table.paths[i]))
+
+    @staticmethod
+    def files(e):
+        return ([e.rir_path] if e.rir_path else []) + [v[0] for v in e.noises]
+
+    def samples(self, path):
+        v = self.cache.get(path)
+        if v is None:
+            i = self.index[path]
+            nmax = int(self.aux.nsamp[i])
+            if nmax < 1:
+                raise ValueError("%s: no samples" % path)
+            buf = torch.empty(1, nmax)
+            self.aux.read_padded(np.asarray([i]), nmax, buf, 1)
+            v = self.cache[path] = buf.numpy()[0]
+            self.reads += 1
+            while len(self.cache) > 1 and sum(a.nbytes for a in self.cache.values()) > AUX_CACHE_BYTES:
+                self.cache.popitem(last=False)
+        return v
+
+    def inputs(self, idx):
+        """(rir, noises, names) of the rows idx, as features.augment takes them"""
+        rir, noises, names = [], [], []
+        for i in idx:
+            e = self.entries[i]
+            rir.append(self.samples(e.rir_path) if e.rir_path else None)
+            noises.append([(self.samples(p), d, st, snr) for p, d, st, snr in e.noises])
+            names.append(e.path if not e.augmented else "%s with %s" % (e.path, ", ".join(self.files(e))))
+        return rir, noises, names
+
+
+def augment_inputs(table, idx):
+    """(rir, noises, names) for features.augment of the rows idx of the table of an augmented wav.scp
+    (wav_scp_batches(..., augment=True): table.augmentation is its WavAugmentation)"""
+    return table.augmentation.inputs(idx)
+
+
 # ---- functional API ----
 def fbank(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None):
     """wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or device ints, each >= frame length).
@@ -505,17 +797,25 @@ def options_from_configs(fbank_config=None, vad_config=None, cmn_window=0):
     return fb, vad_opts, cmn
 
 
-def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsample=False, speed=None):
+def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsample=False, speed=None, augment=False):
     """(keys, ingest.WavTable, batches [(indices, Nmax)], indices shorter than one frame) of a wav.scp ('key path' lines; pipe
-    entries are refused): length-sorted by sample count, at most 10 % padded samples per batch.
+    entries are refused, except - with augment=True, for a caller that applies them - the wav-reverberate entries that
+    parse_wav_entry accepts): length-sorted by the speech file's sample count, at most 10 % padded samples per batch.  With such
+    entries the table is the speech files' and table.augmentation a WavAugmentation (augment_inputs(table, idx) gives what
+    features.augment takes); wav_scp may also be what read_wav_scp returned, (keys, entries), so that a caller parses the file once;
+    without any, nothing differs from a call without `augment`.
 
     A file whose header rate is above / below fb.sample_frequency is refused, naming it, unless allow_downsample / allow_upsample
     is set (compute-fbank-feats' flags).  With them every batch holds files of ONE rate, table.rate[indices[0]]: files are grouped
     by rate, then sorted and padded within a rate.  `short` is judged on the length after resampling (and after `speed`)."""
     from . import ingest
-    tab = [l.rstrip().split(None, 1) for l in open(wav_scp) if l.strip()]
-    keys = [k for k, _ in tab]
-    table = ingest.WavTable([p for _, p in tab], 0)
+    keys, entries = read_wav_scp(wav_scp) if isinstance(wav_scp, str) else wav_scp
+    augmented = any(e.augmented for e in entries)
+    if augmented and not augment:
+        raise ValueError("wav.scp pipe entries are not applied here: %r" % [e for e in entries if e.augmented][0].path)
+    table = ingest.WavTable([e.path for e in entries], 0)
+    if augmented:
+        table.augmentation = WavAugmentation(table, entries)
     fo = _int_rate(fb.sample_frequency, "wav_scp_batches")
     for i in np.nonzero(table.rate != fo)[0]:
         r = int(table.rate[i])

@@ -80,6 +80,10 @@ _SIGS = {
     "spk_cmn_select": [_P] * 6 + [_I] * 5 + [_P],
     "spk_resample_tile": [_I, _I, _I],
     "spk_resample_fwd": [_P, _P, _I, _L, _P, _P, _I, _I, _I, _P, _P, _L, _P],
+    "spk_augment_max_rir": [],
+    "spk_augment_max_early": [],
+    "spk_augment_workspace": [_I, _L, _I, _I, _L, _I, ctypes.POINTER(_L)],
+    "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
 _lib = None

@@ -15,12 +15,20 @@ the files utt2spk (sp<F>-<utt> sp<F>-<spk>) and utt2uniq (sp<F>-<utt> <utt>); on
 F x rate to rate (LinearResample, where the shell script runs `sox speed`), the VAD sees the perturbed audio, and the dither is keyed
 by the written key, so the copies of an utterance get different noise.
 
+Entries that are the recipe's wav-reverberate commands (feature_pre.sh:109-167: the reverb, noise, music and babble copies that
+steps/data/reverberate_data_dir.py and steps/data/augment_data_dir.py write; the grammar: features.parse_wav_entry) are applied on
+the GPU (features.augment) and quantised to 16 bits as the pipe would, before resampling and the fbank; the number of samples the
+quantisation clipped is reported.  The dither is keyed by the written key.  --speed is refused with such entries.  --vad-scp FILE
+(with --egs) takes the voiced frames from that file's 0/1 vectors under the written keys instead of computing the VAD: the
+recipe copies the clean set's vad.scp to the augmented copies.
+
     python scripts/compute_fbank.py data/train/wav.scp out --fbank-config conf/fbank.conf --vad-config conf/vad.conf --egs
     python scripts/compute_fbank.py data/train/wav.scp out_sp0.9 --speed 0.9 --utt2spk data/train/utt2spk --fbank-config ...
 """
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -42,27 +50,39 @@ parser.add_argument("--gpu", type=int, default=0)
 parser.add_argument("--allow-downsample", action="store_true", help="resample files above --sample-frequency instead of refusing them")
 parser.add_argument("--allow-upsample", action="store_true", help="resample files below --sample-frequency instead of refusing them")
 parser.add_argument("--speed", help="speed perturbation factor as a decimal, e.g. 0.9 or 1.1: keys become sp<F>-<utt>")
+parser.add_argument("--vad-scp", help="with --egs: vad.scp of 0/1 vectors per written key; the voiced frames come from it, not from compute-vad")
+parser.add_argument("--time-batches", action="store_true", help="also print the seconds the batch loop took (tools/augment_bench.py)")
 parser.add_argument("--utt2spk", help="with --speed: 'utt spk' lines; writes <out-dir>/utt2spk and <out-dir>/utt2uniq of the copies")
 
 
 def main():
     args = parser.parse_args()
-    if args.egs and not args.vad_config:
+    if args.egs and not args.vad_config and not args.vad_scp:
         parser.error("--egs needs --vad-config")
+    if args.vad_scp and not args.egs:
+        parser.error("--vad-scp needs --egs")
     if args.utt2spk and not args.speed:
         parser.error("--utt2spk needs --speed")
     import pytorch_kaldi_resnet_amd  # noqa: F401
     from pytorch_kaldi_resnet_amd import features, kaldi_io
+    try:
+        parsed = features.read_wav_scp(args.wav_scp)
+        augmented = any(e.augmented for e in parsed[1])
+    except ValueError as e:
+        parser.error(str(e))
+    if augmented and args.speed:
+        parser.error("--speed does not combine with wav-reverberate entries in %s" % args.wav_scp)
     torch.cuda.set_device(args.gpu)
     fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window if args.egs else 0)
     fo = int(fb.sample_frequency)
     try:
         if args.speed:
             features.speed_rates(args.speed, fo)
-        keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size, args.allow_downsample,
-                                                               args.allow_upsample, args.speed)
+        keys, table, batches, short = features.wav_scp_batches(parsed, fb, args.batch_size, args.allow_downsample,
+                                                               args.allow_upsample, args.speed, augment=True)
     except ValueError as e:
         parser.error(str(e))
+    vad_scp = dict(l.split(None, 1) for l in open(args.vad_scp) if l.strip()) if args.vad_scp else None
     utt2spk = dict(l.split()[:2] for l in open(args.utt2spk) if l.strip()) if args.utt2spk else None
     if args.speed:              # the written keys; the dither stream of a copy is keyed by its own key
         orig = keys
@@ -80,17 +100,41 @@ def main():
     # utterance is kept, and feats.scp / vad.scp / utt2num_frames are written in wav.scp order at the end - an scp line may
     # point anywhere in its ark
     where = {}                  # utterance index -> (feats offset, frames, vad offset or None)
+    clipped = 0                 # samples the 16-bit quantisation of augmented entries clipped
     write_vad = vad_opts is not None and not args.egs
+    t_start = time.perf_counter()
     with torch.no_grad(), open(ark, "wb") as fa, open(vark if write_vad else os.devnull, "wb") as fv:
         for idx, nmax in batches:
             buf = torch.empty(len(idx), nmax).pin_memory()
             table.read_padded(idx, nmax, buf, args.threads)
             wave = buf.cuda(non_blocking=True)
             ids = [features.utt_id(keys[i]) for i in idx]
+            if augmented:
+                rir, noises, names = features.augment_inputs(table, idx)
+                try:
+                    wave, nclip = features.augment(wave, table.nsamp[idx], rir, noises, quantize=True,
+                                                   sample_rate=int(table.rate[idx[0]]), names=names)
+                except ValueError as e:
+                    sys.exit("compute_fbank: %s" % e)
+                clipped += int(nclip.sum())
             wave, nsamp = features.resample(wave, table.nsamp[idx], rate_in(table.rate[idx[0]]), fo)     # one rate per batch
             feats, T, loge = features.fbank(wave, nsamp, fb, ids, args.seed)
             v = None
-            if vad_opts is not None:
+            if vad_scp is not None:
+                vidx = np.zeros((len(idx), feats.shape[2]), dtype=np.int32)
+                cnt = np.zeros(len(idx), dtype=np.int64)
+                for r, i in enumerate(idx):
+                    if keys[i] not in vad_scp:
+                        sys.exit("compute_fbank: %s has no entry in %s" % (keys[i], args.vad_scp))
+                    vv = kaldi_io.read_vec_flt(vad_scp[keys[i]].strip())
+                    if vv.shape[0] != T[r]:
+                        sys.exit("compute_fbank: %s has %d frames but its vector in %s has %d" % (keys[i], T[r], args.vad_scp,
+                                                                                                 vv.shape[0]))
+                    nz = np.nonzero(vv != 0)[0]
+                    cnt[r] = nz.size
+                    vidx[r, :nz.size] = nz
+                feats, T = features.select_voiced(feats, T, torch.from_numpy(vidx).cuda(), cnt, cmn)
+            elif vad_opts is not None:
                 v, vidx, cnt = features.vad(loge, T, vad_opts)
                 if args.egs:
                     feats, T = features.select_voiced(feats, T, vidx, cnt, cmn)
@@ -107,6 +151,7 @@ def main():
                     voff = fv.tell()
                     kaldi_io.write_vec_flt(fv, v[r, :T[r]].astype(np.float32))
                 where[i] = (off, int(T[r]), voff)
+    t_batches = time.perf_counter() - t_start
     with open(os.path.join(args.out_dir, "feats.scp"), "w") as fs, \
             open(os.path.join(args.out_dir, "utt2num_frames"), "w") as fn:
         for i, k in enumerate(keys):
@@ -124,6 +169,10 @@ def main():
         open(os.path.join(args.out_dir, "utt2uniq"), "w").write(u2u)
         if u2s is not None:
             open(os.path.join(args.out_dir, "utt2spk"), "w").write(u2s)
+    if augmented:
+        print("compute_fbank: %d samples clipped by the 16-bit quantisation of the augmented entries" % clipped)
+    if args.time_batches:
+        print("compute_fbank: %.3f s for the batches" % t_batches)
     print("compute_fbank: wrote %d of %d utterances to %s" % (len(where), len(keys), args.out_dir))
 
 
