@@ -400,6 +400,24 @@ int spk_augment_fwd(const float* wave, const int* nsamp, int B, long long Nmax, 
                     const double* desc_snr, int nd, long long Fmax, const float* twiddle, float* spectra, float* y, double* work,
                     int quantize, float* out, unsigned long long* clipped, void* stream);
 
+/* ---- Kaldi's one-byte compressed matrices (csrc/cm.hip) -------------------------------------------------
+ * The 'CM ' format that Kaldi's feature scripts write by default (the reference reads it in scripts/kaldi_io.py:427-460): per
+ * matrix (min, range), per column four 16-bit points (p0, p25, p75, p100), one byte per value, column-major.  All arithmetic in
+ * fp32, every operation rounded on its own:  U(p) = min + (range * 1.52590218966964e-05f) * p,  P = U(p), and a code c stands for
+ *   c <= 64: P0 + (P25 - P0) * c * (1/64.f);  c <= 192: P25 + (P75 - P25) * (c - 64) * (1/128.f);
+ *   else P75 + (P100 - P75) * (c - 192) * (1/63.f). */
+/* codes [B][F][T] (libspkio: spk_ark_read_crop_codes / _padded_codes), colhdr [B][F][4] = P (16-byte aligned), lengths [B] or
+ * NULL -> out [B][F][T] fp32 (4-byte aligned), 0 for t >= lengths[b].  The bits the host readers give. */
+int spk_cm_decode(const unsigned char* codes, const float* colhdr, const int* lengths, int B, int F, int T, float* out, void* stream);
+/* x [B][F][Tcap], T[b] frames of row b (0 <= T[b] <= Tcap; nothing past T[b] is read) -> per row the parts of the record of its
+ * [T[b]][F] matrix: minrange [B][2], hdr [B][F][4] (the 16-bit points as ints), codes [B][F][Tcap] (t < T[b] written, the rest
+ * untouched).  T[b] == 0 writes nothing for b.  A row holding a non-finite value, or whose range overflows, gets minrange (NaN, NaN)
+ * and nothing else.  ws: B * F * 2 floats.  Points: with s the sorted column and q = T / 4, (s[0], s[q], s[3q], s[T - 1]) for
+ * T >= 5 and (s[0], s[1], s[2], s[3]) below, through Q(v) = (int)(clamp((v - min) / range, 0, 1) * 65535 + 0.499f) and kept
+ * strictly increasing; found by a radix select, so T is not bounded by LDS. */
+int spk_cm_compress(const float* x, const int* T, int B, int F, int Tcap, float* ws, float* minrange, int* hdr, unsigned char* codes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

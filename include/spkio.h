@@ -1,4 +1,4 @@
-/* libspkio - native batch ingest of Kaldi float32 matrices (host-side C ABI, no device code).
+/* libspkio - native batch ingest of Kaldi float32 and one-byte compressed matrices (host-side C ABI, no device code).
  * Replaces, for fixed-length training batches, the per-sample path of the reference:
  *   kaldi_io.read_mat (scripts/kaldi_io.py:376-410, open_or_fd :41-71) -> random crop + transpose
  *   (scripts/datasets.py:59-72) -> default collate.
@@ -21,6 +21,25 @@ int spk_ark_read_crop(int B, const char* const* paths, const int64_t* data_offse
  * length-masked predict over a length-sorted batch */
 int spk_ark_read_padded(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows, int F, int T,
                         float* out, int nthreads);
+/* Kaldi's one-byte compressed matrices ('CM ') next to float32 'FM '.  kinds[i]: 0 'FM ', 1 'CM ';
+ * data_offsets[i] of a 'CM ' entry is the byte of its first column header; its header sizes are checked against the file length.
+ * 'CM2' / 'CM3' / 'DM ' stay refused.  spk_ark_probe above refuses 'CM ' (it cannot say which kind an entry is). */
+int spk_ark_probe_kinds(int n, const char* const* paths, const int64_t* offsets, int32_t* rows, int32_t* cols,
+                        int64_t* data_offsets, int32_t* kinds);
+/* spk_ark_read_crop / spk_ark_read_padded with the probed kinds; 'FM ' and 'CM ' entries may be mixed.  A 'CM ' entry is decoded
+ * on the host in float32, every operation rounded on its own: the bits of kaldi_io.read_mat.  (The two functions above take the
+ * same entries and find the kind in front of each payload.) */
+int spk_ark_read_crop_kinds(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows,
+                            const int32_t* starts, const int32_t* kinds, int F, int T, float* out, int nthreads);
+int spk_ark_read_padded_kinds(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows,
+                              const int32_t* kinds, int F, int T, float* out, int nthreads);
+/* 'CM ' entries as stored, the input of the GPU decode in libspkhip: codes[b][f][t] = the code of frame starts[b] + t, bin f (padded form:
+ * frame t, 0 for rows[b] <= t < T), colhdr[b][f][4] = the float32 values of the column header (p0, p25, p75, p100):
+ * min + (range * 1.52590218966964e-05f) * p. */
+int spk_ark_read_crop_codes(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows,
+                            const int32_t* starts, int F, int T, uint8_t* codes, float* colhdr, int nthreads);
+int spk_ark_read_padded_codes(int B, const char* const* paths, const int64_t* data_offsets, const int32_t* rows, int F, int T,
+                              uint8_t* codes, float* colhdr, int nthreads);
 void spk_ark_close_all(void);
 /* text-ark embedding writer: out <- "key [ v0 v1 ... ]\n" per row of v[n][D], each value printed exactly as numpy's
  * str(np.float32) does - the line format of the reference's scripts/decode.py:199-206.  Returns the bytes written

@@ -244,6 +244,79 @@ def _host_ints(v, dtype=np.int64):
     return np.asarray(v, dtype=dtype).reshape(-1)
 
 
+# ---- Kaldi's one-byte compressed matrices ('CM '; csrc/cm.hip) ----
+def compress(feats, T):
+    """Kaldi's CompressedMatrix (format 'CM ': one byte per value) of every row of a batch of features, on the GPU.
+    feats: float32 cuda [B, F, Tcap], T: frames per row (host or device ints in [0, Tcap]); whatever lies past T[b] is ignored.
+    Returns cuda tensors (minrange [B, 2] float32, hdr [B, F, 4] int32 - the 16-bit column headers -, codes [B, F, Tcap] uint8, zero
+    past T[b]): codes[b, :, :T[b]] is the column-major payload of the [T[b], F] matrix, kaldi_io.write_cm writes a record from these
+    parts.  A row with T[b] = 0 has nothing written (zeros).  A row with a non-finite value (or whose range overflows float32) is
+    refused: ValueError naming the row."""
+    if not isinstance(feats, torch.Tensor) or feats.dim() != 3 or feats.dtype != torch.float32 or not feats.is_cuda:
+        raise ValueError("compress: feats must be a float32 cuda tensor [B, F, Tcap]")
+    B, F, Tcap = feats.shape
+    n = _host_ints(T, np.int32)
+    if n.size != B:
+        raise ValueError("compress: %d frame counts for %d rows" % (n.size, B))
+    if B == 0 or F == 0:
+        raise ValueError("compress: empty batch [%d, %d, %d]" % (B, F, Tcap))
+    if (n < 0).any() or (n > Tcap).any():
+        bad = int(np.nonzero((n < 0) | (n > Tcap))[0][0])
+        raise ValueError("compress: row %d has %d frames, outside [0, Tcap %d]" % (bad, int(n[bad]), Tcap))
+    dev = feats.device
+    minrange = torch.zeros(B, 2, device=dev)
+    hdr = torch.zeros(B, F, 4, dtype=torch.int32, device=dev)
+    codes = torch.zeros(B, F, Tcap, dtype=torch.uint8, device=dev)
+    if Tcap == 0:
+        return minrange, hdr, codes
+    feats = feats.contiguous()
+    tdev = torch.from_numpy(n).to(dev)
+    ws = torch.empty(B, F, 2, device=dev)
+    hip.call("spk_cm_compress", hip.ptr(feats), hip.ptr(tdev), B, F, Tcap, hip.ptr(ws), hip.ptr(minrange), hip.ptr(hdr), hip.ptr(codes),
+             hip.stream())
+    ok = torch.isfinite(minrange).all(dim=1).cpu().numpy()
+    if not ok.all():
+        bad = int(np.nonzero(~ok)[0][0])
+        raise ValueError("compress: row %d holds a non-finite value (or its range overflows float32)" % bad)
+    return minrange, hdr, codes
+
+
+def column_headers(minrange, hdr):
+    """the float32 values of 16-bit column headers: min + (range * 1.52590218966964e-05f) * p, every operation rounded to float32
+    on its own (on the host: numpy never fuses).  minrange [B, 2], hdr [B, F, 4] (tensors or arrays) -> float32 array [B, F, 4]"""
+    mr = minrange.detach().cpu().numpy() if isinstance(minrange, torch.Tensor) else np.asarray(minrange)
+    h = hdr.detach().cpu().numpy() if isinstance(hdr, torch.Tensor) else np.asarray(hdr)
+    mr = mr.astype(np.float32).reshape(-1, 1, 2)
+    scale = mr[:, :, 1:2] * np.float32(1.52590218966964e-05)
+    return (mr[:, :, 0:1] + scale * h.astype(np.float32)).astype(np.float32)
+
+
+def decompress(codes, colhdr, lengths=None, out=None):
+    """The GPU decode of 'CM ' codes.  codes: uint8 cuda [B, F, T] (as ArkTable.read_crop_codes / read_padded_codes or compress
+    give them), colhdr: float32 cuda [B, F, 4], the decoded column headers (column_headers), lengths: None or per-row frame counts
+    (cuda int32 tensor, or host ints).  Returns float32 [B, F, T] (into `out` when given: contiguous, 4-byte aligned), zero for
+    t >= lengths[b]; the same bits as kaldi_io.read_mat of the record."""
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 3 or codes.dtype != torch.uint8 or not codes.is_cuda:
+        raise ValueError("decompress: codes must be a uint8 cuda tensor [B, F, T]")
+    B, F, T = codes.shape
+    if B == 0 or F == 0 or T == 0:
+        raise ValueError("decompress: empty batch [%d, %d, %d]" % (B, F, T))
+    if not isinstance(colhdr, torch.Tensor) or colhdr.dtype != torch.float32 or tuple(colhdr.shape) != (B, F, 4) or not colhdr.is_cuda:
+        raise ValueError("decompress: colhdr must be a float32 cuda tensor [%d, %d, 4]" % (B, F))
+    dev = codes.device
+    if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int32):
+        lengths = torch.from_numpy(_host_ints(lengths, np.int32)).to(dev)
+    if lengths is not None and lengths.numel() != B:
+        raise ValueError("decompress: %d lengths for %d rows" % (lengths.numel(), B))
+    if out is None:
+        out = torch.empty(B, F, T, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, F, T) or not out.is_cuda:
+        raise ValueError("decompress: out must be a float32 cuda tensor [%d, %d, %d]" % (B, F, T))
+    hip.call("spk_cm_decode", hip.ptr(codes.contiguous()), hip.ptr(colhdr.contiguous()), hip.ptr(lengths), B, F, T, hip.ptr(out),
+             hip.stream())
+    return out
+
+
 # ---- resampling (Kaldi's LinearResample; csrc/resample.hip) ----
 LOWPASS_FILTER_WIDTH = 6        # zero crossings of the windowed sinc (Kaldi's ResampleWaveform)
 

@@ -83,6 +83,8 @@ _SIGS = {
     "spk_augment_max_rir": [],
     "spk_augment_max_early": [],
     "spk_augment_workspace": [_I, _L, _I, _I, _L, _I, ctypes.POINTER(_L)],
+    "spk_cm_decode": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "spk_cm_compress": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 

@@ -32,6 +32,15 @@ def lib():
         l.spk_ark_read_crop.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_int]
         l.spk_ark_read_padded.argtypes = [ctypes.c_int, cpp, i64p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        l.spk_ark_probe_kinds.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, i64p, i32p]
+        l.spk_ark_read_crop_kinds.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_int]
+        l.spk_ark_read_padded_kinds.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_int]
+        l.spk_ark_read_crop_codes.argtypes = [ctypes.c_int, cpp, i64p, i32p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_int]
+        l.spk_ark_read_padded_codes.argtypes = [ctypes.c_int, cpp, i64p, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int]
         l.spk_wav_probe.argtypes = [ctypes.c_int, cpp, ctypes.c_int, i32p, i64p, i64p]
         l.spk_wav_read_padded.argtypes = [ctypes.c_int, cpp, i64p, i64p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int]
         l.spk_text_vectors_bound.argtypes = [ctypes.c_int, ctypes.c_int, cpp]
@@ -68,8 +77,20 @@ def _split_rx(rx):
     return path, int(off)
 
 
+KIND_FM, KIND_CM = 0, 1        # ArkTable.kind: float32 'FM ' / one-byte compressed 'CM ' 
+
+
+def _i32p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _i64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
 class ArkTable:
-    """Parsed scp: per line the ark path, the payload offset and the frame count (headers probed once)."""
+    """Parsed scp: per line the ark path, the payload offset, the frame count and the kind of the record - float32 'FM ' or
+    Kaldi's one-byte compressed 'CM ', mixed freely (headers probed once)."""
 
     def __init__(self, rxfiles):
         paths, offs = zip(*[_split_rx(r) for r in rxfiles])
@@ -80,43 +101,60 @@ class ArkTable:
         self.rows = np.zeros(n, dtype=np.int32)
         self.cols = np.zeros(n, dtype=np.int32)
         self.data_off = np.zeros(n, dtype=np.int64)
+        self.kind = np.zeros(n, dtype=np.int32)
         arr = (ctypes.c_char_p * n)(*[self._cpaths[p].value for p in paths])
         offs = np.asarray(offs, dtype=np.int64)
-        _check(lib().spk_ark_probe(n, arr, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                   self.rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                   self.cols.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                   self.data_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), "spk_ark_probe")
+        _check(lib().spk_ark_probe_kinds(n, arr, _i64p(offs), _i32p(self.rows), _i32p(self.cols), _i64p(self.data_off),
+                                         _i32p(self.kind)), "spk_ark_probe_kinds")
+        self.all_cm = bool(n > 0 and (self.kind == KIND_CM).all())
 
-    def read_crop(self, idx, starts, T, out, nthreads=4):
-        """out: contiguous float32 host tensor [B, F, T] (ideally pinned)."""
+    def _batch(self, idx):
         B = len(idx)
         F = int(self.cols[idx[0]])
-        assert out.is_contiguous() and tuple(out.shape) == (B, F, T) and out.dtype == torch.float32
         assert (self.cols[idx] == F).all()
         arr = (ctypes.c_char_p * B)(*[self._cpaths[self.paths[i]].value for i in idx])
-        doff = np.ascontiguousarray(self.data_off[idx])
-        rows = np.ascontiguousarray(self.rows[idx])
+        return (B, F, arr, np.ascontiguousarray(self.data_off[idx]), np.ascontiguousarray(self.rows[idx]),
+                np.ascontiguousarray(self.kind[idx]))
+
+    def read_crop(self, idx, starts, T, out, nthreads=4):
+        """out: contiguous float32 host tensor [B, F, T] (ideally pinned).  'CM ' entries are decoded on the host, to the bits of
+        kaldi_io.read_mat."""
+        B, F, arr, doff, rows, kind = self._batch(idx)
+        assert out.is_contiguous() and tuple(out.shape) == (B, F, T) and out.dtype == torch.float32
         st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32))
-        _check(lib().spk_ark_read_crop(B, arr, doff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                       rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                       st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), F, T, out.data_ptr(), nthreads),
+        _check(lib().spk_ark_read_crop_kinds(B, arr, _i64p(doff), _i32p(rows), _i32p(st), _i32p(kind), F, T, out.data_ptr(), nthreads),
                "spk_ark_read_crop")
         return out
 
     def read_padded(self, idx, T, out, nthreads=4):
         """Whole utterances idx (each of 1..T frames) into a contiguous float32 host tensor out [B, F, T] (ideally pinned), the
         frames past each utterance's length zero-filled; self.rows[idx] are the lengths to pass to predict(x, lengths=...)."""
-        B = len(idx)
-        F = int(self.cols[idx[0]])
+        B, F, arr, doff, rows, kind = self._batch(idx)
         assert out.is_contiguous() and tuple(out.shape) == (B, F, T) and out.dtype == torch.float32
-        assert (self.cols[idx] == F).all()
-        arr = (ctypes.c_char_p * B)(*[self._cpaths[self.paths[i]].value for i in idx])
-        doff = np.ascontiguousarray(self.data_off[idx])
-        rows = np.ascontiguousarray(self.rows[idx])
-        _check(lib().spk_ark_read_padded(B, arr, doff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), F, T, out.data_ptr(), nthreads),
+        _check(lib().spk_ark_read_padded_kinds(B, arr, _i64p(doff), _i32p(rows), _i32p(kind), F, T, out.data_ptr(), nthreads),
                "spk_ark_read_padded")
         return out
+
+    def read_crop_codes(self, idx, starts, T, codes, colhdr, nthreads=4):
+        """'CM ' entries as stored, for features.decompress (the GPU decode): codes, a contiguous uint8 host tensor [B, F, T]
+        (codes[b, f, t]: frame starts[b] + t, bin f), and colhdr, contiguous float32 [B, F, 4], the decoded column headers.  A
+        quarter of read_crop's bytes and no transpose; an 'FM ' entry is an error."""
+        B, F, arr, doff, rows, kind = self._batch(idx)
+        assert codes.is_contiguous() and tuple(codes.shape) == (B, F, T) and codes.dtype == torch.uint8
+        assert colhdr.is_contiguous() and tuple(colhdr.shape) == (B, F, 4) and colhdr.dtype == torch.float32
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32))
+        _check(lib().spk_ark_read_crop_codes(B, arr, _i64p(doff), _i32p(rows), _i32p(st), F, T, codes.data_ptr(), colhdr.data_ptr(),
+                                             nthreads), "spk_ark_read_crop_codes")
+        return codes, colhdr
+
+    def read_padded_codes(self, idx, T, codes, colhdr, nthreads=4):
+        """read_crop_codes for whole utterances idx (each of 1..T frames): codes zero past each utterance's length"""
+        B, F, arr, doff, rows, kind = self._batch(idx)
+        assert codes.is_contiguous() and tuple(codes.shape) == (B, F, T) and codes.dtype == torch.uint8
+        assert colhdr.is_contiguous() and tuple(colhdr.shape) == (B, F, 4) and colhdr.dtype == torch.float32
+        _check(lib().spk_ark_read_padded_codes(B, arr, _i64p(doff), _i32p(rows), F, T, codes.data_ptr(), colhdr.data_ptr(), nthreads),
+               "spk_ark_read_padded_codes")
+        return codes, colhdr
 
 
 class WavTable:
@@ -192,7 +230,11 @@ class NativeTrainLoader:
         its own copy stream (overlapping the previous step's kernels), records an event per ring slot, and the reader
         thread waits for that event before it refills the slot - the training loop never syncs with the host, so
         without this guard the reader could overwrite a slot whose asynchronous copy has not executed yet.  Yields
-        device tensors, already ordered after the copy on the consumer's current stream."""
+        device tensors, already ordered after the copy on the consumer's current stream.
+        When every entry of the scp is a one-byte compressed 'CM ' matrix the ring holds the codes as they
+        lie in the archive (a quarter of the bytes, no transpose) plus the small column headers; both are copied and decoded to
+        float32 by spk_cm_decode on the copy stream, ahead of the same event.  With device=None, or 'FM ' entries among them, the
+        reader decodes on the host and the batches are float32 as before - the same bits either way."""
         self.device = torch.device(device) if device is not None else None
         utt2spk = {}
         for line in open(utt2spkid_file):
@@ -246,7 +288,13 @@ class NativeTrainLoader:
         q = queue.Queue(maxsize=self.prefetch)
         dev = self.device
         nslot = self.prefetch + 2
-        ring = [torch.empty(self.bs * F * self.T).pin_memory() for _ in range(nslot)] if dev is not None else None
+        as_codes = dev is not None and self.table.all_cm
+        if as_codes:
+            from . import features
+            ring = [torch.empty(self.bs * F * self.T, dtype=torch.uint8).pin_memory() for _ in range(nslot)]
+            hring = [torch.empty(self.bs * F * 4).pin_memory() for _ in range(nslot)]
+        else:
+            ring = [torch.empty(self.bs * F * self.T).pin_memory() for _ in range(nslot)] if dev is not None else None
         copied = [None] * nslot          # per slot: event recorded after the H2D copy that last read the slot
         if self.chunk_range is not None:
             from .datasets import chunk_length_schedule
@@ -273,7 +321,11 @@ class NativeTrainLoader:
                         buf = ring[slot][:len(sel) * F * T].view(len(sel), F, T)
                     else:
                         buf = torch.empty(len(sel), F, T)
-                    self.table.read_crop(rows, starts, T, buf, self.threads)
+                    if as_codes:
+                        buf = (buf, hring[slot][:len(sel) * F * 4].view(len(sel), F, 4))
+                        self.table.read_crop_codes(rows, starts, T, buf[0], buf[1], self.threads)
+                    else:
+                        self.table.read_crop(rows, starts, T, buf, self.threads)
                     q.put((slot, buf, torch.from_numpy(self.labels[sel])))
                     k += 1
                 q.put(None)
@@ -295,7 +347,10 @@ class NativeTrainLoader:
                 continue
             cur = torch.cuda.current_stream(dev)
             with torch.cuda.stream(copy_stream):
-                xg = buf.to(dev, non_blocking=True)
+                if as_codes:         # bytes and headers across, then the decode, all before the event below
+                    xg = features.decompress(buf[0].to(dev, non_blocking=True), buf[1].to(dev, non_blocking=True))
+                else:
+                    xg = buf.to(dev, non_blocking=True)
                 yg = lab.pin_memory().to(dev, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)

@@ -63,10 +63,13 @@ def _read_i32(fd):
 
 def _read_compressed(fd):
     """Kaldi CompressedMatrix ('CM '): global (min, range, rows, cols), per-column 4 x uint16 quantiles,
-    uint8 payload stored column-major; piecewise-linear decode."""
-    vmin, vrange, rows, cols = struct.unpack("<ffii", fd.read(16))
+    uint8 payload stored column-major; piecewise-linear decode.  All in float32, in Kaldi's operation order (DESIGN.md section
+    6g): the native reader and the GPU decode (csrc/cm.hip) return the same bits."""
+    head = fd.read(16)
+    vmin, vrange = np.frombuffer(head, dtype="<f4", count=2)
+    rows, cols = struct.unpack("<ii", head[8:])
     hdr = np.frombuffer(fd.read(cols * 8), dtype="<u2").reshape(cols, 4).astype(np.float32)
-    hdr = vmin + vrange * 1.52590218966964e-05 * hdr
+    hdr = vmin + (vrange * np.float32(1.52590218966964e-05)) * hdr      # the scale rounded to float32 first, as Kaldi does
     data = np.frombuffer(fd.read(cols * rows), dtype=np.uint8).reshape(cols, rows).astype(np.float32)
     p0, p25, p75, p100 = (hdr[:, i:i + 1] for i in range(4))
     out = np.where(data <= 64, p0 + (p25 - p0) * data * (1 / 64.0),
@@ -161,6 +164,32 @@ def write_mat(fd_or_path, m, key=""):
             raise TypeError("write_mat takes float32/float64, got %s" % m.dtype)
         fd.write(b"\x04" + struct.pack("<i", m.shape[0]) + b"\x04" + struct.pack("<i", m.shape[1]))
         fd.write(np.ascontiguousarray(m).tobytes())
+        return off
+    finally:
+        if own:
+            fd.close()
+
+
+def write_cm(fd_or_path, vmin, vrange, hdr, codes, key=""):
+    """Binary 'CM ' (compressed, one byte per value) matrix from its already-compressed parts (features.compress, DESIGN.md section
+    6g): global (vmin, vrange), hdr [cols, 4] uint16 column headers, codes [cols, rows] uint8 - column-major, which for a [T, F]
+    feature matrix is the [F][T] layout of a batch row.  Returns the byte offset of the \\0B flag."""
+    hdr = np.asarray(hdr)
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8 or codes.ndim != 2 or hdr.shape != (codes.shape[0], 4):
+        raise TypeError("write_cm takes uint8 codes [cols, rows] and headers [cols, 4], got %s %s and %s"
+                        % (codes.dtype, codes.shape, hdr.shape))
+    if hdr.min() < 0 or hdr.max() > 65535:
+        raise ValueError("write_cm: column headers outside uint16")
+    fd, own = open_rx(fd_or_path, "wb")
+    try:
+        if key:
+            fd.write((key + " ").encode("latin1"))
+        off = fd.tell()
+        fd.write(b"\0BCM ")
+        fd.write(np.array([vmin, vrange], dtype="<f4").tobytes() + struct.pack("<ii", codes.shape[1], codes.shape[0]))
+        fd.write(np.ascontiguousarray(hdr.astype("<u2")).tobytes())
+        fd.write(np.ascontiguousarray(codes).tobytes())
         return off
     finally:
         if own:

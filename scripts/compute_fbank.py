@@ -3,7 +3,8 @@
 (+ compute-vad), and with --egs what local/nnet3/xvector/prepare_feats_for_egs.sh:68-70 makes (apply-cmvn-sliding
 --norm-vars=false --center=true --cmn-window=W, then select-voiced-frames).
 
-Writes <out-dir>/feats.ark + feats.scp ([T, F] float32 matrices that train_resnet.py / decode.py read), utt2num_frames, and with
+Writes <out-dir>/feats.ark + feats.scp ([T, F] float32 matrices that train_resnet.py / decode.py read; with --compress Kaldi's
+one-byte compressed matrices, which they read as well - DESIGN.md section 6g), utt2num_frames, and with
 --vad-config vad.ark + vad.scp (float vectors of 0/1 per frame; without --egs).  Utterances shorter than one frame and (--egs) without
 voiced frames are reported and skipped.  Dither noise is keyed by (--seed, a stable hash of the utterance key): the features of an
 utterance do not depend on its batch.
@@ -52,6 +53,8 @@ parser.add_argument("--allow-upsample", action="store_true", help="resample file
 parser.add_argument("--speed", help="speed perturbation factor as a decimal, e.g. 0.9 or 1.1: keys become sp<F>-<utt>")
 parser.add_argument("--vad-scp", help="with --egs: vad.scp of 0/1 vectors per written key; the voiced frames come from it, not from compute-vad")
 parser.add_argument("--time-batches", action="store_true", help="also print the seconds the batch loop took (tools/augment_bench.py)")
+parser.add_argument("--compress", action="store_true", help="write feats.ark as Kaldi's one-byte compressed matrices ('CM ', what "
+                    "Kaldi's own feature scripts write by default): a quarter of the bytes, lossy; compressed on the GPU")
 parser.add_argument("--utt2spk", help="with --speed: 'utt spk' lines; writes <out-dir>/utt2spk and <out-dir>/utt2uniq of the copies")
 
 
@@ -138,13 +141,25 @@ def main():
                 v, vidx, cnt = features.vad(loge, T, vad_opts)
                 if args.egs:
                     feats, T = features.select_voiced(feats, T, vidx, cnt, cmn)
-            feats = feats.cpu().numpy()
+            if args.compress:       # after the CMN / voiced-frame selection: what is written is what gets compressed
+                try:
+                    mr, hd, cd = features.compress(feats, T)
+                except ValueError as e:
+                    fin = torch.isfinite(feats).all(dim=1).cpu().numpy()
+                    bad = [keys[i] for r, i in enumerate(idx) if T[r] > 0 and not fin[r, :T[r]].all()]
+                    sys.exit("compute_fbank: --compress: non-finite feature value in %s (%s)" % (", ".join(bad) or "a batch", e))
+                mr, hd, cd = mr.cpu().numpy(), hd.cpu().numpy(), cd.cpu().numpy()
+            else:
+                feats = feats.cpu().numpy()
             v = v.cpu().numpy() if write_vad else None
             for r, i in enumerate(idx):
                 if T[r] == 0:
                     print("compute_fbank: skipping %s: no voiced frames" % keys[i])
                     continue
-                off = kaldi_io.write_mat(fa, np.ascontiguousarray(feats[r, :, :T[r]].T), key=keys[i])
+                if args.compress:
+                    off = kaldi_io.write_cm(fa, mr[r, 0], mr[r, 1], hd[r], cd[r, :, :T[r]], key=keys[i])
+                else:
+                    off = kaldi_io.write_mat(fa, np.ascontiguousarray(feats[r, :, :T[r]].T), key=keys[i])
                 voff = None
                 if write_vad:
                     fv.write((keys[i] + " ").encode())

@@ -162,8 +162,10 @@ def native_generator(model, args):
     """Length-bucketed extraction through libspkio: utterances of equal frame count share a batch (whole utterance when
     --chunk-size -1, else the first chunk-size frames... the reference crops at random; extraction of a fixed window is
     deterministic here), each rank takes every world-th batch.  --pad-batches: length-sorted batches of unequal lengths padded
-    to a common T (ingest.pad_batches) and the length-masked predict instead of equal-length buckets."""
-    from pytorch_kaldi_resnet_amd import ingest
+    to a common T (ingest.pad_batches) and the length-masked predict instead of equal-length buckets.
+    An scp of one-byte compressed 'CM ' matrices only is read as codes + column headers - a quarter of the
+    bytes through the pinned buffer and the copy - and decoded on the GPU (features.decompress) with the batch's lengths."""
+    from pytorch_kaldi_resnet_amd import features, ingest
     from pytorch_kaldi_resnet_amd.ingest import ArkTable
     tab = [l.rstrip().split(None, 1) for l in open(args.decode_scp)]
     utts = [u for u, _ in tab]
@@ -206,8 +208,15 @@ def native_generator(model, args):
         if buf is None:
             for k in [k for k in pinned if k[0] == key[0]]:
                 del pinned[k]                    # one live buffer per parity: its previous batch has been consumed
-            buf = pinned[key] = torch.empty(len(b), F, T).pin_memory()
-        if args.pad_batches:
+            if table.all_cm:
+                buf = pinned[key] = (torch.empty(len(b), F, T, dtype=torch.uint8).pin_memory(), torch.empty(len(b), F, 4).pin_memory())
+            else:
+                buf = pinned[key] = torch.empty(len(b), F, T).pin_memory()
+        if table.all_cm and args.pad_batches:
+            table.read_padded_codes(b, T, buf[0], buf[1], max(1, args.workers))
+        elif table.all_cm:
+            table.read_crop_codes(b, [0] * len(b), T, buf[0], buf[1], max(1, args.workers))
+        elif args.pad_batches:
             table.read_padded(b, T, buf, max(1, args.workers))
         else:
             table.read_crop(b, [0] * len(b), T, buf, max(1, args.workers))
@@ -229,7 +238,11 @@ def native_generator(model, args):
             buf = nxt.result()
             nxt = rd.submit(load, n + 1) if n + 1 < len(mine) else None
             lengths = table.rows[b] if args.pad_batches else None
-            pred = model.predict(buf.cuda(args.gpu, non_blocking=True), lengths=lengths).cpu().numpy()
+            if table.all_cm:
+                x = features.decompress(buf[0].cuda(args.gpu, non_blocking=True), buf[1].cuda(args.gpu, non_blocking=True), lengths)
+            else:
+                x = buf.cuda(args.gpu, non_blocking=True)
+            pred = model.predict(x, lengths=lengths).cpu().numpy()
             if pending is not None:
                 pending.result()
             pending = wr.submit(emit, f, [utts[k] for k in b], pred)
