@@ -162,7 +162,9 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     if (lane == 0) sred[wave] = se;
     __syncthreads();
     se = (sred[0] + sred[1]) + (sred[2] + sred[3]);
-    const float lse = mx + logf(se);
+    const float lg = logf(se);
+    const float lse = mx + lg;
+    const bool shifted = !(fabsf(mx) < 64.f);
     if (tid == 0) {
         loss_row[b] = lse - tgt;
         if (rank) rank[b] = cnt;
@@ -170,7 +172,9 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     if (dlogits) {
         float* d = dlogits + (size_t)b * S;
         for (int j = tid; j < S; j += 256) {
-            float p = expf(row[j] - lse);
+            // x - lse carries the rounding of lse, half an ulp of |lse|, as relative error of p: below 4e-6 while |max| < 64
+            // (lse < 128) and the plain form stays; beyond that (x - max) - log(sum), as log_softmax (5e-4 at logits of 1e4)
+            float p = shifted ? expf((row[j] - mx) - lg) : expf(row[j] - lse);
             if (j == lab) p -= 1.f;
             d[j] = p * gscale;
         }

@@ -858,12 +858,21 @@ def stats_pool_bwd(x, gout, mode, amax_out=None):
     return dx
 
 
+def _ptr_rows(t):
+    """Device pointer of a 2-D tensor whose rows are contiguous but may be pitched (a column slice of a wider tensor): the
+    callee takes stride(0) as its leading dimension."""
+    assert t.is_cuda and t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1], \
+        "libspkhip takes rows of unit stride only"
+    return t.data_ptr()
+
+
 def gemm(A, Bm, M, N, K, sam, sak, sbk, sbn, bias=None, out=None, alpha=1.0, accumulate=False):
-    """out[M][N] = alpha * sum_k A[m*sam+k*sak] * B[k*sbk+n*sbn] (+bias[n]) (+out)."""
+    """out[M][N] = alpha * sum_k A[m*sam+k*sak] * B[k*sbk+n*sbn] (+bias[n]) (+out).  `out` may be a column slice of a wider
+    tensor (ldc = out.stride(0) > N)."""
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
     ws = _workspace_named("gemm", hip.lib().spk_gemm_workspace(M, N, K), A.device)
-    call("spk_gemm_f32", ptr(A), ptr(Bm), ptr(out), ptr(bias), M, N, K, sam, sak, sbk, sbn, out.stride(0), float(alpha),
+    call("spk_gemm_f32", ptr(A), ptr(Bm), _ptr_rows(out), ptr(bias), M, N, K, sam, sak, sbk, sbn, out.stride(0), float(alpha),
          1 if accumulate else 0, ptr(ws), stream(), label="gemm_f32_kernel", flops=2.0 * M * N * K)
     return out
 
@@ -965,9 +974,10 @@ def trial_cosine(en, te, ia, ib):
 
 
 def topk_mean_std(scores, k):
-    """mean / unbiased std of the k largest entries of every row of scores [N][M]."""
+    """mean / unbiased std of the k largest entries of every row of scores [N][M] (a column slice of a wider tensor is fine:
+    ld = scores.stride(0))."""
     N, M = scores.shape
     mean = torch.empty(N, device=scores.device, dtype=torch.float32)
     std = torch.empty_like(mean)
-    call("spk_topk_mean_std", ptr(scores), ptr(mean), ptr(std), N, M, int(k), scores.stride(0), stream())
+    call("spk_topk_mean_std", _ptr_rows(scores), ptr(mean), ptr(std), N, M, int(k), scores.stride(0), stream())
     return mean, std
