@@ -161,7 +161,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const T* __restrict__ 
         }
         const double mean = s / count;
         double var = ss / count - mean * mean;
-        if (var < 0.0) var = 0.0;
+        // (one value per channel has no variance: sumsq - mean^2 would be the float32 rounding of x^2, up to 2^-24 x^2 against eps)
+        if (var < 0.0 || count <= 1.0) var = 0.0;
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         const float g = gamma[ch], b = beta[ch];
         const float sc = g * invstd;

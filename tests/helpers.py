@@ -207,7 +207,8 @@ def sigma_of(slot_t):
     e = (bits >> 23) & 0xFF
     if e in (0, 255):
         return 1.0
-    return 2.0 ** (14 - (e - 127))
+    se = min(max(127 + 14 - (e - 127), 1), 254)          # the result stays a finite normal float32 (amax < 2^-113: 2^127)
+    return 2.0 ** (se - 127)
 
 
 def slot_value(slot_t):
