@@ -328,6 +328,35 @@ int spk_trial_cosine(const float* en /*[n_en][D]*/, const float* te /*[n_te][D]*
  * (scripts/compute_topk_mean_std.py:18-21: scores.topk(300), torch.std_mean) */
 int spk_topk_mean_std(const float* scores, float* mean_out, float* std_out, int N, int M, int k, long long ld, void* stream);
 
+/* ---- evaluation stage (csrc/eval.hip): speaker-mean cohort, S-norm per trial, error-rate sweep --------
+ * Everything here reproduces the reference's Python expressions bit for bit: fp64 (fp32 where numpy uses it), every operation
+ * rounded on its own (no fused multiply-add), a fixed order wherever the order shows in the result. */
+/* which = 0: pairs one block of spk_sort_trials sorts in LDS; 1: positions per block of spk_error_sweep's scan */
+int spk_eval_tile(int which);
+/* out[s][d] = mean over the rows rows[seg_off[s] .. seg_off[s + 1]) of emb, accumulated in that order as
+ * acc = (float)((double)acc + emb[r][d]) and divided as acc / (float)count: numpy's float32 += float64 and /= int of
+ * scripts/compute_speaker_mean.py:15-27.  rows: row indices grouped by speaker, archive order inside a speaker. */
+int spk_segment_mean(const double* emb /*[N][D]*/, const int* rows /*[N]*/, const int* seg_off /*[S+1]*/, float* out /*[S][D]*/,
+                     int N, int S, int D, void* stream);
+/* out[t] = (s - e_mean[ia[t]]) / max(e_std[ia[t]], 1e-8) / 2 + (s - t_mean[ib[t]]) / max(t_std[ib[t]], 1e-8) / 2 in fp64 with
+ * s = (double)score[t]: scripts/adaptive_snorm.py:28-35.  score: float [T] (score_f64 = 0: what spk_trial_cosine wrote) or
+ * double [T] (score_f64 = 1: what a score file holds). */
+int spk_trial_snorm(const void* score, int score_f64, const int* ia, const int* ib, const double* e_mean, const double* e_std,
+                    const double* t_mean, const double* t_std, double* out, int T, void* stream);
+/* order[T]: the permutation that sorts score[T] ascending, equal scores (-0.0 equals +0.0) in index order - Python's stable
+ * sorted(enumerate(scores), key=itemgetter(1)) of scripts/compute_eer.py:40-42 and local/compute_min_dcf.py:59-61.  No NaN
+ * (the caller checks).  1 <= T < 2^31; ws: spk_sort_trials_workspace(T) bytes. */
+size_t spk_sort_trials_workspace(int T);
+int spk_sort_trials(const double* score, unsigned* order, void* ws, int T, void* stream);
+/* ComputeErrorRates + the EER of scripts/compute_eer.py:35-70,101-102 and ComputeMinDcf of local/compute_min_dcf.py:54-106 for
+ * P <= 8 cost triples costs[P][3] = (p_target, c_miss, c_fa) (device memory), over label[T] (0 / 1) taken through order:
+ *   out_d = eer, then (minDCF, threshold = the score at its position) per triple;
+ *   out_i = position of the EER, targets, non-targets, then the position of the minimum per triple (lowest position on ties).
+ * Both classes must be present (the caller checks).  ws: spk_error_sweep_workspace(T, P) bytes. */
+size_t spk_error_sweep_workspace(int T, int P);
+int spk_error_sweep(const double* score, const unsigned char* label, const unsigned* order, const double* costs, int P,
+                    double* out_d /*[1+2P]*/, long long* out_i /*[3+P]*/, void* ws, int T, void* stream);
+
 /* ---- feature front end (csrc/frontend.hip; DESIGN.md "Feature front end") ------------------------------------------------
  * Replaces the Kaldi binaries of stage 1 of the reference's feature_pre.sh:77-104 (compute-fbank-feats with conf/fbank.conf,
  * compute-vad with conf/vad.conf) and local/nnet3/xvector/prepare_feats_for_egs.sh:68-70 (apply-cmvn-sliding --norm-vars=false

@@ -85,6 +85,11 @@ _SIGS = {
     "spk_augment_workspace": [_I, _L, _I, _I, _L, _I, ctypes.POINTER(_L)],
     "spk_cm_decode": [_P, _P, _P, _I, _I, _I, _P, _P],
     "spk_cm_compress": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "spk_eval_tile": [_I],
+    "spk_segment_mean": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "spk_trial_snorm": [_P, _I] + [_P] * 7 + [_I, _P],
+    "spk_sort_trials": [_P, _P, _P, _I, _P],
+    "spk_error_sweep": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
@@ -120,6 +125,10 @@ def lib():
         l.spk_bn_finalize_workspace.argtypes = [_I, _I]
         l.spk_gemm_workspace.restype = ctypes.c_size_t
         l.spk_gemm_workspace.argtypes = [_I, _I, _I]
+        l.spk_sort_trials_workspace.restype = ctypes.c_size_t
+        l.spk_sort_trials_workspace.argtypes = [_I]
+        l.spk_error_sweep_workspace.restype = ctypes.c_size_t
+        l.spk_error_sweep_workspace.argtypes = [_I, _I]
         for name, sig in _SIGS.items():
             fn = getattr(l, name)
             fn.argtypes = sig
@@ -134,7 +143,8 @@ def has_experimental():
 
 
 def exported_symbols():
-    return ["spk_version", "spk_last_error", "spk_conv_wgrad_workspace", "spk_bn_finalize_workspace", "spk_gemm_workspace"] + list(_SIGS)
+    return ["spk_version", "spk_last_error", "spk_conv_wgrad_workspace", "spk_bn_finalize_workspace", "spk_gemm_workspace",
+            "spk_sort_trials_workspace", "spk_error_sweep_workspace"] + list(_SIGS)
 
 
 def ptr(t):

@@ -981,3 +981,64 @@ def topk_mean_std(scores, k):
     std = torch.empty_like(mean)
     call("spk_topk_mean_std", _ptr_rows(scores), ptr(mean), ptr(std), N, M, int(k), scores.stride(0), stream())
     return mean, std
+
+
+# ---- evaluation stage (csrc/eval.hip) -------------------------------------------------------------------------------------
+def sort_tile():
+    """(key, index) pairs one block of spk_sort_trials sorts in LDS"""
+    return hip.lib().spk_eval_tile(0)
+
+
+def sweep_block():
+    """positions per block of the scan inside spk_error_sweep"""
+    return hip.lib().spk_eval_tile(1)
+
+
+def segment_mean(emb, rows, seg_off):
+    """emb [N][D] float64, rows [N] int32 grouped by segment, seg_off [S+1] int32 -> float32 [S][D] (spk_segment_mean)."""
+    N, D = emb.shape
+    S = seg_off.numel() - 1
+    assert emb.dtype == torch.float64 and rows.dtype == torch.int32 and seg_off.dtype == torch.int32 and rows.numel() == N
+    out = torch.empty(S, D, device=emb.device, dtype=torch.float32)
+    call("spk_segment_mean", ptr(emb), ptr(rows), ptr(seg_off), ptr(out), N, S, D, stream())
+    return out
+
+
+def trial_snorm(score, ia, ib, e_mean, e_std, t_mean, t_std):
+    """adaptive S-norm of score [T] (float32 or float64) -> float64 [T]; the statistics are float64 tables indexed by ia / ib."""
+    T = score.numel()
+    assert score.dtype in (torch.float32, torch.float64) and ia.dtype == torch.int32 and ib.dtype == torch.int32
+    assert ia.numel() == T and ib.numel() == T and all(t.dtype == torch.float64 for t in (e_mean, e_std, t_mean, t_std))
+    out = torch.empty(T, device=score.device, dtype=torch.float64)
+    call("spk_trial_snorm", ptr(score), 1 if score.dtype == torch.float64 else 0, ptr(ia), ptr(ib), ptr(e_mean), ptr(e_std),
+         ptr(t_mean), ptr(t_std), ptr(out), T, stream())
+    return out
+
+
+def sort_trials(score):
+    """score [T] float64 without NaN -> int32 [T] (the uint32 permutation; T < 2^31): ascending, ties in index order."""
+    T = score.numel()
+    assert score.dtype == torch.float64 and score.dim() == 1
+    if T < 1 or T >= 1 << 31:
+        raise ValueError("sort_trials: T=%d must lie in [1, 2^31)" % T)
+    if bool(torch.isnan(score).any()):
+        raise ValueError("sort_trials: a score is NaN")
+    order = torch.empty(T, device=score.device, dtype=torch.int32)
+    ws = torch.empty(hip.lib().spk_sort_trials_workspace(T), device=score.device, dtype=torch.uint8)
+    call("spk_sort_trials", ptr(score), ptr(order), ptr(ws), T, stream())
+    return order
+
+
+def error_sweep(score, label, order, costs):
+    """score [T] float64, label [T] uint8, order [T] from sort_trials, costs: P <= 8 triples (p_target, c_miss, c_fa) ->
+    (out_d [1+2P] float64, out_i [3+P] int64) on the device, laid out as include/spkhip.h says."""
+    T, P = score.numel(), len(costs)
+    assert score.dtype == torch.float64 and label.dtype == torch.uint8 and order.dtype == torch.int32
+    assert label.numel() == T and order.numel() == T and P <= 8
+    cd = torch.tensor([[float(v) for v in c] for c in costs], dtype=torch.float64).reshape(P, 3).to(score.device)
+    out_d = torch.empty(1 + 2 * P, device=score.device, dtype=torch.float64)
+    out_i = torch.empty(3 + P, device=score.device, dtype=torch.int64)
+    ws = torch.empty(hip.lib().spk_error_sweep_workspace(T, P), device=score.device, dtype=torch.uint8)
+    call("spk_error_sweep", ptr(score), ptr(label), ptr(order), ptr(cd) if P else None, P, ptr(out_d), ptr(out_i), ptr(ws), T,
+         stream())
+    return out_d, out_i

@@ -24,3 +24,15 @@ python scripts/compute_mean.py $dir/train.iv $dir/mean.vec
 python scripts/cosine_score.py --mean $dir/mean.vec --enroll $dir/test.iv --test $dir/test.iv --trials $datadir/trials \
   --score-file $dir/scores_cosine
 echo "EER: $(python scripts/compute_eer.py $dir/scores_cosine $datadir/trials 2>/dev/null)" | tee $dir/eer_cosine
+# stages 11-13 of the reference: speaker-mean cohort, top-300 cohort statistics, then test.sh for the cosine and the snorm back
+# end.  Everything goes under $dir/backend ($dir/eer_cosine above is not rewritten); the data dir additionally holds utt2spk.
+# SPK_SCORE_BACKEND=hip runs these steps on the GPU.
+impl=${SPK_SCORE_BACKEND:-host}
+mkdir -p $dir/backend
+cp $dir/train.iv $dir/test.iv $dir/mean.vec $dir/backend/
+python scripts/compute_speaker_mean.py --backend $impl $dir/backend/train.iv $datadir/utt2spk $dir/backend/spk_mean.vec \
+  > $dir/log/compute_speaker_mean.log
+python scripts/compute_topk_mean_std.py --backend $impl --mean $dir/backend/mean.vec --cohort-file $dir/backend/spk_mean.vec \
+  --ark-file $dir/backend/test.iv --mean-std-file $dir/backend/topk_mean_std > $dir/log/compute_topk_mean_std.log
+./test.sh $dir/backend $dir/backend cosine 12 $datadir/trials
+./test.sh $dir/backend $dir/backend snorm 12 $datadir/trials

@@ -13,6 +13,7 @@ if __name__ == "__main__":
     ap.add_argument("--test", type=str, help="test topk mean and std file")
     ap.add_argument("--score-in", type=str, help="score in file")
     ap.add_argument("--score-out", type=str, help="score out file")
+    ap.add_argument("--backend", choices=["host", "hip"], default="host", help="hip: the per-trial normalisation runs on the GPU")
     a = ap.parse_args()
-    scoring.adaptive_snorm(scoring.read_mean_std(a.enroll), scoring.read_mean_std(a.test), a.score_in, a.score_out)
+    scoring.adaptive_snorm(scoring.read_mean_std(a.enroll), scoring.read_mean_std(a.test), a.score_in, a.score_out, backend=a.backend)
     print("saved adaptive S-norm scores in {}".format(a.score_out))
