@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(Conv1x1Args a) {
                     val += ad;
                 }
                 __builtin_nontemporal_store(val, a.out + eo[k]);
-                out_mx = fmaxf(out_mx, fabsf(val));
+                out_mx = fmaxf(out_mx, spk_finite_abs(val));
                 if (flags & SPK_EPI_BNBWD) {
                     const float rw = rwv[k];
                     const bool on = has_bnmask ? ((bmw[k] >> r) & 1u) != 0 : (rw * bsc + bsh > 0.f);

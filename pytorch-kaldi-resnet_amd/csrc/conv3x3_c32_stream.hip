@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_stream_kernel(Conv3x3C32Ar
         C32_T(5);
         // epilogue: register e = pixel m = (e & 3) + 8 (e >> 2) + 4 h of the row tile -> tile row 2 wave + (m >> 4), column m & 15; channel r
         const bool ragged = y0 + C32_TH > H || x0 + C32_TW > W;
-        float ts = 0.f, tq = 0.f;
+        float ts = 0.f, tq = 0.f, tile_mx = 0.f;
         float* ob = a.out + (size_t)((b * H + y0 + 2 * wave) * W + x0) * 32 + r;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -223,10 +223,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_stream_kernel(Conv3x3C32Ar
 #ifndef C32_ABL_NOSTORE
             __builtin_nontemporal_store(val, ob + (row * W + lx) * 32);
 #endif
-            out_mx = fmaxf(out_mx, fabsf(val));
+            tile_mx = fmaxf(tile_mx, fabsf(val));
             ts += val;
             tq = __builtin_fmaf(val, val, tq);
         }
+        // non-finite values stay out of the absmax hand-off (spk_finite_abs): only a wave that stored one walks its values again
+        if (__builtin_amdgcn_ballot_w64(!(tile_mx < __builtin_inff())) != 0) {
+            tile_mx = 0.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = e >> 3, lx = (e & 3) + 8 * ((e >> 2) & 1) + 4 * h;
+                if (ragged && (y0 + 2 * wave + row >= H || x0 + lx >= W)) continue;
+                tile_mx = fmaxf(tile_mx, spk_finite_abs(acc[e] * inv_sig * inv_wsig));
+            }
+        }
+        out_mx = fmaxf(out_mx, tile_mx);
         s_sum += (double)ts;
         s_sq += (double)tq;
         C32_T(6);

@@ -414,7 +414,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                             if (owner && core[u]) {
                                 conv_st(img_draw + off[u], side);
                                 if (has_side_dz) conv_st(img_dz + off[u], dz);
-                                side_mx = fmaxf(fmaxf(side_mx, fmaxf(fabsf(w[0]), fabsf(w[1]))), fmaxf(fabsf(w[2]), fabsf(w[3])));
+                                side_mx = fmaxf(side_mx, spk_finite_amax4(w));
                             }
                         }
                     }
@@ -906,7 +906,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                         sd_w = w;
                         sd_dz = dz;
                         sd_off = pof[u % PIPE_D];
-                        const float mx = fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fabsf(w[2]), fabsf(w[3])));
+                        const float mx = spk_finite_amax4(w);
                         side_mx = sd_go ? fmaxf(side_mx, mx) : side_mx;
                     } else if constexpr (PRE) {
                         // f16 pair tensor: select zero bits outside the image, write the two terms as they are
@@ -1186,7 +1186,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                     }
                     if (wz_row) v = (f32x4){0.f, 0.f, 0.f, 0.f};
                     conv_st(dst, v);
-                    out_mx = fmaxf(fmaxf(out_mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                    out_mx = fmaxf(out_mx, spk_finite_amax4(v));
                     if (flags & SPK_EPI_BNBWD) {
                         // v is the gradient wrt a BatchNorm(+ReLU) output: accumulate (sum dz, sum dz*xhat) of that BN so
                         // its backward needs no separate reduction pass over this tensor
@@ -1252,7 +1252,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                             v[3] = fmaxf(v[3], 0.f);
                         }
                         conv_st(a.out + ob + qc * 4, v);
-                        out_mx = fmaxf(fmaxf(out_mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                        out_mx = fmaxf(out_mx, spk_finite_amax4(v));
                         ssum += v;
                         for (int c_ = 0; c_ < 4; ++c_) ssq[c_] = __builtin_fmaf(v[c_], v[c_], ssq[c_]);      // (explicit: the same rounding in every instantiation)
                     }
@@ -1310,7 +1310,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                             v[3] = fmaxf(v[3], 0.f);
                         }
                         conv_st(dst, v);
-                        out_mx = fmaxf(fmaxf(out_mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                        out_mx = fmaxf(out_mx, spk_finite_amax4(v));
                         if (f_bnb) {
                             // v is the gradient wrt a BatchNorm(+ReLU) output: accumulate (sum dz, sum dz*xhat) of that BN so
                             // its backward needs no separate reduction pass over this tensor

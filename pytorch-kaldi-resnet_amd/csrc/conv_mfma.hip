@@ -129,6 +129,11 @@ static int conv_mfma_entry(const float* in, const float* wpk, float* out, const 
     a.min_dy = mindy; a.min_dx = mindx;
     a.halo_h = (TH - 1) * IS + (maxdy - mindy) + 1;
     a.halo_w = (TW - 1) * IS + (maxdx - mindx) + 1;
+    // A halo one pixel wide and several high (a 1x1 convolution on a map or tile of width 1) has no 32-bit reciprocal:
+    // ceil(2^32 / 1) wraps to 0, every staged pixel landed in row 0 and all rows but the first were staged as padding.  Such a
+    // tile stages a second column that no tap reads - zeros beyond a map of width 1, the neighbouring tile's pixels on a wider
+    // map (outside the tile's own pixels: the side outputs of IN_BNBWD skip it); the offsets below follow the wider pitch.
+    if (a.halo_w == 1 && a.halo_h > 1) a.halo_w = 2;
     a.kc = kc;
     {   // expand (spatial tap) x (channel plane): plane-major, so one plane's taps are consecutive
         int sp_off[9], sp_w[9];

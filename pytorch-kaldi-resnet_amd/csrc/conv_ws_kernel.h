@@ -177,7 +177,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs a) {
                                 if (owner && core[u]) {
                                     *(f32x4*)(img_draw + off[u]) = w;
                                     if (a.side_dz) *(f32x4*)(img_dz + off[u]) = dz;
-                                    side_mx = fmaxf(fmaxf(side_mx, fmaxf(fabsf(w[0]), fabsf(w[1]))), fmaxf(fabsf(w[2]), fabsf(w[3])));
+                                    side_mx = fmaxf(side_mx, spk_finite_amax4(w));
                                 }
                             }
                         }
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ConvArgs a) {
                         vv[3] = fmaxf(vv[3], 0.f);
                     }
                     *(f32x4*)dst = vv;
-                    out_mx = fmaxf(fmaxf(out_mx, fmaxf(fabsf(vv[0]), fabsf(vv[1]))), fmaxf(fabsf(vv[2]), fabsf(vv[3])));
+                    out_mx = fmaxf(out_mx, spk_finite_amax4(vv));
                     if (flags & SPK_EPI_BNBWD) {
                         const f32x4 rw = rwv[kk];
                         f32x4 dz;

@@ -137,6 +137,16 @@ static __device__ __forceinline__ float spk_finite_abs(float v) {
     const float a = fabsf(v);
     return a < __builtin_inff() ? a : 0.f;      // false for inf and NaN
 }
+// the same for the four values a lane stores at once, at one compare per call while nothing non-finite is stored - every wave of
+// a healthy step: the plain maximum first, and only a wave in which some lane met an inf (or four NaNs) takes the per-value form.
+// (The vote makes the branch wave-uniform, so it stays a scalar branch instead of eight more selects per call: the epilogues of
+// the convolutions pass every output element of the step through here.)
+static __device__ __forceinline__ float spk_finite_amax4(f32x4 v) {
+    float q = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    if (__builtin_amdgcn_ballot_w64(!(q < __builtin_inff())) != 0)
+        q = fmaxf(fmaxf(spk_finite_abs(v[0]), spk_finite_abs(v[1])), fmaxf(spk_finite_abs(v[2]), spk_finite_abs(v[3])));
+    return q;
+}
 // wave-wide max of a non-negative float, then one atomicMax on its bit pattern (order-independent: deterministic)
 static __device__ __forceinline__ void spk_wave_amax_commit(float v, unsigned* dst) {
 #pragma unroll

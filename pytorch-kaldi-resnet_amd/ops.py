@@ -166,6 +166,7 @@ GROUPED_3X3 = os.environ.get("SPK_WGRAD_3X3_GROUPS", "1") == "1"   # 3x3 weight 
 GROUPED_1X1_BLOCKS = int(os.environ.get("SPK_WGRAD_1X1_BLOCKS", "512"))
 PIPE_MIN_CIN = int(os.environ.get("SPK_PIPE_MIN_CIN", "64"))    # 32 channels = two chunks: nothing to pipeline, and the second tile costs occupancy
 PIPE_MAX_LDS = int(os.environ.get("SPK_PIPE_MAX_LDS", str(80 * 1024)))      # two halo tiles; <= 80 KiB keeps two blocks per CU
+PIPE_TILES = ((2, 1), (3, 1), (1, 2), (2, 2), (3, 2), (1, 4))      # (MT, NT) register tiles of conv_pipe_kernel (csrc/conv_pipe.hip)
 # the same idea for the 3x3 weight gradients (f16x3 mode): eight-wave blocks, one per CU (conv_wgrad_ws_kernel).  Opt-in:
 # bit-identical, but 10-15 % SLOWER than conv_wgrad_split_kernel on every layer (tools/wg_abl3.sh, profiles/r02_wgrad_ablation.log:
 # producers alone 0.31 ms, consumers alone 0.28 ms, together 0.49 ms - the staging is VALU-bound and a SIMD does not run one
@@ -371,8 +372,9 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
     halo9 = ((TH - 1) * IS + key[3]) * ((TW - 1) * IS + key[4])
     # (fused BatchNorm backward: the ReLU mask as sign bits, or recomputed from the raw tensor - not read from an activation)
     bnbwd_ok = in_bnbwd is None or pipe_fused
+    # ... on a register tile csrc/conv_pipe.hip instantiates; any other tile stays on conv_mfma_kernel (same LDS tile, same sums)
     pipe = (PIPE_CONV and ws is None and split == 3 and len(taps) == 9 and kc == 1 and bnbwd_ok and halo9 <= 576
-            and (2 * halo9 + 1) * 80 <= PIPE_MAX_LDS and Cin >= PIPE_MIN_CIN)
+            and (2 * halo9 + 1) * 80 <= PIPE_MAX_LDS and Cin >= PIPE_MIN_CIN and (MT, NT) in PIPE_TILES)
     if pipe:
         flags |= CONV_PIPE
     # its 16x16x32 form (conv_kernel.h, M16): the (3, 2) register tile, at most eight staging items per plane
