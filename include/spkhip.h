@@ -78,6 +78,9 @@ int spk_build_flags(void);
 #define SPK_IN_PRESPLIT (1 << 14)    /* spk_conv_mfma: `in` is an f16 pair tensor scaled by the sigma of *in_amax (plain input only) */
 #define SPK_SIDE_PRESPLIT (1 << 15)  /* spk_conv_mfma + SPK_IN_BNBWD: side_draw leaves as an f16 pair tensor (scale: *in_amax) */
 #define SPK_DY_PRESPLIT (1 << 16)    /* spk_conv_wgrad: `dy` is an f16 pair tensor scaled by the sigma of *dy_amax */
+#define SPK_CONV_CK32 (1 << 23)      /* spk_conv_mfma + SPK_IN_BNBWD, split = 3, Cin = 32, MT = 1 or 2, NT = 1 (not CONV_PIPE / CONV_WS): the
+                                        staging takes whole 128-byte pixels (one 32-channel plane of 144 B per LDS pixel instead of two
+                                        16-channel planes of 80 B staged one after the other).  Bit-identical results at an equal tile */
 #define SPK_EPI_WMASK (1 << 24)      /* spk_conv_mfma_len / spk_stem_conv_fwd_len only: an output pixel of image b at width (time)
                                         x >= wlen[b] is stored as 0 after the whole epilogue and does not enter out_amax / the
                                         statistics (length-masked eval forward of a padded batch).  Every other entry refuses it */

@@ -22,6 +22,9 @@ static __device__ __forceinline__ f32x4 conv_ld(const float* p) {
 #ifndef STAGE_U2
 #define STAGE_U2 2  // pixels in flight per thread in the fused BatchNorm-backward staging (three loads each)
 #endif
+#ifndef STAGE_U2_C32
+#define STAGE_U2_C32 4  // the same with 32-channel planes (CKP = 32): LDS, not registers, bounds that form's occupancy (three blocks per
+#endif                  // CU at 16 x 16 pixels), so the registers of the fourth wave per SIMD buy more loads in flight per wave
 
 // SPLIT == 0: operands stay fp32 (v_mfma_f32_32x32x2_f32).  SPLIT == 6 / 9: every fp32 operand is split into three bf16
 // terms (x = x1 + x2 + x3 exactly: 3 x 8 significand bits) while it is staged (activations) or packed (weights), and the
@@ -30,14 +33,21 @@ static __device__ __forceinline__ f32x4 conv_ld(const float* p) {
 // (tools/probe/split_probe.hip), at 16/6 of its rate.
 #define SPK_SPLIT_CK 16   // channels per staged plane of the bf16-split kernels (32 = full 128-byte lines per pass was
                           // measured 5 % slower: 208-byte LDS pixels force smaller tiles)
+// CKP (f16x3 only): the plane width as a template argument.  CKP == 32 at Cin == 32 is the whole-pixel form of the fused
+// BatchNorm-backward data gradient: a staging pass takes all 128 bytes of a pixel (eight lanes per pixel, a wave instruction
+// reads eight whole lines of each staged tensor), the tile is staged once - one chunk, no second staging phase - and the LDS
+// pixel is [2 terms][32 ch fp16] + 16 pad = 144 B.  The K loop still consumes one 16-channel group per step: the step table
+// has 2 x 9 entries, group-major (tap_off carries the group's LDS offset, tap_g its weight group), so the accumulators see the
+// same sequence of products as with two 16-channel planes and every output is bit-identical at an equal tile.
 // SPLIT == 3: fp16 two-term operands (spk_common.h, "f16x3"): same structure with two terms per value, three products on
 // v_mfma_f32_32x32x16_f16, a power-of-two input scale (static for activations, from the tensor's absmax for gradients)
 // and the accumulators scaled back in the epilogue.
-template <int SPLIT>
+template <int SPLIT, int CKP = SPK_SPLIT_CK>
 struct ConvCfg {
+    static_assert(CKP == SPK_SPLIT_CK || (SPLIT == 3 && CKP == 32), "plane width: 16, or 32 in the f16x3 mode");
     static constexpr int NTERM = SPLIT == 3 ? 2 : 3;       // operand terms (split kernels)
     static constexpr int MAXSUM = SPLIT == 9 ? 4 : (SPLIT == 6 ? 2 : 1);   // products (sa, sb) with sa + sb <= MAXSUM
-    static constexpr int CK = SPLIT ? SPK_SPLIT_CK : 32;   // channels per staged plane
+    static constexpr int CK = SPLIT ? CKP : 32;   // channels per staged plane
     static constexpr int TPP = CK / 4;           // threads per staged pixel (one float4 of channels each)
     static constexpr int PPP = 256 / TPP;        // pixels per staging pass of the block
     static constexpr int KG = CK / 16;           // split: 16-channel MFMA groups per plane
@@ -78,9 +88,10 @@ struct ConvArgs {
     int halo_h, halo_w, min_dy, min_dx;
     unsigned halo_w_magic;   // ceil(2^32 / halo_w): p / halo_w == umulhi(p, magic) for p * halo_w < 2^32
     int ntaps, ncg, nblocks, flags;
-    int tap_off[9];   // LDS offset (16-byte units) of the (tap, channel plane) inside the staged tile
-    int tap_w[9];     // weight tap index
-    int tap_g[9];     // weight K-group offset of the channel plane (fp32: 4 groups of 8 channels per plane; split: 1 of 16)
+    int tap_off[18];  // LDS offset (16-byte units) of the (tap, channel plane) inside the staged tile; 32-channel planes of the
+                      //   f16x3 mode: of the (tap, 16-channel group) - group-major, 2 x 9 entries
+    int tap_w[18];    // weight tap index
+    int tap_g[18];    // weight K-group offset of the channel plane (fp32: 4 groups of 8 channels per plane; split: 1 of 16)
     // f16x3 operand mode (SPLIT == 3)
     const unsigned* in_amax;   // float bits of the staged tensor's absmax (or an upper estimate); NULL: static in_sigma
     float in_sigma;            // static input scale when in_amax is NULL
@@ -140,9 +151,10 @@ static __device__ unsigned long long g_conv_stamps[CONV_STAMP_BLOCKS][16];      
 #define SPK_FL_ADDMASK (1 << 20)
 #define SPK_FL_BNMASK (1 << 21)
 #define SPK_FL_INMASK (1 << 22)      // fused input BatchNorm backward: its ReLU mask as sign bits (else recomputed from the raw tensor); no side_dz
-template <int MT, int NT, bool BNBWD, int SPLIT, bool PIPE, bool BITS = false, bool PRE = false, bool M16 = false, int FL = -1>
+template <int MT, int NT, bool BNBWD, int SPLIT, bool PIPE, bool BITS = false, bool PRE = false, bool M16 = false, int FL = -1, int CKP = SPK_SPLIT_CK>
 static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
-    using Cfg = ConvCfg<SPLIT>;
+    using Cfg = ConvCfg<SPLIT, CKP>;
+    static_assert(CKP == SPK_SPLIT_CK || (BNBWD && !PIPE), "32-channel planes: the fused BatchNorm-backward form of conv_mfma_kernel");
     constexpr int CK = Cfg::CK, TPP = Cfg::TPP, PPP = Cfg::PPP, LP4 = Cfg::LP4, NTERM = Cfg::NTERM;
     static_assert(!M16 || (PIPE && !BNBWD && SPLIT == 3), "M16: the pipelined f16x3 kernel with a plain or pair input");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -364,7 +376,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
                 const f32x4 k1 = *(const f32x4*)(a.in_coef + c), m1 = *(const f32x4*)(a.in_coef + a.Cin + c);
                 const f32x4 m2 = *(const f32x4*)(a.in_coef + 2 * a.Cin + c);
                 const bool owner = (cg == 0);
-                constexpr int U2 = STAGE_U2;
+                constexpr int U2 = (CK == 32 && FL >= 0) ? STAGE_U2_C32 : STAGE_U2;      // (the generic FL < 0 instance keeps its registers)
                 for (int base = prow; base < halo_pix; base += PPP * U2) {
                     f32x4 v[U2], rw[U2], ac[U2];
                     unsigned mw[U2];
@@ -778,7 +790,7 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
             // per n-tile, SPLIT MFMAs per (m-tile, n-tile).
             const f32x4* lds4 = (const f32x4*)lds;
             // packed weights: [tap][Cin/16][term][Cout/32][64 lanes][8 bf16]
-            const float* wbase = a.wpk + ((size_t)(ch * a.kc) * NTERM * cout32 + cg * NT) * 256 + lane * 4;
+            const float* wbase = a.wpk + ((size_t)(ch * a.kc * Cfg::KG) * NTERM * cout32 + cg * NT) * 256 + lane * 4;     // (groups of 16, not planes)
             const size_t tap_stride = (size_t)(a.Cin >> 4) * NTERM * cout32 * 256;
             const size_t grp_stride = (size_t)NTERM * cout32 * 256;
             const size_t term_stride = (size_t)cout32 * 256;
@@ -1362,9 +1374,9 @@ static __device__ __forceinline__ void conv_body(const ConvArgs& a) {
     }
 }
 
-template <int MT, int NT, bool BNBWD, int SPLIT, int FL = -1>
+template <int MT, int NT, bool BNBWD, int SPLIT, int FL = -1, int CKP = SPK_SPLIT_CK>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
-    conv_body<MT, NT, BNBWD, SPLIT, false, false, false, false, FL>(a);
+    conv_body<MT, NT, BNBWD, SPLIT, false, false, false, false, FL, CKP>(a);
 }
 
 // the in-wave pipelined form (f16x3 operands; conv_pipe.hip)

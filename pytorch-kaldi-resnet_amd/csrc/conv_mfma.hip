@@ -21,7 +21,7 @@
 #include "conv_kernel.h"
 
 // bf16-split instantiations live in their own translation unit (conv_split.hip)
-int spk_launch_conv_split(const ConvArgs& a, size_t lds_bytes, int MT, int NT, int split, hipStream_t st);
+int spk_launch_conv_split(const ConvArgs& a, size_t lds_bytes, int MT, int NT, int split, int ck, hipStream_t st);
 // in-wave pipelined form (conv_pipe.hip)
 int spk_launch_conv_pipe(const ConvArgs& a, size_t lds_bytes, int MT, int NT, hipStream_t st);
 // wave-specialised persistent form (conv_ws.hip)
@@ -69,10 +69,17 @@ static int conv_mfma_entry(const float* in, const float* wpk, float* out, const 
     SPK_REQUIRE(ntaps >= 1 && ntaps <= 9, "spk_conv_mfma: ntaps=%d out of range", ntaps);
     SPK_REQUIRE(split == 0 || split == 3 || split == 6 || split == 9,
                 "spk_conv_mfma: split=%d (0 = fp32 operands, 6 / 9 = bf16 cross terms, 3 = fp16 two-term operands)", split);
-    const int ck = split ? SPK_SPLIT_CK : 32;                     // channels per staged plane
+    // whole-pixel staging (conv_kernel.h, CKP): the fused BatchNorm-backward data gradient at Cin = 32 in the f16x3 mode
+    const bool ck32 = (flags & SPK_CONV_CK32) != 0;
+    SPK_REQUIRE(!ck32 || (split == 3 && Cin == 32 && (flags & SPK_IN_BNBWD) && kc == 1 && !(flags & (SPK_CONV_WS | SPK_CONV_PIPE))),
+                "spk_conv_mfma: CONV_CK32 (32-channel planes) exists for the fused BatchNorm-backward form of conv_mfma_kernel at Cin = 32 in the "
+                "f16x3 mode");
+    flags &= ~SPK_CONV_CK32;
+    const int ck = split ? (ck32 ? 32 : SPK_SPLIT_CK) : 32;       // channels per staged plane
     const int nterm = split == 3 ? 2 : 3;
-    const int lp4 = split ? (nterm * SPK_SPLIT_CK * 2 + 16) / 16 : 9;    // LDS pixel pitch in 16-byte units (ConvCfg<SPLIT>::LP4)
-    SPK_REQUIRE(kc >= 1 && ntaps * kc <= 9 && Cin % (ck * kc) == 0, "spk_conv_mfma: kc=%d incompatible with ntaps=%d, Cin=%d", kc, ntaps, Cin);
+    const int lp4 = split ? (nterm * ck * 2 + 16) / 16 : 9;       // LDS pixel pitch in 16-byte units (ConvCfg<SPLIT, CKP>::LP4)
+    const int kgrp = split ? ck / 16 : 1;                         // split: K steps per (tap, plane) = 16-channel groups of the plane
+    SPK_REQUIRE(kc >= 1 && ntaps * kc * kgrp <= (ck32 ? 18 : 9) && Cin % (ck * kc) == 0, "spk_conv_mfma: kc=%d incompatible with ntaps=%d, Cin=%d", kc, ntaps, Cin);
     SPK_REQUIRE(TH >= 1 && TW >= 1 && TH * TW <= 128 * MT / ws_wc, "spk_conv_mfma: tile %dx%d exceeds %d pixels (MT=%d)", TH, TW, 128 * MT / ws_wc, MT);
     SPK_REQUIRE(IS >= 1 && OS >= 1 && ooy >= 0 && oox >= 0, "spk_conv_mfma: bad strides/offsets");
     SPK_REQUIRE((OH - 1) * OS + ooy < OHf && (OW - 1) * OS + oox < OWf, "spk_conv_mfma: logical grid exceeds the output tensor");
@@ -148,9 +155,17 @@ static int conv_mfma_entry(const float* in, const float* wpk, float* out, const 
             a.tap_w[tt] = sp_w[t];
             a.tap_g[tt] = pl * (split ? SPK_SPLIT_CK / 16 : 4);
         }
+        // 32-channel planes (kc == 1): one step per (16-channel group, tap), group-major - the second group sits 32 bytes (two
+        // 16-byte units) into a term of the LDS pixel and one group further in the packed weights
+        for (int tt = 0; ck32 && tt < ntaps * kgrp; ++tt) {
+            const int t = tt % ntaps, g = tt / ntaps;
+            a.tap_off[tt] = sp_off[t] + g * 2;
+            a.tap_w[tt] = sp_w[t];
+            a.tap_g[tt] = g;
+        }
     }
     a.halo_w_magic = (unsigned)((0x100000000ULL + (unsigned long long)a.halo_w - 1) / (unsigned long long)a.halo_w);
-    a.ntaps = ntaps * kc; a.ncg = Cout / (32 * NT * ws_wc);
+    a.ntaps = ntaps * kc * (ck32 ? kgrp : 1); a.ncg = Cout / (32 * NT * ws_wc);
     a.nblocks = B * a.tiles_y * a.tiles_x * a.ncg;
     a.flags = flags;
     size_t lds_bytes = (size_t)kc * a.halo_h * a.halo_w * lp4 * 16;
@@ -187,7 +202,7 @@ static int conv_mfma_entry(const float* in, const float* wpk, float* out, const 
         a.flags = flags & ~SPK_CONV_PIPE;
         return spk_launch_conv_pipe(a, lds2, MT, NT, st);
     }
-    if (split) return spk_launch_conv_split(a, lds_bytes, MT, NT, split, st);
+    if (split) return spk_launch_conv_split(a, lds_bytes, MT, NT, split, ck, st);
 #define CASE(M, N) if (MT == M && NT == N) return launch_conv<M, N>(a, lds_bytes, st)
     CASE(1, 1); CASE(2, 1); CASE(3, 1); CASE(4, 1);
     CASE(1, 2); CASE(2, 2); CASE(3, 2); CASE(4, 2);

@@ -4,6 +4,26 @@
 // is the fp16 two-term form (three products on v_mfma_f32_32x32x16_f16, power-of-two operand scales).
 #include "conv_kernel.h"
 
+// whole-pixel form of the fused BatchNorm-backward data gradient at Cin = 32 (conv_kernel.h, CKP = 32): the register tiles of
+// its two candidate tiles - (2, 1) for 16 x 16 pixels, (1, 1) for 128-pixel tiles - with the same compile-time flag variants as
+// the 16-channel form below, and the generic FL = -1
+template <int MT, int NT>
+static int launch_split_ck32(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
+#ifndef SPK_NO_FL_VARIANTS
+    const int var = a.flags | (a.add_mask ? SPK_FL_ADDMASK : 0) | (a.bn_mask ? SPK_FL_BNMASK : 0) | (a.in_mask ? SPK_FL_INMASK : 0);
+    constexpr int V2 = SPK_IN_BNBWD | SPK_SIDE_PRESPLIT | SPK_EPI_STATS | SPK_EPI_BNBWD | SPK_FL_INMASK;
+    constexpr int V1 = SPK_IN_BNBWD | SPK_SIDE_PRESPLIT | SPK_EPI_ADD | SPK_EPI_STATS | SPK_EPI_BNBWD | SPK_FL_ADDMASK | SPK_FL_BNMASK;
+    if (!a.in_act && !a.bn_act && !a.side_dz && var == V2)
+        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, true, 3, V2, 32>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    else if (!a.in_act && !a.bn_act && !a.side_dz && var == V1)
+        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, true, 3, V1, 32>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    else
+#endif
+        hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, true, 3, -1, 32>), dim3(a.nblocks), dim3(256), lds_bytes, st, a);
+    SPK_LAUNCH_CHECK("spk_conv_mfma(split, 32-channel planes)");
+    return 0;
+}
+
 template <int MT, int NT, int SPLIT>
 static int launch_split(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
     if (a.flags & SPK_IN_BNBWD) {
@@ -50,7 +70,13 @@ static int launch_split(const ConvArgs& a, size_t lds_bytes, hipStream_t st) {
     return 0;
 }
 
-int spk_launch_conv_split(const ConvArgs& a, size_t lds_bytes, int MT, int NT, int split, hipStream_t st) {
+int spk_launch_conv_split(const ConvArgs& a, size_t lds_bytes, int MT, int NT, int split, int ck, hipStream_t st) {
+    if (ck == 32) {      // (the entry has checked: f16x3, Cin = 32, fused BatchNorm backward)
+        if (MT == 2 && NT == 1) return launch_split_ck32<2, 1>(a, lds_bytes, st);
+        if (MT == 1 && NT == 1) return launch_split_ck32<1, 1>(a, lds_bytes, st);
+        spk_set_error("spk_conv_mfma: 32-channel planes are instantiated for MT=2 / MT=1 with NT=1, not MT=%d NT=%d", MT, NT);
+        return -1;
+    }
 #define CASE(M, N)                                                      \
     if (MT == M && NT == N) {                                           \
         if (split == 3) return launch_split<M, N, 3>(a, lds_bytes, st); \

@@ -45,6 +45,7 @@ enum {
     SPK_CONV_M16 = 1 << 17,       // with SPK_CONV_PIPE: the v_mfma_f32_16x16x32_f16 form of the pipelined kernel (taps paired per K step)
     SPK_WGRAD_NOSHIFT = 1 << 18,  // spk_conv_wgrad, 3x3 grouped kernel: keep the plain K loop where the shifted-window form applies (A/B)
     SPK_WGRAD_M16 = 1 << 19,      // spk_conv_wgrad, 3x3 grouped kernel with a pair-tensor dy: the v_mfma_f32_16x16x32_f16 form, dy by LDS DMA
+    SPK_CONV_CK32 = 1 << 23,      // spk_conv_mfma + IN_BNBWD, f16x3, Cin = 32: stage whole 128-byte pixels (32-channel planes, conv_kernel.h CKP)
     // (bits 20-22 are the compile-time variant bits of conv_kernel.h / conv1x1_stream.hip: SPK_FL_*, V_*)
     SPK_EPI_WMASK = 1 << 24       // spk_conv_mfma_len / spk_stem_conv_fwd_len: output pixels at width x >= wlen[b] are stored as 0
                                   //   and stay out of out_amax (length-masked eval forward of padded utterances)

@@ -13,6 +13,7 @@ CONV_PIPE = 1024
 WGRAD_GROUPS = 2048        # spk_conv_wgrad flags: 1x1 f16x3 kernel with 1 << (bits 12-13) input-channel groups per block
 IN_PRESPLIT, SIDE_PRESPLIT, DY_PRESPLIT = 1 << 14, 1 << 15, 1 << 16     # f16 pair tensors (include/spkhip.h)
 CONV_M16 = 1 << 17      # 16x16x32 form of the pipelined convolution
+CONV_CK32 = 1 << 23     # fused BatchNorm-backward data gradient at Cin = 32 (f16x3): whole 128-byte pixels per staging pass
 WGRAD_NOSHIFT = 1 << 18  # 3x3 grouped weight gradient: plain K loop instead of the shifted-window form (A/B)
 WGRAD_M16 = 1 << 19      # 3x3 grouped weight gradient on 16x16x32 with dy (a pair tensor) staged by LDS DMA
 EPI_WMASK = 1 << 24     # length-masked epilogue: outputs at width x >= wlen[b] stored as 0 (spk_conv_mfma_len, spk_stem_conv_fwd_len)

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import hip, tiling
-from .hip import (CONV_M16, CONV_PIPE, CONV_WS, DY_PRESPLIT, IN_PRESPLIT, SIDE_PRESPLIT, WGRAD_GROUPS, EPI_ADD, EPI_AFFINE, EPI_BNBWD, EPI_RELU,
+from .hip import (CONV_CK32, CONV_M16, CONV_PIPE, CONV_WS, DY_PRESPLIT, IN_PRESPLIT, SIDE_PRESPLIT, WGRAD_GROUPS, EPI_ADD, EPI_AFFINE, EPI_BNBWD, EPI_RELU,
                   EPI_STATS, EPI_WMASK, IN_AFFINE_RELU, IN_BNBWD, MASK_ACT, MASK_NONE, MASK_RAW,
                   call, ptr, stream)
 
@@ -164,6 +164,12 @@ C32M16 = os.environ.get("SPK_C32M16", "1") == "1"         # ... and its 32-chann
 WM_SHIFT = os.environ.get("SPK_WM_SHIFT", "1") == "1"      # 3x3 grouped weight gradient: shifted-window K loop where it applies (csrc/conv_wgrad_wm.hip, SH)
 GROUPED_3X3 = os.environ.get("SPK_WGRAD_3X3_GROUPS", "1") == "1"   # 3x3 weight gradients: 2 x 2 (cin group x cout group) wave layout
 GROUPED_1X1_BLOCKS = int(os.environ.get("SPK_WGRAD_1X1_BLOCKS", "512"))
+# fused BatchNorm-backward data gradient at Cin = 32 (f16x3, conv_mfma_kernel): channels per staged plane.  32 = whole 128-byte
+# pixels per staging pass, one chunk (csrc/conv_kernel.h, CKP); 16 = two 16-channel planes staged one after the other.  Same
+# sums in the same order: bit-identical results at an equal tile (tests/test_c32_whole_pixel_gpu.py).
+C32_PLANE = int(os.environ.get("SPK_C32_PLANE", "32"))
+assert C32_PLANE in (16, 32), "SPK_C32_PLANE: 16 or 32"
+C32_PLANE_TILES = ((2, 1), (1, 1))        # register tiles csrc/conv_split.hip instantiates with 32-channel planes
 PIPE_MIN_CIN = int(os.environ.get("SPK_PIPE_MIN_CIN", "64"))    # 32 channels = two chunks: nothing to pipeline, and the second tile costs occupancy
 PIPE_MAX_LDS = int(os.environ.get("SPK_PIPE_MAX_LDS", str(80 * 1024)))      # two halo tiles; <= 80 KiB keeps two blocks per CU
 PIPE_TILES = ((2, 1), (3, 1), (1, 2), (2, 2), (3, 2), (1, 4))      # (MT, NT) register tiles of conv_pipe_kernel (csrc/conv_pipe.hip)
@@ -343,7 +349,9 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
     if tiling.AUTOTUNE and key not in (tiling.FORCE_CONV_SPLIT if split else tiling.FORCE_CONV) and PROFILE is None and not torch.cuda.is_current_stream_capturing():
         _autotune_conv(key, x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, epi_affine, epi_add, relu, split,
                        in_amax=in_amax, in_presplit=in_presplit)
-    TH, TW, MT, NT = tiling.conv_tile(*key, mode=1 if in_bnbwd is not None else 0, split=split)
+    # (mode 2: the fused data gradient that may stage whole pixels - its own table key, 144 B per halo pixel)
+    c32 = C32_PLANE == 32 and split == 3 and Cin == 32 and in_bnbwd is not None and len(taps) == 9
+    TH, TW, MT, NT = tiling.conv_tile(*key, mode=(2 if c32 else 1) if in_bnbwd is not None else 0, split=split)
     # Producer / consumer (wave-specialised, persistent) kernel for the bf16-split 3x3 launches (csrc/conv_ws_kernel.h) with
     # its own wave layouts and tiles; everything else stays on conv_mfma_kernel.
     ws, WC = None, 1
@@ -381,6 +389,10 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
     m16 = pipe and PIPE_M16 and in_bnbwd is None and (MT, NT) == (3, 2) and halo9 <= 512 and IS == 1
     if m16:
         flags |= CONV_M16
+    # whole-pixel staging of the 32-channel fused data gradient: on the register tiles compiled for it, on conv_mfma_kernel
+    c32 = c32 and ws is None and not pipe and kc == 1 and (MT, NT) in C32_PLANE_TILES
+    if c32:
+        flags |= CONV_CK32
     if ws is not None:
         flags |= CONV_WS | ({1: 0, 2: 1, 4: 2}[WC] << 8)
     if in_affine is not None:
@@ -435,7 +447,7 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
                 else ("conv_pipe_kernel<%d,%d,false,false%s>" % (MT, NT, (",true,true" if in_presplit else ",false,true") if m16 else (",true" if in_presplit else "")) if in_bnbwd is None
                       else "conv_pipe_kernel<%d,%d,true,true>" % (MT, NT)) if pipe
                 else "conv_mfma_kernel<%d,%d,%s,%d>" % (MT, NT, "true" if in_bnbwd is not None else "false", split)) + (
-             " C%d %dx%d" % (Cout, OH, OW) if LABEL_SHAPES else ""),
+             " C%d %dx%d%s" % (Cout, OH, OW, " plane32" if c32 else "") if LABEL_SHAPES else ""),
          flops=2.0 * B * OH * OW * Cout * Cin * len(taps),
          # algorithmic bytes: the input pixels this launch reads (all of them for a stride-1 / full-tap launch), the output it
          # writes, and every fused side stream once: shortcut add, raw + side draw of the fused BatchNorm backward, raw of the

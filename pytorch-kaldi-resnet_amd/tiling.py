@@ -10,6 +10,7 @@ from functools import lru_cache
 
 LDS_PIX_BYTES = 144
 SPLIT_PIX_BYTES = int(_os.environ.get('SPK_SPLIT_PIX_BYTES', '112'))   # LDS bytes per pixel of the bf16-split kernels (csrc/conv_kernel.h)
+C32_WHOLE_PIX_BYTES = 144     # f16x3, fused BatchNorm-backward data gradient at Cin = 32 with whole-pixel staging: [2 terms][32 ch fp16] + 16
 LDS_SOFT = 52 * 1024      # 3 blocks / CU
 LDS_HARD = 80 * 1024      # 2 blocks / CU
 
@@ -173,20 +174,23 @@ for _e in filter(None, _os.environ.get("SPK_PLAIN_TILE", "").split(";")):
 
 def conv_tile(OH, OW, IS, kspan_y, kspan_x, ntaps, Cout, mode=0, split=0):
     """mode 1 = data gradient with the BatchNorm backward fused into its input staging (heavier staging: it may prefer
-    wider channel tiles); table keys carry the mode as an 8th element and fall back to the plain entry.  split != 0
-    (bf16-split operands) consults its own table first."""
+    wider channel tiles); mode 2 = the same at Cin = 32 in the f16x3 mode with whole-pixel staging (C32_WHOLE_PIX_BYTES per
+    halo pixel, which is what the cost model prices).  Table keys carry the mode as an 8th element; mode 2 falls back to the
+    mode 1 entry, both to the plain entry.  split != 0 (bf16-split operands) consults its own table first."""
     key = (OH, OW, IS, kspan_y, kspan_x, ntaps, Cout)
     if mode and _FUSED_TILE_OVERRIDE and key == _FUSED_TILE_OVERRIDE[0]:
         return _FUSED_TILE_OVERRIDE[1]
     if not mode and (OH, OW, ntaps, Cout) in _PLAIN_TILE_OVERRIDE:
         return _PLAIN_TILE_OVERRIDE[(OH, OW, ntaps, Cout)]
     if split:
-        if mode and key + (mode,) in FORCE_CONV_SPLIT:
-            return FORCE_CONV_SPLIT[key + (mode,)]
+        for m in range(mode, 0, -1):
+            if key + (m,) in FORCE_CONV_SPLIT:
+                return FORCE_CONV_SPLIT[key + (m,)]
         if key in FORCE_CONV_SPLIT:
             return FORCE_CONV_SPLIT[key]
-    if mode and key + (mode,) in FORCE_CONV:
-        return FORCE_CONV[key + (mode,)]
+    for m in range(mode, 0, -1):
+        if key + (m,) in FORCE_CONV:
+            return FORCE_CONV[key + (m,)]
     if key in FORCE_CONV:
         return FORCE_CONV[key]
     return _conv_tile(*key)
