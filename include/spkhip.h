@@ -278,6 +278,46 @@ int spk_f16_window_count(const float* x, const float* scale, const float* shift,
  * scale input of a convolution / weight gradient that applies BatchNorm+ReLU while staging (SPK_IN_AFFINE_RELU) */
 int spk_affine_estimate(const float* scale, const float* shift, int C, const unsigned* amax_in, unsigned* est, void* stream);
 
+/* ---- squeeze-and-excitation (SELayer / SEBasicBlock, scripts/model.py:17-33,67-97; csrc/se.hip) ----------
+ * Tensors are NHWC fp32 [B][H*W][C], C a power of two in [32, 1024]; the gate matrices are W1 [Cr][C] (se.fc.0.weight) and
+ * W2 [C][Cr] (se.fc.2.weight), Cr <= 64, no biases.  z = scale_c raw + shift_c is the block's second BatchNorm (no ReLU).
+ * Every reduction runs in a fixed order (fp32 inside a block of pixels, fp64 across blocks and utterances): no float atomics. */
+/* reduction blocks per utterance: `partial` of spk_se_squeeze holds B * chunks * C floats, of spk_se_bwd_reduce twice that */
+int spk_se_chunks(long long HW);
+/* sums[b][c] = sum over the H*W pixels of x (AdaptiveAvgPool2d(1) before the division, :20,30); wlen (int32 [B], or NULL):
+ * only the columns w < wlen[b] count */
+int spk_se_squeeze(const float* x, float* partial, double* sums /*[B][C]*/, int B, int H, int W, int C, const int* wlen,
+                   void* stream);
+/* q = scale * sums / count + shift (scale = shift = NULL: q = sums / count), count = H * W or H * wlen[b];
+ * u = relu(W1 q) [B][Cr]; g = sigmoid(W2 u) [B][C] (:21-26,31) - all three are kept for the backward pass */
+int spk_se_excite(const double* sums, const float* scale, const float* shift, const float* W1, const float* W2, float* q,
+                  float* u, float* g, int B, int C, int Cr, int H, int W, const int* wlen, void* stream);
+/* out = [relu](g[b][c] * (raw * scale + shift) [+ res | + res * res_scale + res_shift]) (:33,94-95; scale = shift = NULL: the
+ * identity affine).  mask_out / amax_out as in spk_bn_apply; wlen: pixels at width w >= wlen[b] are stored as 0 */
+int spk_se_apply(const float* raw, const float* scale, const float* shift, const float* gate, const float* res,
+                 const float* res_scale, const float* res_shift, float* out, unsigned* mask_out, int B, int H, int W, int C,
+                 int relu, unsigned* amax_out, const int* wlen, void* stream);
+/* S[b][0][c] = sum_hw e, S[b][1][c] = sum_hw e * raw with e = dout masked by `act` (mask_mode 1: the activated block output,
+ * 3: its sign bits).  chan_amax ([C] zeros, or NULL): also the absmax of e per channel (float bits) */
+int spk_se_bwd_reduce(const float* dout, const float* raw, const float* act, float* partial, double* S /*[B][2][C]*/, int B,
+                      long long HW, int C, int mask_mode, unsigned* chan_amax, void* stream);
+/* the gate's backward chain and the BatchNorm-backward finalize of dz = g e + dq / HW, from the [B][C] tables alone:
+ * dg = scale S2 + shift S1, da = dg g (1 - g) [B][C], du = W2^T da [u > 0] [B][Cr], dq = W1^T du -> dq [2][B][C] = (dq, dq / HW);
+ * dW1 = sum_b du (x) q, dW2 = sum_b da (x) u, dgamma, dbeta (overwritten, or added to when accumulate != 0);
+ * coef [3][C] = (gamma invstd, mean dz, mean dz xhat) for spk_se_bwd_apply; est_out: atomicMax of the float bits of the bound
+ * max_c |k1| (A + max_b |dq / HW| + |m1| + Xhat |m2|)(1 + 2^-16) of |draw|, A from amax_in (absmax of dout) or chan_amax,
+ * Xhat = (R + |mean|) invstd with R from raw_amax - valid because 0 <= g <= 1 */
+int spk_se_bwd_gate(const double* S, const double* sums, const float* q, const float* u, const float* g, const float* W1,
+                    const float* W2, const float* mean, const float* invstd, const float* scale, const float* shift,
+                    const float* gamma, float* da, float* du, float* dq, float* dW1, float* dW2, float* dgamma, float* dbeta,
+                    float* coef, int accumulate, int B, int C, int Cr, long long HW, const unsigned* amax_in,
+                    const unsigned* raw_amax, const unsigned* chan_amax, unsigned* est_out, void* stream);
+/* draw = k1 (g e + dqs - m1 - xhat m2), as fp32 or (pair_scale) as an f16 pair tensor; e_out (may be dout itself, or NULL):
+ * e = dout [out > 0], the shortcut gradient; amax_out: absmax of draw */
+int spk_se_bwd_apply(const float* dout, const float* raw, const float* act, const float* gate, const float* dqs /*[B][C]*/,
+                     const float* mean, const float* invstd, const float* coef, float* draw, float* e_out, int B, long long HW,
+                     int C, int mask_mode, unsigned* amax_out, const unsigned* pair_scale, void* stream);
+
 /* ---- statistics pooling (StatsPooling, scripts/model.py:435-457; mode 0 = 'mean', 1 = 'mean+std') -------- */
 int spk_stats_pool_fwd(const float* x /*[B][H][W][C]*/, float* out /*[B][C*H*(1+mode)]*/, int B, int H, int W, int C,
                        int mode, void* stream);

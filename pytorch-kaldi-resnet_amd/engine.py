@@ -7,6 +7,12 @@ Data flow of one BasicBlock in training (reference scripts/model.py:48-64), NHWC
     out  = relu(bn2(raw2) + shortcut)                          one fused elementwise pass
 so each block costs 7 tensor passes over HBM instead of 11.  Saved for backward: x, raw1, raw2, out (+ the
 downsample's raw output).  Backward recomputes relu(bn1(raw1)) on the fly inside wgrad's input staging.
+
+SEBasicBlock (arch "se_resnet34", scripts/model.py:67-97): the last line becomes
+    sums = squeeze(raw2); q, u, g = excite(sums, bn2, W1, W2); out = relu(g * bn2(raw2) + shortcut)
+- one more read of raw2.  Backward: e = dout*[out > 0] is the shortcut gradient, bn2 sees dz = g*e + dq/HW; one pass reduces
+(sum e, sum e*raw2) per utterance, the gate kernels turn those [B][C] tables into dW1, dW2, dq and bn2's backward statistics,
+one pass writes draw2 (csrc/se.hip).  The data-gradient fusions that assume dz = d*[out > 0] are off around that BatchNorm.
 """
 import torch
 
@@ -83,6 +89,9 @@ class _Block:
         self.ds = None
         if bp.downsample is not None:
             self.ds = (_Conv(bp.downsample[0]), _BN(bp.downsample[1]))
+        # SEBasicBlock: the gate's parameter holder (w1 = se.fc.0.weight [C/16][C], w2 = se.fc.2.weight [C][C/16]).  The block's
+        # tail is then squeeze -> excite -> apply instead of bn_apply, and its last BatchNorm backward runs on the se_bwd kernels
+        self.se = bp.se if bp.kind == "se_basic" else None
 
 
 class _LogitsFn(torch.autograd.Function):
@@ -250,6 +259,16 @@ class Engine:
                 o_amax = take()
                 if c.stride == 2:
                     stage += 1
+                if last and b.se is not None:
+                    # z = bn2(conv2(.)) without ReLU or add, then the gate from its per-utterance channel means (over the valid
+                    # columns only) and out = relu(g z + shortcut), masked to the stage width here
+                    wls = None if wl is None else wl[stage]
+                    z, _ = ops.conv_fwd(h, c.wpk, c.cout, c.k, c.stride, epi_affine=(ev[0], ev[1]),
+                                        in_amax=h_amax if ops.split_for(c.k) == 3 else None)
+                    _, gate = self._se_gate(b, z, None, wls)
+                    h = ops.se_apply(z, None, gate, res=res, relu=True, amax_out=o_amax, wlen=wls)
+                    h_amax = o_amax
+                    continue
                 h, _ = ops.conv_fwd(h, c.wpk, c.cout, c.k, c.stride, epi_affine=(ev[0], ev[1]),
                                     epi_add=res if last else None, relu=True,
                                     in_amax=h_amax if ops.split_for(c.k) == 3 else None, out_amax=o_amax,
@@ -257,6 +276,14 @@ class Engine:
                 h_amax = o_amax
             a, a_amax = h, h_amax
         return a
+
+    @staticmethod
+    def _se_gate(b, t, affine, wlen=None):
+        """squeeze + excite of an SE block on the tensor t (raw conv output with `affine` = its BatchNorm rows, or z itself)
+        -> ((sums, q, u, g) as the backward needs them, g)"""
+        sums = ops.se_squeeze(t, wlen)
+        q, u, g = ops.se_excite(sums, affine, b.se.w1.data, b.se.w2.data, t.shape[1], t.shape[2], wlen)
+        return (sums, q, u, g), g
 
     def embed_eval(self, x, wl=None):
         feat = self.trunk_eval(x, wl)
@@ -391,13 +418,22 @@ class Engine:
                 raws.append(raw)
                 h, aff, h_amax = raw, (t4[2], t4[3]), est
             out_amax = take()
+            gate = None
+            if b.se is not None:
+                rec["se"], gate = self._se_gate(b, h, aff)
             if b.ds is not None:
                 rawd, st = ops.conv_fwd(a, b.ds[0].wpk, b.ds[0].cout, 1, b.ds[0].stride, stats=True,
                                         in_amax=a_amax if ops.split_for(1) == 3 else None)
                 td = b.ds[1].finalize(st, rawd.shape[0] * rawd.shape[1] * rawd.shape[2], keep=save)
-                out = ops.bn_apply(h, aff[0], aff[1], res=rawd, res_affine=(td[2], td[3]), relu=True, mask=use_masks,
-                                   amax_out=out_amax)
+                if gate is not None:
+                    out = ops.se_apply(h, aff, gate, res=rawd, res_affine=(td[2], td[3]), relu=True, mask=use_masks,
+                                       amax_out=out_amax)
+                else:
+                    out = ops.bn_apply(h, aff[0], aff[1], res=rawd, res_affine=(td[2], td[3]), relu=True, mask=use_masks,
+                                       amax_out=out_amax)
                 rec["rawd"] = rawd
+            elif gate is not None:
+                out = ops.se_apply(h, aff, gate, res=a, relu=True, mask=use_masks, amax_out=out_amax)
             else:
                 out = ops.bn_apply(h, aff[0], aff[1], res=a, relu=True, mask=use_masks, amax_out=out_amax)
             out, amask = out if use_masks else (out, None)
@@ -505,6 +541,10 @@ class Engine:
                 chan = self.chan_amax and amx is not None and stage_of[bi] == last_stage
                 if chan and bi > 0 and stage_of[bi - 1] == last_stage:
                     prev = None            # that BatchNorm's statistics come from its own reduction pass, with per-channel absmax
+                if bi > 0 and self.blocks[bi - 1].se is not None:
+                    # below an SE block the gradient wrt that BatchNorm's output is g e + dq / HW, not d [out > 0]: the epilogue
+                    # reduction (EPI_BNBWD) does not apply - its statistics come from the block's own tables (se_bwd_gate)
+                    prev = None
                 d, part, d_amax = self._block_bwd(self.blocks[bi], saved["blocks"][bi], d, acc, part, prev, d_amax, amx, chan)
                 saved["blocks"][bi] = None
                 if on_stage_done and (bi == 0 or stage_of[bi - 1] != stage_of[bi]):
@@ -558,8 +598,9 @@ class Engine:
             # form under a rigorous bound known before it is computed, staged by plain copy in its data and weight gradients
             pairs = f16 and self.pair_draw
             raw_amax = rec["raw_amax"][i] if f16 else None
-            if self.fuse_bn_apply and c.stride == 1 and (self.fuse_apply_min_c <= c.cout <= self.fuse_apply_max_c
-                                                         or (c.k == 1 and self.fuse_apply_1x1)):
+            se_last = last and b.se is not None     # (never the fused IN_BNBWD form: it assumes dz = g [out > 0])
+            if not se_last and self.fuse_bn_apply and c.stride == 1 and (self.fuse_apply_min_c <= c.cout <= self.fuse_apply_max_c
+                                                                         or (c.k == 1 and self.fuse_apply_1x1)):
                 ca = None
                 if g_part is None:
                     ca = amx.take_n(c.cout) if (chan and last and f16) else None
@@ -593,7 +634,24 @@ class Engine:
                 lazy_dz = False
                 est = take() if pairs else None
                 pair = (g_amax, raw_amax, est) if pairs else None
-                if last:
+                if se_last:
+                    # SE block: e = dout [out > 0] is the shortcut gradient; the BatchNorm sees dz = g e + dq / HW.  One pass
+                    # reduces (sum e, sum e raw) per utterance, the gate kernels turn those tables into dW1, dW2, dq and the
+                    # BatchNorm-backward statistics, one pass writes draw (and e, unless the first conv re-forms it from the bits)
+                    bits = rec.get("mask")
+                    lazy_dz = b.ds is None and bits is not None and n > 1
+                    ca = amx.take_n(c.cout) if (chan and pairs) else None
+                    mode, actm = (MASK_BITS, bits) if bits is not None else (MASK_ACT, out)
+                    sums, q, u, gate = rec["se"]
+                    S = ops.se_bwd_reduce(g, raw, actm, mode, chan_amax=ca)
+                    w1, w2 = b.se.w1, b.se.w2
+                    coef, dq, _, _ = ops.se_bwd_gate(S, sums, q, u, gate, w1.data, w2.data, bn.t4, bn.h.weight.data, w1.grad,
+                                                     w2.grad, bn.h.weight.grad, bn.h.bias.grad, raw.shape[1] * raw.shape[2],
+                                                     accumulate=acc, pair=pair, chan_amax=ca)
+                    draw = ops.se_bwd_apply(g, raw, actm, mode, gate, dq[1], bn.t4, coef, e_out=None if lazy_dz else g,
+                                            amax_out=draw_amax, pair_scale=est)
+                    dz = None if lazy_dz else g                         # (dout now holds e)
+                elif last:
                     # separate BatchNorm-backward pass (then a plain, pipelined data gradient).  With sign masks it reads the
                     # bits instead of the block output, and with an identity shortcut dz is not stored: the first conv's
                     # data-gradient epilogue re-forms it from dout and the bits (as in the fused form above)

@@ -57,6 +57,13 @@ _SIGS = {
     "spk_bnbwd_estimate": [_P, _P, _P, _I, _P, _P, _P, _P],
     "spk_f16_window_count": [_P, _P, _P, _L, _I, _P, _I, _P, _P],
     "spk_affine_estimate": [_P, _P, _I, _P, _P, _P],
+    "spk_se_chunks": [_L],
+    "spk_se_squeeze": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "spk_se_excite": [_P] * 8 + [_I] * 5 + [_P, _P],
+    "spk_se_apply": [_P] * 9 + [_I] * 5 + [_P, _P, _P],
+    "spk_se_bwd_reduce": [_P] * 5 + [_I, _L, _I, _I, _P, _P],
+    "spk_se_bwd_gate": [_P] * 20 + [_I] * 4 + [_L] + [_P] * 5,
+    "spk_se_bwd_apply": [_P] * 10 + [_I, _L, _I, _I, _P, _P, _P],
     "spk_stats_pool_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stats_pool_fwd_len": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stats_pool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],

@@ -2,7 +2,8 @@
 
 Mirrors the reference module's interface (scripts/model.py:334-432): same constructor arguments (plus a
 real ``arch`` switch, which the reference parses but ignores - train_resnet.py:42,152), ``forward(x, y)``,
-``predict(x)``, ``loadParameters(state)``, the 219/225/224-key ``state_dict`` naming, ``parameters()`` whose
+``predict(x)``, ``loadParameters(state)``, the 219/225/224-key ``state_dict`` naming (251 keys with
+``arch="se_resnet34"``), ``parameters()`` whose
 ``.grad`` is filled by ``loss.backward()``, and ``train()/eval()`` switching BatchNorm behaviour.  All
 arithmetic runs in libspkhip.so (hand-written gfx950 kernels) through ``engine.Engine``; the modules below
 only hold parameters.  There is no CPU path: calling forward on a CPU tensor raises.
@@ -20,7 +21,9 @@ ARCH_LAYERS = {
     "resnet34": ("basic", [3, 4, 6, 3]),
     "resnet50": ("bottleneck", [3, 4, 6, 3]),
     "resnet101": ("bottleneck", [3, 4, 23, 3]),
+    "se_resnet34": ("se_basic", [3, 4, 6, 3]),      # SEBasicBlock, scripts/model.py:67-97,300-302
 }
+SE_REDUCTION = 16                    # scripts/model.py:18,70
 STAGE_WIDTH = [32, 64, 128, 256]     # scripts/model.py:215-218
 STAGE_STRIDE = [1, 2, 2, 2]
 
@@ -62,6 +65,25 @@ class LinearP(nn.Module):
             self.register_parameter("bias", None)
 
 
+class SEP(nn.Module):
+    """Holder for SELayer (scripts/model.py:17-26): fc = Sequential(Linear(C, C/16, no bias), ReLU, Linear(C/16, C, no bias),
+    Sigmoid) - the state-dict keys are se.fc.0.weight [C/16, C] and se.fc.2.weight [C, C/16], nn.Linear's default init."""
+
+    def __init__(self, channel, reduction=SE_REDUCTION):
+        super().__init__()
+        self.fc = nn.Module()
+        self.fc.add_module("0", LinearP(channel, channel // reduction, bias=False))
+        self.fc.add_module("2", LinearP(channel // reduction, channel, bias=False))
+
+    @property
+    def w1(self):
+        return getattr(self.fc, "0").weight
+
+    @property
+    def w2(self):
+        return getattr(self.fc, "2").weight
+
+
 class AAMP(nn.Module):
     """Holder for AAMLayer.weight [n_classes, in_feats], xavier_normal_ (scripts/model.py:470-471)."""
 
@@ -76,11 +98,13 @@ class BlockP(nn.Module):
     def __init__(self, kind, inplanes, planes, stride, downsample):
         super().__init__()
         self.kind, self.stride = kind, stride
-        if kind == "basic":      # scripts/model.py:38-46
+        if kind in ("basic", "se_basic"):      # scripts/model.py:38-46, 70-79
             self.conv1 = ConvP(inplanes, planes, 3, stride)
             self.bn1 = BNP(planes)
             self.conv2 = ConvP(planes, planes, 3, 1)
             self.bn2 = BNP(planes)
+            if kind == "se_basic":
+                self.se = SEP(planes)
         else:                    # Bottleneck with expansion = 1, scripts/model.py:100-113
             self.conv1 = ConvP(inplanes, planes, 1, 1)
             self.bn1 = BNP(planes)

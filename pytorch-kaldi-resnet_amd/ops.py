@@ -852,6 +852,88 @@ def bn_bwd_partial(dy, raw, act, bn4, mask_mode, chan_amax=None):
     return part
 
 
+# ---- squeeze-and-excitation (csrc/se.hip) -----------------------------------------------------------------------------------
+def se_squeeze(x, wlen=None):
+    """sums [B][C] (fp64) of an NHWC tensor over H*W; wlen (int32 device [B]): over the first wlen[b] columns only"""
+    B, H, W, C = x.shape
+    if wlen is not None:
+        _check_wlen(wlen, B)
+    part = torch.empty(B * hip.lib().spk_se_chunks(H * W) * C, device=x.device, dtype=torch.float32)
+    sums = torch.empty(B, C, device=x.device, dtype=torch.float64)
+    call("spk_se_squeeze", ptr(x), ptr(part), ptr(sums), B, H, W, C, ptr(wlen), stream(), nbytes=4.0 * x.numel())
+    return sums
+
+
+def se_excite(sums, affine, w1, w2, H, W, wlen=None):
+    """(q [B][C], u [B][Cr], g [B][C]) from the squeeze sums: q = scale*sums/count + shift (affine=None: sums/count),
+    u = relu(w1 q), g = sigmoid(w2 u); count = H*W, or H*wlen[b]"""
+    B, C = sums.shape
+    Cr = w1.shape[0]
+    assert tuple(w1.shape) == (Cr, C) and tuple(w2.shape) == (C, Cr)
+    q = torch.empty(B, C, device=sums.device, dtype=torch.float32)
+    u = torch.empty(B, Cr, device=sums.device, dtype=torch.float32)
+    g = torch.empty(B, C, device=sums.device, dtype=torch.float32)
+    call("spk_se_excite", ptr(sums), ptr(affine[0]) if affine else None, ptr(affine[1]) if affine else None, ptr(w1), ptr(w2),
+         ptr(q), ptr(u), ptr(g), B, C, Cr, H, W, ptr(wlen), stream())
+    return q, u, g
+
+
+def se_apply(raw, affine, gate, res=None, res_affine=None, relu=True, mask=False, amax_out=None, wlen=None, out=None):
+    """out = [relu](gate[b][c]*(raw*scale + shift) [+ res | + res*rscale + rshift]) (affine=None: gate*raw); mask / amax_out as
+    in bn_apply; wlen: columns w >= wlen[b] are stored as 0"""
+    B, H, W, C = raw.shape
+    if wlen is not None:
+        _check_wlen(wlen, B)
+    if out is None:
+        out = torch.empty_like(raw)
+    mk = torch.empty(B * H * W * (C // 32), device=raw.device, dtype=torch.int32) if mask else None
+    call("spk_se_apply", ptr(raw), ptr(affine[0]) if affine else None, ptr(affine[1]) if affine else None, ptr(gate), ptr(res),
+         ptr(res_affine[0]) if res_affine else None, ptr(res_affine[1]) if res_affine else None, ptr(out), ptr(mk), B, H, W, C,
+         1 if relu else 0, ptr(amax_out), ptr(wlen), stream(),
+         nbytes=4.0 * raw.numel() * (2 + (1 if res is not None else 0)) + (raw.numel() / 8 if mask else 0))
+    return (out, mk) if mask else out
+
+
+def se_bwd_reduce(dout, raw, act, mask_mode, chan_amax=None):
+    """S [B][2][C] (fp64) = (sum_hw e, sum_hw e*raw), e = dout masked by act (MASK_ACT: the block output, MASK_BITS: its bits)"""
+    B, H, W, C = raw.shape
+    part = torch.empty(B * hip.lib().spk_se_chunks(H * W) * 2 * C, device=raw.device, dtype=torch.float32)
+    S = torch.empty(B, 2, C, device=raw.device, dtype=torch.float64)
+    call("spk_se_bwd_reduce", ptr(dout), ptr(raw), ptr(act), ptr(part), ptr(S), B, H * W, C, mask_mode, ptr(chan_amax), stream(),
+         nbytes=_bn_bwd_bytes(raw, mask_mode, 2))
+    return S
+
+
+def se_bwd_gate(S, sums, q, u, g, w1, w2, bn4, gamma, dw1, dw2, dgamma, dbeta, HW, accumulate=False, pair=None, chan_amax=None):
+    """Backward of the gate and the BatchNorm-backward finalize of dz = g*e + dq/HW from the [B][C] tables (spk_se_bwd_gate).
+    -> (coef [3][C], dq [2][B][C] = (dq, dq/HW), da [B][C], du [B][Cr]).  dw1 / dw2 / dgamma / dbeta are overwritten or
+    accumulated.  pair = (amax_in, raw_amax, est): est receives the rigorous bound of |draw| (f16x3 mode)."""
+    B, C = q.shape
+    Cr = u.shape[1]
+    dev = q.device
+    coef = torch.empty(3, C, device=dev, dtype=torch.float32)
+    dq = torch.empty(2, B, C, device=dev, dtype=torch.float32)
+    da = torch.empty(B, C, device=dev, dtype=torch.float32)
+    du = torch.empty(B, Cr, device=dev, dtype=torch.float32)
+    call("spk_se_bwd_gate", ptr(S), ptr(sums), ptr(q), ptr(u), ptr(g), ptr(w1), ptr(w2), ptr(bn4[0]), ptr(bn4[1]), ptr(bn4[2]),
+         ptr(bn4[3]), ptr(gamma), ptr(da), ptr(du), ptr(dq), ptr(dw1), ptr(dw2), ptr(dgamma), ptr(dbeta), ptr(coef),
+         1 if accumulate else 0, B, C, Cr, HW, ptr(pair[0]) if pair else None, ptr(pair[1]) if pair else None,
+         ptr(chan_amax) if pair else None, ptr(pair[2]) if pair else None, stream())
+    return coef, dq, da, du
+
+
+def se_bwd_apply(dout, raw, act, mask_mode, g, dqs, bn4, coef, e_out=None, amax_out=None, pair_scale=None, draw_out=None):
+    """draw = k1*(g*e + dqs - m1 - xhat*m2), fp32 or (pair_scale: the bound slot) an f16 pair tensor; e = dout*[out > 0] goes
+    to e_out when given (dout itself is allowed)"""
+    B, H, W, C = raw.shape
+    if draw_out is None:
+        draw_out = torch.empty_like(raw)
+    call("spk_se_bwd_apply", ptr(dout), ptr(raw), ptr(act), ptr(g), ptr(dqs), ptr(bn4[0]), ptr(bn4[1]), ptr(coef), ptr(draw_out),
+         ptr(e_out), B, H * W, C, mask_mode, ptr(amax_out), ptr(pair_scale), stream(),
+         nbytes=_bn_bwd_bytes(raw, mask_mode, 3 + (1 if e_out is not None else 0)))
+    return draw_out
+
+
 def stats_pool_fwd(x, mode, wlen=None):
     """wlen: int32 device [B] valid widths: row b pools over its first wlen[b] frames only (spk_stats_pool_fwd_len)"""
     B, H, W, C = x.shape

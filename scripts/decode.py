@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 parser = argparse.ArgumentParser(description="speaker-embedding extraction (MI355X-native)")
 parser.add_argument("--spk_num", type=int, help="number of speakers")
-parser.add_argument("--arch", type=str, required=True)
+parser.add_argument("--arch", type=str, required=True, help="resnet18/34/50/101 or se_resnet34")
 parser.add_argument("--input-dim", type=int, required=True)
 parser.add_argument("--pooling", type=str, required=True, help="mean or mean+std")
 parser.add_argument("--chunk-size", default=-1, type=int)

@@ -37,7 +37,7 @@ parser.add_argument("--dataset", type=str, default="v1", help="v1 or v2")
 parser.add_argument("--min-chunk-size", default=200, type=int)
 parser.add_argument("--max-chunk-size", default=400, type=int)
 parser.add_argument("--log-dir", type=str, required=True, help="logging directory")
-parser.add_argument("-a", "--arch", metavar="ARCH", default="resnet34", help="resnet18/34/50/101")
+parser.add_argument("-a", "--arch", metavar="ARCH", default="resnet34", help="resnet18/34/50/101 or se_resnet34")
 parser.add_argument("-j", "--workers", default=2, type=int, metavar="N")
 parser.add_argument("--epochs", default=10, type=int, metavar="N")
 parser.add_argument("--start-epoch", default=0, type=int, metavar="N")
