@@ -1,5 +1,6 @@
 """Thin Python wrappers over the libspkhip exports: shape checks, output allocation (torch caching
 allocator owns every device buffer), tile selection, tap tables.  No arithmetic happens here."""
+import collections
 import ctypes
 import os
 
@@ -261,59 +262,110 @@ class PackTable:
 
 STREAM_1X1 = os.environ.get("SPK_STREAM_1X1", "1") == "1"
 STREAM_1X1_BLOCKS = int(os.environ.get("SPK_STREAM_1X1_BLOCKS", "512"))       # persistent blocks: two per CU
-
-
-def _conv1x1_stream(x, wpk, out, in_affine, epi_add, add_mask, bn_bwd, want_stats, in_amax, out_amax, in_presplit):
-    B, H, W, C = x.shape
-    P = B * H * W
-    tp = 64 * (1 if C >= 128 else (2 if C == 64 else 4))
-    nblocks = max(1, min(STREAM_1X1_BLOCKS, -(-P // tp)))
-    flags = 0
-    if in_affine is not None:
-        flags |= IN_AFFINE_RELU
-    if in_presplit:
-        assert in_affine is None
-        flags |= IN_PRESPLIT
-    if epi_add is not None:
-        assert epi_add.shape == out.shape
-        flags |= EPI_ADD
-    bn_mask = bn_bwd[3] if (bn_bwd is not None and len(bn_bwd) > 3) else None
-    for mk in (bn_mask, add_mask):
-        if mk is not None:
-            assert mk.dtype == torch.int32 and mk.numel() == out.numel() // 32, "sign mask shape"
-    stats = None
-    if bn_bwd is not None:
-        want_stats = True
-        flags |= EPI_BNBWD
-        assert bn_bwd[0].shape == out.shape
-    if want_stats:
-        flags |= EPI_STATS
-        stats = torch.empty(hip.lib().spk_conv1x1_stream_rows(nblocks, C), C, 2, device=x.device, dtype=torch.float32)
-    call("spk_conv1x1_stream", ptr(x), ptr(wpk), ptr(out), ptr(in_affine[0]) if in_affine else None,
-         ptr(in_affine[1]) if in_affine else None, ptr(epi_add), ptr(add_mask), ptr(bn_bwd[0]) if bn_bwd else None, ptr(bn_mask),
-         ptr(bn_bwd[2]) if bn_bwd else None, ptr(stats), P, C, flags, ptr(in_amax), ptr(out_amax), nblocks, stream(),
-         label="conv1x1_stream_kernel<%d>" % C + (" C%d %dx%d" % (C, H, W) if LABEL_SHAPES else ""),
-         flops=2.0 * P * C * C,
-         nbytes=4.0 * (P * C * (2 + (1 if epi_add is not None else 0) + (1 if bn_bwd is not None else 0))
-                       + (P * C / 32) * ((bn_mask is not None) + (add_mask is not None)) + wpk.numel()))
-    return stats
-
-
 STREAM_C32 = os.environ.get("SPK_STREAM_C32", "1") == "1"
 STREAM_C32_BLOCKS = int(os.environ.get("SPK_STREAM_C32_BLOCKS", "512"))
+FWD_TAPS = tuple((kh - 1, kw - 1, kh * 3 + kw) for kh in range(3) for kw in range(3))
+
+# What a forward / data-gradient launch needs that is not a pointer (_plan_conv).  stats_rows: partial-statistics rows where
+# flags carry EPI_STATS (None for spk_conv1x1_stream: spk_conv1x1_stream_rows says); key: the tile-table key, and the tile,
+# register tile, wave layout, kc, ips and effective IS of spk_conv_mfma / spk_conv_mfma_len (the streaming entries have none).
+ConvPlan = collections.namedtuple("ConvPlan", "entry flags label nblocks stats_rows key TH TW MT NT WC kc ips IS",
+                                  defaults=(None,) * 9 + (1, 1))
+# ... and a weight-gradient launch (_plan_wgrad).  family: wm16 | c32m16 | wm | 1x1 | ws | pipe | split | f32
+WgradPlan = collections.namedtuple("WgradPlan", "TH TW WN family cg nsplit flags label")
 
 
-def _conv3x3_c32_stream(x, wpk, out, in_affine, in_amax, out_amax):
-    B, H, W, _ = x.shape
-    ntiles = B * (-(-H // 8)) * (-(-W // 16))
-    nblocks = max(1, min(STREAM_C32_BLOCKS, ntiles))
-    stats = torch.empty(4 * nblocks, 32, 2, device=x.device, dtype=torch.float32)
-    flags = EPI_STATS | (IN_AFFINE_RELU if in_affine is not None else 0)
-    call("spk_conv3x3_c32_stream", ptr(x), ptr(wpk), ptr(out), ptr(in_affine[0]) if in_affine else None,
-         ptr(in_affine[1]) if in_affine else None, ptr(stats), B, H, W, flags, ptr(in_amax), ptr(out_amax), nblocks, stream(),
-         label="conv3x3_c32_stream_kernel" + (" C32 %dx%d" % (H, W) if LABEL_SHAPES else ""),
-         flops=2.0 * B * H * W * 32 * 32 * 9, nbytes=4.0 * (2 * B * H * W * 32 + wpk.numel()))
-    return stats
+def _mask_form(t, n):
+    """how a BatchNorm-backward operand tuple (bn_bwd: n = 3, in_bnbwd: n = 4) carries its ReLU mask: None | "sign" (one more
+    element: sign-bit words) | "raw" (no activation: recomputed from the raw tensor) | "act" (an activation tensor)"""
+    return None if t is None else "sign" if len(t) > n else "raw" if t[1] is None else "act"
+
+
+def _plan_conv(B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, taps, IS, OS, ooy, oox, split, experimental, in_affine=False,
+               epi_affine=False, epi_add=False, relu=False, want_stats=False, bn_bwd=None, in_bnbwd=None, side=False,
+               add_mask=False, in_presplit=False, side_presplit=False, wlen=False, out_is_x=False):
+    """Which kernel form a forward / data-gradient launch takes, on which tile, under which label: integers, booleans (is the
+    optional operand there) and the module switches in, a ConvPlan out - no tensor, no device, no library call.  bn_bwd /
+    in_bnbwd: _mask_form.  experimental: the library has the opt-in kernel forms (_experimental())."""
+    ntaps = len(taps)
+    dys, dxs = [t[0] for t in taps], [t[1] for t in taps]
+    want_stats = want_stats or bn_bwd is not None
+    flags = ((IN_AFFINE_RELU if in_affine else 0) | (IN_PRESPLIT if in_presplit else 0) | (SIDE_PRESPLIT if side_presplit else 0)
+             | (EPI_AFFINE if epi_affine else 0) | (EPI_ADD if epi_add else 0) | (EPI_RELU if relu else 0)
+             | (IN_BNBWD if in_bnbwd is not None else 0) | (EPI_BNBWD if bn_bwd is not None else 0) | (EPI_WMASK if wlen else 0)
+             | (EPI_STATS if want_stats else 0))
+    shape = " C%d %dx%d" % (Cout, OH, OW) if LABEL_SHAPES else ""
+    # what both streaming kernels ask: f16x3, the same map in and out at stride 1, training-mode epilogues, no length mask
+    same_map = (not wlen and split == 3 and IS == 1 and OS == 1 and ooy == 0 and oox == 0 and (IH, IW) == (OH, OW) == (OHf, OWf)
+                and in_bnbwd is None and not side and not epi_affine and not relu and not side_presplit)
+    # Streaming 3x3 forward kernel of the 32-channel layer (csrc/conv3x3_c32_stream.hip): 32 -> 32 channels, the forward tap
+    # order, raw output + statistics, plain or fused-BatchNorm input.  (A data gradient has mirrored taps: general kernel.)
+    stream_c32 = (STREAM_C32 and same_map and Cin == 32 and Cout == 32 and want_stats and bn_bwd is None and not epi_add
+                  and not in_presplit and not add_mask and tuple(taps) == FWD_TAPS and B * OH * OW * 32 < 2 ** 31 - 65536)
+    if stream_c32:
+        nblocks = max(1, min(STREAM_C32_BLOCKS, B * (-(-IH // 8)) * (-(-IW // 16))))
+        return ConvPlan("spk_conv3x3_c32_stream", flags, "conv3x3_c32_stream_kernel" + shape, nblocks, 4 * nblocks)
+    # Streaming 1x1 kernel (csrc/conv1x1_stream.hip): C -> C channels (raw output + statistics; data gradients: shortcut add with
+    # or without its sign mask, BatchNorm-backward statistics with the mask as sign bits or recomputed from the raw tensor).
+    # Everything else - eval-mode epilogues, strided 1x1, other widths, the fused input BatchNorm backward, an activation tensor
+    # as the mask, an output that aliases the input - stays on the general kernel.
+    stream_1x1 = (STREAM_1X1 and same_map and ntaps == 1 and dys[0] == 0 and dxs[0] == 0 and Cin == Cout and Cin in (32, 64, 128)
+                  and not out_is_x and bn_bwd != "act" and B * OH * OW * Cin < 2 ** 31)
+    if stream_1x1:
+        tp = 64 * (1 if Cin >= 128 else (2 if Cin == 64 else 4))
+        nblocks = max(1, min(STREAM_1X1_BLOCKS, -(-(B * IH * IW) // tp)))
+        return ConvPlan("spk_conv1x1_stream", flags, "conv1x1_stream_kernel<%d>" % Cin + shape, nblocks)
+    ips = 1
+    if ntaps == 1 and IS > 1 and dys[0] == 0 and dxs[0] == 0:
+        ips, IS = IS, 1          # strided 1x1: address the input through a strided view, stage only the pixels used
+    key = (OH, OW, IS, max(dys) - min(dys) + 1, max(dxs) - min(dxs) + 1, ntaps, Cout)
+    # (mode 2: the fused data gradient that may stage whole pixels - its own table key, 144 B per halo pixel)
+    c32 = C32_PLANE == 32 and split == 3 and Cin == 32 and in_bnbwd is not None and ntaps == 9
+    TH, TW, MT, NT = tiling.conv_tile(*key, mode=(2 if c32 else 1) if in_bnbwd is not None else 0, split=split)
+    # fused BatchNorm backward with the mask as sign bits on <= 128 output channels: optionally the in-wave pipelined kernel
+    pipe_fused = (PIPE_CONV and PIPE_BNBWD and split == 3 and in_bnbwd == "sign" and MT * NT <= 4 and Cout <= 128
+                  and WS_FORCE is None and WS_CONV != "1" and not side_presplit)
+    # Producer / consumer (wave-specialised, persistent) kernel for the bf16-split 3x3 launches (csrc/conv_ws_kernel.h) with
+    # its own wave layouts and tiles; f16 pair tensors and everything else stay on conv_mfma_kernel / conv_pipe_kernel.
+    ws_on = (WS_CONV == "1" or WS_FORCE is not None or (
+        WS_CONV == "auto" and experimental and split == 3 and in_bnbwd is not None and Cout >= WS_AUTO_MIN_COUT and not pipe_fused))
+    ws, WC = None, 1
+    if split and ws_on and not side_presplit and not in_presplit and ntaps >= WS_MIN_TAPS and ips == 1:
+        ws = WS_FORCE or tiling.ws_tile(*key)
+    if ws is not None:
+        TH, TW, MT, NT, WC = ws
+        flags |= CONV_WS | ({1: 0, 2: 1, 4: 2}[WC] << 8)
+    # single-tap (1x1) convolutions stage several 32-channel planes per barrier: their K loop per plane is only 4 MFMA groups
+    kc = 1
+    if ntaps == 1:
+        halo = ((TH - 1) * IS + 1) * ((TW - 1) * IS + 1)
+        kc = next((c for c in KC_CANDIDATES if Cin % (32 * c) == 0 and c * halo * tiling.LDS_PIX_BYTES <= tiling.LDS_HARD), 1)
+    # in-wave pipelined kernel (csrc/conv_kernel.h, PIPE): f16x3 3x3 launches whose two halo tiles fit, with a plain input (or the
+    # fused BatchNorm backward above: the ReLU mask as sign bits - not read from an activation), on a register tile
+    # csrc/conv_pipe.hip instantiates; any other tile stays on conv_mfma_kernel (same LDS tile, same sums)
+    halo9 = ((TH - 1) * IS + key[3]) * ((TW - 1) * IS + key[4])
+    pipe = (PIPE_CONV and ws is None and split == 3 and ntaps == 9 and kc == 1 and (in_bnbwd is None or pipe_fused) and halo9 <= 576
+            and (2 * halo9 + 1) * 80 <= PIPE_MAX_LDS and Cin >= PIPE_MIN_CIN and (MT, NT) in PIPE_TILES)
+    # its 16x16x32 form (conv_kernel.h, M16): the (3, 2) register tile, at most eight staging items per plane
+    m16 = pipe and PIPE_M16 and in_bnbwd is None and (MT, NT) == (3, 2) and halo9 <= 512 and IS == 1
+    # whole-pixel staging of the 32-channel fused data gradient: on the register tiles compiled for it, on conv_mfma_kernel
+    c32 = c32 and ws is None and not pipe and kc == 1 and (MT, NT) in C32_PLANE_TILES
+    flags |= (CONV_PIPE if pipe else 0) | (CONV_M16 if m16 else 0) | (CONV_CK32 if c32 else 0)
+    fused = "true" if in_bnbwd is not None else "false"
+    if ws is not None:
+        label = "conv_ws_kernel<%d,%d,%d,%s,%d>" % (MT, NT, WC, fused, split)
+    elif pipe and in_bnbwd is not None:
+        label = "conv_pipe_kernel<%d,%d,true,true>" % (MT, NT)
+    elif pipe:
+        pair = ",true" if in_presplit else (",false" if m16 else "")
+        label = "conv_pipe_kernel<%d,%d,false,false%s%s>" % (MT, NT, pair, ",true" if m16 else "")
+    else:
+        label = "conv_mfma_kernel<%d,%d,%s,%d>" % (MT, NT, fused, split)
+    if LABEL_SHAPES and c32:
+        shape += " plane32"
+    rows = (4 // WC) * B * (-(-OH // TH)) * (-(-OW // TW))      # one partial row per wave (per pixel group of waves)
+    return ConvPlan("spk_conv_mfma_len" if wlen else "spk_conv_mfma", flags, label + shape, None, rows, key,
+                    TH, TW, MT, NT, WC, kc, ips, IS)
 
 
 def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, epi_affine, epi_add, relu, want_stats,
@@ -321,95 +373,20 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
                  in_presplit=False, side_presplit=False, wlen=None):
     B, IH, IW, Cin = x.shape
     OHf, OWf = out.shape[1], out.shape[2]
+    pa = (B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, taps, IS, OS, ooy, oox, split, _experimental(), in_affine is not None,
+          epi_affine is not None, epi_add is not None, relu, want_stats, _mask_form(bn_bwd, 3), _mask_form(in_bnbwd, 4),
+          side is not None, add_mask is not None, in_presplit, side_presplit, wlen is not None, out is x)
+    if tiling.AUTOTUNE and PROFILE is None and not torch.cuda.is_current_stream_capturing():
+        p = _plan_conv(*pa)      # before the plan that counts: the autotuner fills tiling.FORCE_* (streaming forms have no key)
+        if p.key is not None and p.key not in (tiling.FORCE_CONV_SPLIT if split else tiling.FORCE_CONV):
+            _autotune_conv(p.key, x, wpk, out, Cout, taps, p.IS, OS, ooy, oox, OH, OW, in_affine, epi_affine, epi_add, relu, split,
+                           in_amax=in_amax, in_presplit=in_presplit)
+    p = _plan_conv(*pa)
     if wlen is not None:
         _check_wlen(wlen, B)
-    # Streaming 3x3 forward kernel of the 32-channel layer (csrc/conv3x3_c32_stream.hip): 32 -> 32 channels, stride 1, the forward tap
-    # order, raw output + statistics, plain or fused-BatchNorm input.  (A data gradient has mirrored taps: general kernel.)
-    if (STREAM_C32 and wlen is None and split == 3 and Cin == 32 and Cout == 32 and IS == 1 and OS == 1 and ooy == 0 and oox == 0
-            and (IH, IW) == (OH, OW) == (OHf, OWf) and want_stats and in_bnbwd is None and side is None and epi_affine is None
-            and epi_add is None and not relu and bn_bwd is None and not in_presplit and not side_presplit and add_mask is None
-            and list(taps) == [(kh - 1, kw - 1, kh * 3 + kw) for kh in range(3) for kw in range(3)] and B * OH * OW * 32 < 2 ** 31 - 65536):
-        return _conv3x3_c32_stream(x, wpk, out, in_affine, in_amax, out_amax)
-    # Streaming 1x1 kernel (csrc/conv1x1_stream.hip): C -> C channels at stride 1 in the f16x3 mode, training-mode epilogues only
-    # (raw output + statistics; data gradients: shortcut add with or without its sign mask, BatchNorm-backward statistics with the
-    # mask as sign bits or recomputed from the raw tensor).  Everything else - eval-mode epilogues, strided 1x1, other widths,
-    # the fused input BatchNorm backward, an activation tensor as the mask - stays on the general kernel.
-    if (STREAM_1X1 and wlen is None and split == 3 and len(taps) == 1 and taps[0][0] == 0 and taps[0][1] == 0 and IS == 1 and OS == 1 and ooy == 0
-            and oox == 0 and Cin == Cout and Cin in (32, 64, 128) and (IH, IW) == (OH, OW) == (OHf, OWf) and in_bnbwd is None
-            and side is None and epi_affine is None and not relu and not side_presplit and out is not x
-            and (bn_bwd is None or bn_bwd[1] is None or len(bn_bwd) > 3) and B * OH * OW * Cin < 2 ** 31):
-        return _conv1x1_stream(x, wpk, out, in_affine, epi_add, add_mask, bn_bwd, want_stats, in_amax, out_amax, in_presplit)
-    dys = [t[0] for t in taps]
-    dxs = [t[1] for t in taps]
-    tws = [t[2] for t in taps]
-    ips = 1
-    if len(taps) == 1 and IS > 1 and dys[0] == 0 and dxs[0] == 0:
-        ips, IS = IS, 1          # strided 1x1: address the input through a strided view, stage only the pixels used
-    key = (OH, OW, IS, max(dys) - min(dys) + 1, max(dxs) - min(dxs) + 1, len(taps), Cout)
-    if tiling.AUTOTUNE and key not in (tiling.FORCE_CONV_SPLIT if split else tiling.FORCE_CONV) and PROFILE is None and not torch.cuda.is_current_stream_capturing():
-        _autotune_conv(key, x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, epi_affine, epi_add, relu, split,
-                       in_amax=in_amax, in_presplit=in_presplit)
-    # (mode 2: the fused data gradient that may stage whole pixels - its own table key, 144 B per halo pixel)
-    c32 = C32_PLANE == 32 and split == 3 and Cin == 32 and in_bnbwd is not None and len(taps) == 9
-    TH, TW, MT, NT = tiling.conv_tile(*key, mode=(2 if c32 else 1) if in_bnbwd is not None else 0, split=split)
-    # Producer / consumer (wave-specialised, persistent) kernel for the bf16-split 3x3 launches (csrc/conv_ws_kernel.h) with
-    # its own wave layouts and tiles; everything else stays on conv_mfma_kernel.
-    ws, WC = None, 1
-    # fused BatchNorm backward with the mask as sign bits on <= 128 output channels: optionally the in-wave pipelined kernel
-    pipe_fused = (PIPE_CONV and PIPE_BNBWD and split == 3 and in_bnbwd is not None and len(in_bnbwd) > 4 and MT * NT <= 4
-                  and Cout <= 128 and WS_FORCE is None and WS_CONV != "1" and not side_presplit)
-    ws_on = (WS_CONV == "1" or WS_FORCE is not None or (
-        WS_CONV == "auto" and _experimental() and split == 3 and in_bnbwd is not None and Cout >= WS_AUTO_MIN_COUT
-        and not pipe_fused))
-    if side_presplit or in_presplit:
-        ws_on = False            # f16 pair tensors: conv_mfma_kernel / conv_pipe_kernel only
-    if split and ws_on and len(taps) >= WS_MIN_TAPS and ips == 1:
-        ws = WS_FORCE or tiling.ws_tile(*key)
-    if ws is not None:
-        TH, TW, MT, NT, WC = ws
-    # single-tap (1x1) convolutions stage several 32-channel planes per barrier: their K loop per plane is only 4 MFMA groups
-    kc = 1
-    if len(taps) == 1:
-        halo = ((TH - 1) * IS + 1) * ((TW - 1) * IS + 1)
-        for cand in KC_CANDIDATES:
-            if Cin % (32 * cand) == 0 and cand * halo * tiling.LDS_PIX_BYTES <= tiling.LDS_HARD:
-                kc = cand
-                break
-    flags = 0
-    # in-wave pipelined kernel (csrc/conv_kernel.h, PIPE): f16x3 3x3 launches with a plain input whose two halo tiles fit
-    halo9 = ((TH - 1) * IS + key[3]) * ((TW - 1) * IS + key[4])
-    # (fused BatchNorm backward: the ReLU mask as sign bits, or recomputed from the raw tensor - not read from an activation)
-    bnbwd_ok = in_bnbwd is None or pipe_fused
-    # ... on a register tile csrc/conv_pipe.hip instantiates; any other tile stays on conv_mfma_kernel (same LDS tile, same sums)
-    pipe = (PIPE_CONV and ws is None and split == 3 and len(taps) == 9 and kc == 1 and bnbwd_ok and halo9 <= 576
-            and (2 * halo9 + 1) * 80 <= PIPE_MAX_LDS and Cin >= PIPE_MIN_CIN and (MT, NT) in PIPE_TILES)
-    if pipe:
-        flags |= CONV_PIPE
-    # its 16x16x32 form (conv_kernel.h, M16): the (3, 2) register tile, at most eight staging items per plane
-    m16 = pipe and PIPE_M16 and in_bnbwd is None and (MT, NT) == (3, 2) and halo9 <= 512 and IS == 1
-    if m16:
-        flags |= CONV_M16
-    # whole-pixel staging of the 32-channel fused data gradient: on the register tiles compiled for it, on conv_mfma_kernel
-    c32 = c32 and ws is None and not pipe and kc == 1 and (MT, NT) in C32_PLANE_TILES
-    if c32:
-        flags |= CONV_CK32
-    if ws is not None:
-        flags |= CONV_WS | ({1: 0, 2: 1, 4: 2}[WC] << 8)
-    if in_affine is not None:
-        flags |= IN_AFFINE_RELU
-    if in_presplit:
-        assert split == 3 and in_affine is None and in_bnbwd is None, "f16 pair input: f16x3 mode, plain input"
-        flags |= IN_PRESPLIT
-    if side_presplit:
-        assert split == 3 and in_bnbwd is not None, "f16 pair side output: fused BatchNorm-backward data gradient in the f16x3 mode"
-        flags |= SIDE_PRESPLIT
-    if epi_affine is not None:
-        flags |= EPI_AFFINE
-    if epi_add is not None:
-        flags |= EPI_ADD
-        assert epi_add.shape == out.shape
-    if relu:
-        flags |= EPI_RELU
+    assert not in_presplit or (split == 3 and in_affine is None and in_bnbwd is None), "f16 pair input: f16x3 mode, plain input"
+    assert not side_presplit or (split == 3 and in_bnbwd is not None), "f16 pair side output: fused BatchNorm-backward data gradient in the f16x3 mode"
+    assert epi_add is None or epi_add.shape == out.shape
     # sign masks (uint32 words, 32 channels each, written by bn_apply(mask=True)) replace the activated tensors where given
     in_mask = in_bnbwd[4] if (in_bnbwd is not None and len(in_bnbwd) > 4) else None
     bn_mask = bn_bwd[3] if (bn_bwd is not None and len(bn_bwd) > 3) else None
@@ -417,42 +394,38 @@ def _conv_launch(x, wpk, out, Cout, taps, IS, OS, ooy, oox, OH, OW, in_affine, e
         if mk is not None:
             assert mk.dtype == torch.int32 and mk.numel() == ref.numel() // 32, "sign mask shape"
     if in_bnbwd is not None:
-        flags |= IN_BNBWD
         assert in_affine is None and side is not None and side[0].shape == x.shape
         assert in_bnbwd[0].shape == x.shape and (in_bnbwd[1] is None or in_bnbwd[1].shape == x.shape)
-    stats = None
     if bn_bwd is not None:
-        want_stats = True
-        flags |= EPI_BNBWD
         assert bn_bwd[0].shape == out.shape and (bn_bwd[1] is None or bn_bwd[1].shape == out.shape)
-    if wlen is not None:
-        flags |= EPI_WMASK
-    if want_stats:
-        flags |= EPI_STATS
-        ntile = (4 // WC) * B * (-(-OH // TH)) * (-(-OW // TW))      # one partial row per wave (per pixel group of waves)
-        stats = torch.empty(ntile, Cout, 2, device=x.device, dtype=torch.float32)
-    call("spk_conv_mfma" if wlen is None else "spk_conv_mfma_len", ptr(x), ptr(wpk), ptr(out),
-         ptr(in_affine[0]) if in_affine else None, ptr(in_affine[1]) if in_affine else None,
-         ptr(epi_affine[0]) if epi_affine else None, ptr(epi_affine[1]) if epi_affine else None,
-         ptr(epi_add),
-         ptr(in_bnbwd[0]) if in_bnbwd else None, ptr(in_bnbwd[1]) if (in_bnbwd and in_mask is None) else None,
-         ptr(in_bnbwd[2]) if in_bnbwd else None, ptr(in_bnbwd[3]) if in_bnbwd else None,
-         ptr(in_mask), ptr(bn_mask), ptr(add_mask),
-         ptr(side[0]) if side else None, ptr(side[1]) if side else None,
-         ptr(bn_bwd[0]) if bn_bwd else None, ptr(bn_bwd[1]) if (bn_bwd and bn_mask is None) else None,
-         ptr(bn_bwd[2]) if bn_bwd else None, ptr(stats), B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, IS, OS, ooy, oox, len(taps),
-         _iarr(dys), _iarr(dxs), _iarr(tws), TH, TW, MT, NT, kc, ips, flags, split, ptr(in_amax), ptr(out_amax), ptr(side_amax),
-         *(() if wlen is None else (ptr(wlen),)), stream(),
-         label=(("conv_ws_kernel<%d,%d,%d,%s,%d>" % (MT, NT, WC, "true" if in_bnbwd is not None else "false", split)) if ws is not None
-                else ("conv_pipe_kernel<%d,%d,false,false%s>" % (MT, NT, (",true,true" if in_presplit else ",false,true") if m16 else (",true" if in_presplit else "")) if in_bnbwd is None
-                      else "conv_pipe_kernel<%d,%d,true,true>" % (MT, NT)) if pipe
-                else "conv_mfma_kernel<%d,%d,%s,%d>" % (MT, NT, "true" if in_bnbwd is not None else "false", split)) + (
-             " C%d %dx%d%s" % (Cout, OH, OW, " plane32" if c32 else "") if LABEL_SHAPES else ""),
+    stats = None
+    if p.flags & EPI_STATS:
+        rows = p.stats_rows if p.stats_rows is not None else hip.lib().spk_conv1x1_stream_rows(p.nblocks, Cin)
+        stats = torch.empty(rows, Cout, 2, device=x.device, dtype=torch.float32)
+    in_aff = (ptr(in_affine[0]), ptr(in_affine[1])) if in_affine else (None, None)
+    bn_raw, bn4 = (ptr(bn_bwd[0]), ptr(bn_bwd[2])) if bn_bwd else (None, None)
+    if p.entry == "spk_conv3x3_c32_stream":
+        args = (*in_aff, ptr(stats), B, IH, IW, p.flags, ptr(in_amax), ptr(out_amax), p.nblocks)
+    elif p.entry == "spk_conv1x1_stream":
+        args = (*in_aff, ptr(epi_add), ptr(add_mask), bn_raw, ptr(bn_mask), bn4, ptr(stats), B * IH * IW, Cin, p.flags,
+                ptr(in_amax), ptr(out_amax), p.nblocks)
+    else:
+        args = (*in_aff, ptr(epi_affine[0]) if epi_affine else None, ptr(epi_affine[1]) if epi_affine else None, ptr(epi_add),
+                ptr(in_bnbwd[0]) if in_bnbwd else None, ptr(in_bnbwd[1]) if (in_bnbwd and in_mask is None) else None,
+                ptr(in_bnbwd[2]) if in_bnbwd else None, ptr(in_bnbwd[3]) if in_bnbwd else None,
+                ptr(in_mask), ptr(bn_mask), ptr(add_mask), ptr(side[0]) if side else None, ptr(side[1]) if side else None,
+                bn_raw, ptr(bn_bwd[1]) if (bn_bwd and bn_mask is None) else None, bn4, ptr(stats),
+                B, IH, IW, Cin, OH, OW, OHf, OWf, Cout, p.IS, OS, ooy, oox, len(taps),
+                _iarr([t[0] for t in taps]), _iarr([t[1] for t in taps]), _iarr([t[2] for t in taps]),
+                p.TH, p.TW, p.MT, p.NT, p.kc, p.ips, p.flags, split, ptr(in_amax), ptr(out_amax), ptr(side_amax),
+                *(() if wlen is None else (ptr(wlen),)))
+    ips, eff_is = p.ips, p.IS      # (a strided 1x1 reads every ips-th pixel at an effective stride of 1)
+    call(p.entry, ptr(x), ptr(wpk), ptr(out), *args, stream(), label=p.label,
          flops=2.0 * B * OH * OW * Cout * Cin * len(taps),
          # algorithmic bytes: the input pixels this launch reads (all of them for a stride-1 / full-tap launch), the output it
          # writes, and every fused side stream once: shortcut add, raw + side draw of the fused BatchNorm backward, raw of the
          # BatchNorm whose backward statistics are reduced, the 1-bit masks; packed weights
-         nbytes=4.0 * (B * (IH // ips) * (IW // ips) * Cin * (min(1.0, len(taps) * OH * OW / max(1, (IH // ips) * (IW // ips))) if IS == 1 and OS > 1 else 1.0)
+         nbytes=4.0 * (B * (IH // ips) * (IW // ips) * Cin * (min(1.0, len(taps) * OH * OW / max(1, (IH // ips) * (IW // ips))) if eff_is == 1 and OS > 1 else 1.0)
                        + B * OH * OW * Cout * (1 + (1 if epi_add is not None else 0) + (1 if bn_bwd is not None else 0))
                        + (2 * x.numel() if in_bnbwd is not None else 0)
                        + (x.numel() / 32 if in_mask is not None else 0) + (B * OH * OW * Cout / 32) * ((bn_mask is not None) + (add_mask is not None))
@@ -535,10 +508,7 @@ def conv_fwd(x, wpk, Cout, ksize, stride, in_affine=None, epi_affine=None, epi_a
     OH, OW = conv_out_hw(IH, IW, ksize, stride)
     if out is None:
         out = torch.empty(B, OH, OW, Cout, device=x.device, dtype=torch.float32)
-    if ksize == 3:
-        taps = [(kh - 1, kw - 1, kh * 3 + kw) for kh in range(3) for kw in range(3)]
-    else:
-        taps = [(0, 0, 0)]
+    taps = FWD_TAPS if ksize == 3 else [(0, 0, 0)]
     st = _conv_launch(x, wpk, out, Cout, taps, stride, 1, 0, 0, OH, OW, in_affine, epi_affine, epi_add, relu, stats,
                       split=split_for(ksize), in_amax=in_amax, out_amax=out_amax, wlen=wlen)
     return out, st
@@ -613,9 +583,10 @@ _ws_cache = {}
 _ws_retired = []
 
 
-def _workspace(nbytes, device):
-    """Scratch buffer per (device, launch stream): kernels on different streams never share one."""
-    key = (str(device), torch.cuda.current_stream().cuda_stream)
+def _workspace(nbytes, device, name=None):
+    """Scratch buffer per (purpose, device, launch stream): kernels on different streams never share one, and a named purpose has
+    a buffer of its own (a GEMM may run between a weight gradient and its slab reduce)."""
+    key = (name, str(device), torch.cuda.current_stream().cuda_stream)
     w = _ws_cache.get(key)
     if w is None or w.numel() * 4 < nbytes:
         if w is not None:
@@ -625,16 +596,53 @@ def _workspace(nbytes, device):
     return w
 
 
-def _workspace_named(name, nbytes, device):
-    """like _workspace, with its own buffer per purpose (a GEMM may run between a weight gradient and its slab reduce)"""
-    key = (name, str(device), torch.cuda.current_stream().cuda_stream)
-    w = _ws_cache.get(key)
-    if w is None or w.numel() * 4 < nbytes:
-        if w is not None:
-            _ws_retired.append(w)
-        w = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
-        _ws_cache[key] = w
-    return w
+def _plan_wgrad(B, Cin, OH, OW, Cout, ksize, stride, split, in_affine=False, dy_presplit=False):
+    """Which weight-gradient family runs, on which tile, into how many slabs, under which label (as _plan_conv: no tensor, no
+    device, no library call)."""
+    TH, TW, WN = tiling.wgrad_tile(OH, OW, Cin, Cout, ksize, stride, split=split)
+    f16_3x3 = split == 3 and ksize == 3
+    if C32M16 and f16_3x3 and WN == 1 and dy_presplit:
+        TH, TW, WN = tiling.c32m16_tile(OH, OW, Cin, Cout, ksize, stride) or (TH, TW, WN)      # the 32-channel-group 16x16x32 kernel has its own tile rule
+    nreg = B * (-(-OH // TH)) * (-(-OW // TW))
+    halo = ((TH - 1) * stride + ksize) * ((TW - 1) * stride + ksize)
+    wv, hs = 4 // WN, 4 if halo <= 128 else 5
+    nst = -(-(TH * TW) // 16)                                   # k-steps of the tile: one or two per wave group
+    cg = 0
+    # producer / consumer kernel (csrc/conv_wgrad_split.hip: conv_wgrad_ws_kernel): f16x3 3x3 launches whose two LDS slots fit
+    if WS_WGRAD and f16_3x3 and not dy_presplit and 2 * (halo * 192 + nst * 16 * (WN * 192 + (64 if WN > 1 else 0))) <= 160 * 1024:
+        family, label = "ws", "conv_wgrad_ws_kernel<%d,%d,%d,%d>" % (ksize * ksize, wv, WN, hs)
+    # in-wave pipelined kernel (csrc/conv_wgrad_pipe.hip): two planar LDS slots of 64-byte rows
+    elif (PIPE_WGRAD and f16_3x3 and not dy_presplit and nst % wv == 0 and nst // wv in (1, 2)
+          and 2 * (2 * halo * 64 + 2 * WN * nst * 16 * 64) + 128 <= PIPE_MAX_LDS):
+        family, label = "pipe", "conv_wgrad_pipe_kernel<%d,%d,%d,%d>" % (wv, WN, hs, nst // wv)
+    # 3x3, f16x3: 2 input-channel groups x 2 output-channel groups of waves (csrc/conv_wgrad_wm.hip) ...
+    elif (GROUPED_3X3 and f16_3x3 and WN == 2 and Cin % 64 == 0 and Cout % 64 == 0 and halo <= 112 and TH * TW <= 64
+          and halo * 384 + nst * 16 * 448 <= 80 * 1024):
+        # ... with a pair-tensor dy in the 16x16x32 form, X pixel pitch 416 B (csrc/conv_wgrad_wm16.hip)
+        m16 = WM16 and dy_presplit and halo * 416 + 2 * -(-(TH * TW) // 32) * 32 * 256 <= 80 * 1024
+        family, label, cg = ("wm16", "conv_wgrad_wm16_kernel", 2) if m16 else ("wm", "conv_wgrad_wm_kernel", 2)
+    # ... and that kernel in its 32-channel-group layout (the first layer): four waves split the k-steps and fold at the end of the block
+    elif (C32M16 and f16_3x3 and WN == 1 and dy_presplit and halo <= 192
+          and halo * 192 + 2 * -(-(TH * TW) // 32) * 32 * 128 <= 80 * 1024):
+        family, label = "c32m16", "conv_wgrad_c32m16_kernel"
+    else:
+        family = "split" if split else "f32"
+        label = ("conv_wgrad_split_kernel<%d,%d,%d,%d,%d>" % (ksize * ksize, wv, WN, split, hs) if split
+                 else "conv_wgrad_kernel<%d,%d,%d>" % (ksize * ksize, wv, WN))
+    # 1x1, f16x3: conv_wgrad_1x1_kernel with 2 or 4 input-channel groups per block (csrc/conv_wgrad_1x1.hip)
+    if GROUPED_1X1 and split == 3 and ksize == 1 and WN in (2, 4) and TH * TW <= 64:
+        cg = 4 if Cin % 128 == 0 else (2 if Cin % 64 == 0 else 0)
+        if cg and nst * 16 * (cg * 192 + WN * 192 + 64) > 80 * 1024:
+            cg = 2 if cg == 4 else 0
+        if cg:
+            family, label = "1x1", "conv_wgrad_1x1_kernel<%d,%d,%d>" % (wv, WN, cg)
+    nsplit = min(nreg, tiling.wgrad_nsplit(nreg, Cin, Cout, WN, WS_WGRAD_BLOCKS if family == "ws" else (GROUPED_1X1_BLOCKS if cg else None),
+                                           cin_groups=cg or 1))
+    flags = ((IN_AFFINE_RELU if in_affine else 0) | (CONV_WS if family == "ws" else 0) | (CONV_PIPE if family == "pipe" else 0)
+             | (WGRAD_GROUPS | ({2: 1, 4: 2}[cg] << 12) if cg else 0) | (DY_PRESPLIT if dy_presplit else 0)
+             | (hip.WGRAD_NOSHIFT if family in ("wm", "wm16") and not WM_SHIFT else 0)
+             | (hip.WGRAD_M16 if family in ("wm16", "c32m16") else 0))
+    return WgradPlan(TH, TW, WN, family, cg, nsplit, flags, label + (" C%d %dx%d" % (Cout, OH, OW) if LABEL_SHAPES else ""))
 
 
 def conv_wgrad(x, dy, dw, ksize, stride, in_affine=None, accumulate=False, dy_amax=None, x_amax=None, dy_presplit=False):
@@ -653,61 +661,15 @@ def conv_wgrad(x, dy, dw, ksize, stride, in_affine=None, accumulate=False, dy_am
     if tiling.AUTOTUNE and wkey not in tiling.FORCE_WGRAD and PROFILE is None and not torch.cuda.is_current_stream_capturing():
         tiling.FORCE_WGRAD[wkey] = tiling._wgrad_tile(*wkey)      # placeholder: stops the recursion below
         _autotune_wgrad(wkey, x, dy, ksize, stride, in_affine, dy_amax, x_amax, dy_presplit)
-    TH, TW, WN = tiling.wgrad_tile(OH, OW, Cin, Cout, ksize, stride, split=split)
-    if C32M16 and split == 3 and ksize == 3 and WN == 1 and dy_presplit:
-        TH, TW, WN = tiling.c32m16_tile(OH, OW, Cin, Cout, ksize, stride) or (TH, TW, WN)      # the 32-channel-group 16x16x32 kernel has its own tile rule
-    nreg = B * (-(-OH // TH)) * (-(-OW // TW))
-    # producer / consumer kernel (csrc/conv_wgrad_split.hip: conv_wgrad_ws_kernel): f16x3 3x3 launches whose two LDS slots fit
-    halo = ((TH - 1) * stride + ksize) * ((TW - 1) * stride + ksize)
-    wgws = (WS_WGRAD and split == 3 and ksize == 3 and not dy_presplit
-            and 2 * (halo * 192 + -(-(TH * TW) // 16) * 16 * (WN * 192 + (64 if WN > 1 else 0))) <= 160 * 1024)
-    # in-wave pipelined kernel (csrc/conv_wgrad_pipe.hip): two planar LDS slots of 64-byte rows
-    nst = -(-(TH * TW) // 16)                                   # k-steps of the tile: one or two per wave group
-    wgp = (PIPE_WGRAD and not wgws and not dy_presplit and split == 3 and ksize == 3 and nst % (4 // WN) == 0 and nst // (4 // WN) in (1, 2)
-           and 2 * (2 * halo * 64 + 2 * WN * -(-(TH * TW) // 16) * 16 * 64) + 128 <= PIPE_MAX_LDS)
-    # 1x1, f16x3: conv_wgrad_1x1_kernel with 2 or 4 input-channel groups per block (csrc/conv_wgrad_1x1.hip)
-    cg = 0
-    if GROUPED_1X1 and split == 3 and ksize == 1 and WN in (2, 4) and TH * TW <= 64:
-        cg = 4 if Cin % 128 == 0 else (2 if Cin % 64 == 0 else 0)
-        if cg and -(-(TH * TW) // 16) * 16 * (cg * 192 + WN * 192 + 64) > 80 * 1024:
-            cg = 2 if cg == 4 else 0
-    # 3x3, f16x3: 2 input-channel groups x 2 output-channel groups of waves (csrc/conv_wgrad_wm.hip)
-    wm = (GROUPED_3X3 and not wgws and not wgp and split == 3 and ksize == 3 and WN == 2 and Cin % 64 == 0 and Cout % 64 == 0
-          and halo <= 112 and TH * TW <= 64 and halo * 384 + -(-(TH * TW) // 16) * 16 * 448 <= 80 * 1024)
-    wm16 = wm and WM16 and dy_presplit and halo * 416 + 2 * -(-(TH * TW) // 32) * 32 * 256 <= 80 * 1024     # X pixel pitch 416 B (csrc/conv_wgrad_wm16.hip)
-    # ... and the same kernel in its 32-channel-group layout (the first layer): four waves split the k-steps and fold at the end of the block
-    c32m16 = (C32M16 and not wm and not wgws and not wgp and split == 3 and ksize == 3 and WN == 1 and dy_presplit and halo <= 192
-              and halo * 192 + 2 * -(-(TH * TW) // 32) * 32 * 128 <= 80 * 1024)
-    if wm:
-        cg = 2
-    nsplit = min(nreg, tiling.wgrad_nsplit(nreg, Cin, Cout, WN, WS_WGRAD_BLOCKS if wgws else (GROUPED_1X1_BLOCKS if cg else None),
-                                           cin_groups=cg or 1))
-    nslab = nsplit
-    nbytes = hip.lib().spk_conv_wgrad_workspace(nslab, ksize, Cin, Cout)
+    p = _plan_wgrad(B, Cin, OH, OW, Cout, ksize, stride, split, in_affine is not None, dy_presplit)
+    nbytes = hip.lib().spk_conv_wgrad_workspace(p.nsplit, ksize, Cin, Cout)
     ws = _workspace(nbytes, x.device)
-    flags = (IN_AFFINE_RELU if in_affine is not None else 0) | (CONV_WS if wgws else 0) | (CONV_PIPE if wgp else 0)
-    if cg:
-        flags |= WGRAD_GROUPS | ({2: 1, 4: 2}[cg] << 12)
-    if dy_presplit:
-        flags |= DY_PRESPLIT
-    if wm and not WM_SHIFT:
-        flags |= hip.WGRAD_NOSHIFT
-    if wm16 or c32m16:
-        flags |= hip.WGRAD_M16
     call("spk_conv_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws),
          ptr(in_affine[0]) if in_affine else None, ptr(in_affine[1]) if in_affine else None,
-         B, IH, IW, Cin, OH, OW, Cout, ksize, stride, TH, TW, WN, nsplit, flags, 1 if accumulate else 0, split,
-         ptr(dy_amax) if split == 3 else None, ptr(x_amax) if split == 3 else None, stream(),
-         label=("conv_wgrad_wm16_kernel" if wm16 else "conv_wgrad_c32m16_kernel" if c32m16 else "conv_wgrad_wm_kernel" if wm
-         else ("conv_wgrad_1x1_kernel<%d,%d,%d>" % (4 // WN, WN, cg)) if cg
-         else ("conv_wgrad_ws_kernel<%d,%d,%d,%d>" % (ksize * ksize, 4 // WN, WN, 4 if halo <= 128 else 5)) if wgws
-         else ("conv_wgrad_pipe_kernel<%d,%d,%d,%d>" % (4 // WN, WN, 4 if halo <= 128 else 5, nst // (4 // WN))) if wgp
-         else ("conv_wgrad_split_kernel<%d,%d,%d,%d,%d>" % (
-             ksize * ksize, 4 // WN, WN, split, 4 if ((TH - 1) * stride + ksize) * ((TW - 1) * stride + ksize) <= 128 else 5)) if split
-         else "conv_wgrad_kernel<%d,%d,%d>" % (ksize * ksize, 4 // WN, WN)) + (
-             " C%d %dx%d" % (Cout, OH, OW) if LABEL_SHAPES else ""),
+         B, IH, IW, Cin, OH, OW, Cout, ksize, stride, p.TH, p.TW, p.WN, p.nsplit, p.flags, 1 if accumulate else 0, split,
+         ptr(dy_amax) if split == 3 else None, ptr(x_amax) if split == 3 else None, stream(), label=p.label,
          flops=2.0 * B * OH * OW * Cout * Cin * ksize * ksize, nbytes=4.0 * (x.numel() + dy.numel() + nbytes / 4))
-    call("spk_wgrad_reduce", ptr(ws), ptr(dw), nslab, ksize, Cin, Cout, 1 if accumulate else 0, stream())
+    call("spk_wgrad_reduce", ptr(ws), ptr(dw), p.nsplit, ksize, Cin, Cout, 1 if accumulate else 0, stream())
     return dw
 
 
@@ -967,7 +929,7 @@ def gemm(A, Bm, M, N, K, sam, sak, sbk, sbn, bias=None, out=None, alpha=1.0, acc
     tensor (ldc = out.stride(0) > N)."""
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    ws = _workspace_named("gemm", hip.lib().spk_gemm_workspace(M, N, K), A.device)
+    ws = _workspace(hip.lib().spk_gemm_workspace(M, N, K), A.device, name="gemm")
     call("spk_gemm_f32", ptr(A), ptr(Bm), _ptr_rows(out), ptr(bias), M, N, K, sam, sak, sbk, sbn, out.stride(0), float(alpha),
          1 if accumulate else 0, ptr(ws), stream(), label="gemm_f32_kernel", flops=2.0 * M * N * K)
     return out

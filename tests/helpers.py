@@ -160,7 +160,7 @@ def conv_launch_key(name, a, label):
         f = [("Cin", a["Cin"]), ("Cout", a["Cout"]), ("k", a["ksize"]), ("IS", a["stride"]), ("TH", a["TH"]), ("TW", a["TW"]),
              ("WN", a["WN"]), ("flags", hex(a["flags"])), ("split", a["split"]),
              ("ragH", int(a["OH"] % a["TH"] != 0)), ("ragW", int(a["OW"] % a["TW"] != 0))]
-    elif name == "spk_conv3x3_c32_stream":          # 8 x 16 pixel tiles (ops._conv3x3_c32_stream)
+    elif name == "spk_conv3x3_c32_stream":          # 8 x 16 pixel tiles (ops._plan_conv)
         f = [("Cin", 32), ("Cout", 32), ("k", 3), ("flags", hex(a["flags"])),
              ("ragH", int(a["H"] % 8 != 0)), ("ragW", int(a["W"] % 16 != 0))]
     elif name == "spk_conv1x1_stream":              # pixel-linear tiles over B * H * W: the ragged tail depends on B

@@ -267,6 +267,10 @@ def test_default_chooser_returns_tiles_outside_the_pipelined_set():
     src = open(ops.__file__.replace("ops.py", "csrc/conv_pipe.hip")).read()
     built = src.split("spk_launch_conv_pipe(")[1]
     assert sorted(ops.PIPE_TILES) == sorted((int(m), int(n)) for m, n in __import__("re").findall(r"CASE\((\d), (\d)\)", built))
+    # the plan of that launch (64 input channels: PIPE_MIN_CIN is not what decides it) stays on conv_mfma_kernel
+    p = ops._plan_conv(1, 9, 11, 64, 9, 11, 9, 11, 32, ops.FWD_TAPS, 1, 1, 0, 0, 3, False)
+    assert ops.PIPE_CONV and 64 >= ops.PIPE_MIN_CIN and (p.TH, p.TW, p.MT, p.NT) == (9, 11, 1, 1)
+    assert not p.flags & ops.CONV_PIPE and p.label.startswith("conv_mfma_kernel<1,1,"), p
 
 
 def test_forced_weight_gradient_tiles_satisfy_the_c_abi_and_the_restatement_covers_their_shapes():
