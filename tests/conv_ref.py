@@ -1,7 +1,8 @@
 """fp64 restatement, engineered inputs, operand-mode emulations and per-element error bounds for the convolution kernels
 (csrc/conv_kernel.h with conv_mfma / conv_split / conv_pipe.hip, pack.hip and the conv_wgrad*.hip family) - test infrastructure
-only.  (The two streaming kernels, conv1x1_stream.hip and conv3x3_c32_stream.hip, have their own equality tests against the general
-kernel in tests/test_kernels_gpu.py; here they appear only in the absmax hand-off tests.)
+only.  The two streaming kernels, conv1x1_stream.hip and conv3x3_c32_stream.hip, are the same tap-table launches with their own
+tiling of the pixel axis and their own statistics mechanism: the last part of this file holds their statistics chains, the
+partition of the pixels into partial rows and their case lists (tests/test_conv_stream_edges_cpu.py and _gpu.py).
 
 tests/test_conv_edges_cpu.py shows that the restatement agrees with F.conv2d and autograd in float64, that float32 torch on the
 CPU stays inside the `f32` bound, that the numpy emulation of every operand mode stays inside that mode's representation term
@@ -27,6 +28,7 @@ Everything here is NCHW on the CPU; the GPU file converts.  Rules:
   * integer inputs (x in -2 .. 2, w in -1 .. 1, integer vectors): every operand has one term in every mode and every partial sum
     is an integer below sum|a w|, so wherever that stays below 2^24 (exact_ok) the comparison is `==`.
 """
+import functools
 import math
 
 import numpy as np
@@ -524,3 +526,231 @@ def wgrad_tile_violations(fam, tile, in_hw, stride):
         if TH * TW > (256 // (8 * WN)) * 4:
             bad.append("dY prefetch window")
     return bad
+
+
+# ---- the two streaming kernels (csrc/conv1x1_stream.hip, csrc/conv3x3_c32_stream.hip) ------------------------------------------
+# Both are one tap-table launch (fwd / dgrad1 above) in the f16x3 mode: the outputs are Conv.finish(3, ...).  What is their own:
+# which pixels form a tile, which tiles a persistent block walks, and how the statistics are reduced.
+#
+# Statistics, conv1x1_stream_kernel (epilogue, read line by line): a lane holds one output channel of 2 row tiles x 16 accumulator
+# registers = 32 pixels of a tile.  `float ts = 0, tq = 0` per tile; every live pixel does `ts += val` (`ts += dz`) and
+# `tq += val * val` (`tq += dz * ((rw - bmu) * bis)`): 32 float32 additions into each, and the square / product is a plain C
+# expression - a rounding of its own unless the compiler contracts it, so the bound counts it: 33.  (xhat = (rw - bmu) * bis has two
+# more roundings: bnbwd_stats_ref's ex.)  Then `s_sum += (double)ts` across the tiles of the block, the fold of the lane pair
+# l, l + 32 by __shfl_xor on the doubles (2^-53: inside SLACK), and ONE cast `(float)s_sum` of the row.
+# conv3x3_c32_stream_kernel: a lane holds one channel of 16 pixels of a tile (2 tile rows of its wave x 8 columns); `ts += val`
+# and `tq = __builtin_fmaf(val, val, tq)`: 16 additions, the square inside the fused operation; the same fp64 tail and cast.
+# The cast rounds the ROW'S TOTAL: its term is u |row sum| per row and statistic, stated on the row (stream_stats), not folded
+# into the per-element chain - |row sum| can be far below sum|v|, and a per-element chain would have to be 1 larger for every
+# row an element is not even in.
+STREAM_CHAINS = {"1x1": (32, 33), "3x3": (16, 16)}       # (additions into the sum, roundings into the sum of squares / products)
+
+
+def stream1_tile(C):
+    """conv1x1_stream_kernel<C>: (TP pixels per tile, PPP pixels per staging pass, WM pixel wave groups = partial rows per block)"""
+    return 8192 // C, 1024 // C, 128 // C
+
+
+def stream1_rows(P, C, G):
+    """partial-statistics row of every pixel of the flattened [B H W] axis on a grid of G blocks: tile p / TP belongs to block
+    tile % G, pixel wave group (p % TP) / 64 -> (row [P], number of rows)"""
+    TP, _, WM = stream1_tile(C)
+    p = torch.arange(P)
+    return ((p // TP) % G) * WM + (p % TP) // 64, G * WM
+
+
+def stream3_tiles(B, H, Wd):
+    return B * (-(-H // 8)) * (-(-Wd // 16))
+
+
+def stream3_rows(B, H, Wd, G):
+    """conv3x3_c32_stream_kernel: tiles of 8 x 16 pixels numbered x fastest, then y, then image; VIRTUAL block tile % G (the XCD
+    band permutation renames blocks, tile sets and rows go by the virtual id); wave (y % 8) / 2 -> (row [B H W], number of rows)"""
+    ty, tx = -(-H // 8), -(-Wd // 16)
+    b, y, x = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(Wd), indexing="ij")
+    tile = (b * ty + y // 8) * tx + x // 16
+    return ((tile % G) * 4 + (y % 8) // 2).reshape(-1), 4 * G
+
+
+def stream_stats(v, b, rows, nrows, chains, bnbwd=None):
+    """the partial rows of a streaming kernel's statistics -> (value, bound, magnitude), each [nrows][C][2]: per row stats_ref
+    (bnbwd = (raw, mask, bn4): bnbwd_stats_ref) over the row's own pixels with the chain of the kernel, plus the cast of the row:
+    u (|row sum| + its bound).  magnitude: sum |terms| of the row (integer inputs: exact while it stays below 2^24).  A row
+    without pixels (a wave group past the tail) is 0, exactly.  The fp64 sum of the rows a test forms has the sum of the bounds."""
+    C = v.shape[1]
+
+    def px(t):
+        return t.permute(0, 2, 3, 1).reshape(-1, C)
+    vp, bp = px(v), px(b)
+    if bnbwd is not None:
+        rawp, maskp = px(bnbwd[0]), px(bnbwd[1])
+    val, bnd, mag = (torch.zeros(nrows, C, 2, dtype=torch.float64) for _ in range(3))
+
+    def img(t, idx):
+        return t[idx].t().reshape(1, C, -1, 1)
+    for r in range(nrows):
+        idx = torch.nonzero(rows == r).reshape(-1)
+        if idx.numel() == 0:
+            continue
+        vr, br = img(vp, idx), img(bp, idx)
+        if bnbwd is None:
+            s0, b0, _, _ = stats_ref(vr, br, chains[0])
+            _, _, s1, b1 = stats_ref(vr, br, chains[1])
+            m0, m1 = vr.abs().sum((0, 2, 3)), (vr * vr).sum((0, 2, 3))
+        else:
+            rr, mr = img(rawp, idx), img(maskp, idx)
+            s0, b0, _, _ = bnbwd_stats_ref(vr, br, rr, mr, bnbwd[2], chains[0])
+            _, _, s1, b1 = bnbwd_stats_ref(vr, br, rr, mr, bnbwd[2], chains[1])
+            xh = (rr.double() - v4(bnbwd[2][0])) * v4(bnbwd[2][1])
+            m0, m1 = (vr * mr).abs().sum((0, 2, 3)), (vr * mr * xh).abs().sum((0, 2, 3))
+        val[r, :, 0], val[r, :, 1] = s0, s1
+        bnd[r, :, 0], bnd[r, :, 1] = b0 + U * (s0.abs() + b0), b1 + U * (s1.abs() + b1)
+        mag[r, :, 0], mag[r, :, 1] = m0, m1
+    return val, bnd, mag
+
+
+def stream1(x, w, transpose=False, in_affine=None):
+    """the launch of the streaming 1x1 kernel on a C -> C weight tensor [C][C][1][1]: fwd(), or - transpose - the stride-1 data
+    gradient dgrad1() (the same single tap, the matrix transposed: what pack_conv_weight(transpose=True) hands the kernel), with
+    any staging the entry accepts"""
+    return fwd(x, w.permute(1, 0, 2, 3) if transpose else w, 1, 1, in_affine=in_affine)
+
+
+# -- case lists shared by the CPU and the GPU file
+STREAM1_C = (32, 64, 128)
+STREAM1_BATCH = (3, 5, 7)         # a real batch: image borders inside a tile (a 1x1 convolution must not see them)
+
+
+def stream1_pixels(C):
+    """pixel counts at every boundary of the tiling: one pixel; one short of a staging pass; the last row tile of a tile empty,
+    holding one pixel, one short of full; exactly a tile; a tile and a pixel; two tiles, a staging pass and three pixels; three
+    tiles (a grid of 2: block 0 walks two tiles, block 1 one) - and the batch of STREAM1_BATCH"""
+    TP, PPP, _ = stream1_tile(C)
+    return [1, PPP - 1, TP - 32, TP - 31, TP - 1, TP, TP + 1, 2 * TP + PPP + 3, 3 * TP, int(np.prod(STREAM1_BATCH))]
+
+
+def stream1_layout(P):
+    """P pixels as B x H x W: three images where 3 divides P (else two, else one), H the largest divisor of the rest below its root"""
+    if P == int(np.prod(STREAM1_BATCH)):
+        return STREAM1_BATCH
+    B = 3 if P % 3 == 0 else (2 if P % 2 == 0 else 1)
+    n = P // B
+    H = max(d for d in range(1, int(math.isqrt(n)) + 1) if n % d == 0)
+    return B, H, n // H
+
+
+def stream1_grids(P, C):
+    """ops.STREAM_1X1_BLOCKS of a case: 1, 2 and the tile count (the planner clamps a grid to the tile count)"""
+    nt = -(-P // stream1_tile(C)[0])
+    return sorted({min(g, nt) for g in (1, 2, nt)})
+
+
+def stream1_sweep_pixels(C):
+    TP, PPP, _ = stream1_tile(C)
+    return 2 * TP + PPP + 3
+
+
+# the variants: (input, add, add mask, statistics, BatchNorm backward).  input: "f32" | "aff" (fused BatchNorm + ReLU) | "pair"
+# (f16 pair tensor); BatchNorm backward: None | "raw" (mask recomputed) | "bits".  A variant with a pair input, a mask or the
+# BatchNorm-backward statistics is a data gradient (transposed weights); the others are forwards.
+STREAM1_EPILOGUES = [(False, False, False, None), (False, False, True, None), (True, False, False, None), (True, True, False, None),
+                     (False, False, True, "raw"), (False, False, True, "bits"), (True, True, True, "bits"), (True, False, True, "raw")]
+STREAM1_VARIANTS = [(inp,) + e for inp in ("f32", "aff", "pair") for e in STREAM1_EPILOGUES]
+STREAM1_P_SWEEP = [("aff", False, False, True, None), ("pair", True, True, True, "bits")]
+# the five compile-time instances of spk_conv1x1_stream's PICK; every other variant takes the generic instance
+STREAM1_COMPILED = [("aff", False, False, True, None), ("f32", False, False, True, None), ("pair", False, False, True, "raw"),
+                    ("pair", True, True, False, None), ("pair", True, True, True, "bits")]
+
+
+def stream1_is_dgrad(variant):
+    inp, add, addmask, stats, bnb = variant
+    return inp == "pair" or addmask or bnb is not None
+
+
+def edge_bits(shape, seed):
+    """a ReLU decision [B][C][H][W] whose sign-mask words include all-zero, all-one and single-bit words (bit 0, bit 31), the
+    last pixel's last word being the single bit 31 where there are three pixels or more, and seeded words elsewhere"""
+    B, C, H, Wd = shape
+    P, nw = B * H * Wd, C // 32
+    m = (ints(seed, 0, 1, P, nw, 32) > 0)
+    pat = [torch.zeros(32, dtype=torch.bool), torch.ones(32, dtype=torch.bool), torch.arange(32) == 0, torch.arange(32) == 31]
+    for i in range(min(P, 4) * nw):
+        m.view(-1, 32)[i] = pat[i % 4]
+    if P >= 3:
+        m[P - 1, nw - 1] = pat[3]
+        m[P - 1, 0] = pat[3] if nw == 1 else pat[1]
+    return m.reshape(B, H, Wd, C).permute(0, 3, 1, 2).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def stream1_case(C, P, variant, exact):
+    """inputs and fp64 references of one case (computed once; grids and tests share it; never modified) -> dict"""
+    inp, add, addmask, stats, bnb = variant
+    B, H, Wd = stream1_layout(P)
+    seed = 700 + C + 7 * P
+    c = {"shape": (B, H, Wd), "dgrad": stream1_is_dgrad(variant)}
+    c["x"], c["w"] = conv_inputs(seed, B, C, C, H, Wd, 1, exact)
+    c["ia"] = vec_affine(seed + 2, C, exact) if inp == "aff" else None
+    c["add"] = tensor(seed + 4, exact, B, C, H, Wd) if add else None
+    c["gate"] = edge_bits((B, C, H, Wd), seed + 5) if addmask else None
+    c["conv"] = stream1(c["x"], c["w"], c["dgrad"], c["ia"])
+    c["out"] = c["conv"].finish(3, add=c["add"], add_gate=c["gate"])
+    if bnb is not None:
+        c["raw"], c["bn4"] = tensor(seed + 6, exact, B, C, H, Wd, scale=2.0, shift=0.3), vec_bn4(seed + 7, C, exact)
+        c["mask"] = edge_bits((B, C, H, Wd), seed + 11) if bnb == "bits" else mask_from_raw(c["raw"], c["bn4"][2], c["bn4"][3])
+    return c
+
+
+def stream1_stats(c, G, exact):
+    """partial rows of case c on a grid of G blocks (stream_stats; integer inputs: no element bound)"""
+    if ("stats", G) not in c:
+        v, b = c["out"]
+        rows, nrows = stream1_rows(v.shape[0] * v.shape[2] * v.shape[3], v.shape[1], G)
+        bn = (c["raw"], c["mask"], c["bn4"]) if "raw" in c else None
+        c["stats", G] = stream_stats(v, torch.zeros_like(b) if exact else b, rows, nrows, STREAM_CHAINS["1x1"], bn)
+    return c["stats", G]
+
+
+STREAM3_MAPS = [(1, 1), (1, 16), (8, 1), (8, 16), (8, 17), (9, 16), (7, 15), (9, 33), (17, 17), (25, 49)]
+STREAM3_B = (1, 2)
+STREAM3_SWEEP_MAP = (25, 49)          # 4 x 4 tiles per image: interior tiles without a bounds test, ragged edges one pixel wide
+STREAM3_GRIDS = (1, 5, 7, 8, 15, 16, 24)      # and the tile count; 8, 16, 24, 32: the XCD band permutation
+
+
+def stream3_grids(B, H, Wd):
+    """ops.STREAM_C32_BLOCKS of a case: the tile count (the default grid on a small map), and on the sweep map the grids that
+    leave some blocks a tile more than others in the two-tiles-in-flight loop"""
+    nt = stream3_tiles(B, H, Wd)
+    return sorted({g for g in STREAM3_GRIDS if g <= nt} | {nt}) if (H, Wd) == STREAM3_SWEEP_MAP else [nt]
+
+
+@functools.lru_cache(maxsize=None)
+def stream3_case(B, H, Wd, aff, exact):
+    c = {}
+    seed = 800 + 100 * B + 3 * H + Wd
+    c["x"], c["w"] = conv_inputs(seed, B, 32, 32, H, Wd, 3, exact)
+    c["ia"] = vec_affine(seed + 2, 32, exact) if aff else None
+    c["conv"] = fwd(c["x"], c["w"], 3, 1, in_affine=c["ia"])
+    c["out"] = c["conv"].finish(3)
+    return c
+
+
+def stream3_stats(c, G, exact):
+    if ("stats", G) not in c:
+        v, b = c["out"]
+        rows, nrows = stream3_rows(v.shape[0], v.shape[2], v.shape[3], G)
+        c["stats", G] = stream_stats(v, torch.zeros_like(b) if exact else b, rows, nrows, STREAM_CHAINS["3x3"])
+    return c["stats", G]
+
+
+# operand scales far apart: inputs near 2^40, weights near 2^-50 (exact power-of-two scalings of the usual inputs), and the scale
+# slot the caller hands in a loose bound 2^3 above the true maximum.  Outputs near 2^-10: normal floats.
+FAR_X, FAR_W, FAR_LOOSE = 2.0 ** 40, 2.0 ** -50, 8.0
+
+
+def far_case(C, H, Wd, k):
+    x, w = conv_inputs(900 + C + k, 2, C, C, H, Wd, k)
+    x, w = x * FAR_X, w * FAR_W
+    amax = float(x.abs().max()) * FAR_LOOSE
+    c = fwd(x, w, k, 1)
+    return x, w, amax, c.finish(3, amax=amax)
