@@ -415,7 +415,21 @@ int spk_fbank_fwd(const float* wave, const int* nsamp, const long long* utt_ids,
                   const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P, int F,
                   int snip_edges, float dither, float preemph, int remove_dc, float energy_floor, unsigned long long seed,
                   float* feats, float* log_energy, int* T_out, int Tcap, void* stream);
-/* out[f][j] = the N(0,1) draw spk_fbank_fwd adds (times dither) at position j of frame frame0 + f of utterance utt_id */
+/* compute-mfcc-feats in one launch: replaces `local/make_mfcc.sh:107,126` of the reference's recipe (feature_pre.sh:92-103,
+ * run.sh:74-85 with conf/mfcc.conf), the MFCC as restated in the reference's kaldi.py:550-650.
+ * frames per workgroup tile for these sizes (0: the tile of C + 1 rows and the DCT copy [C][F | 1] do not fit its LDS) */
+int spk_mfcc_tile_frames(int L, int S, int P, int F, int C);
+/* As spk_fbank_fwd up to the log-mel values lm[0 .. F) of a frame (the same operations in the same order; the same dither draws),
+ * then c[k] = sum_n dct[k][n] * lm[n] (n ascending) for k < C, c[k] *= lifter[k]; use_energy: c[0] = the raw log energy (floored
+ * by log(energy_floor) when > 0); htk_compat: row k - 1 gets c[k] for k >= 1, row C - 1 gets c[0] (times sqrt 2 without
+ * use_energy).  dct [C][F] and lifter [C] are device tables built by the host in fp64 (lifter: ones for cepstral_lifter 0).
+ * feats [B][C][Tcap] (time innermost, 0 for t >= T[b]), log_energy [B][Tcap] (always written), T_out[b].  1 <= C <= F <= P. */
+int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax, const float* window,
+                 const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, const float* dct,
+                 const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither, float preemph, int remove_dc,
+                 float energy_floor, int use_energy, int htk_compat, unsigned long long seed, float* feats, float* log_energy,
+                 int* T_out, int Tcap, void* stream);
+/* out[f][j] = the N(0,1) draw spk_fbank_fwd / spk_mfcc_fwd adds (times dither) at position j of frame frame0 + f of utterance utt_id */
 int spk_fbank_dither_noise(float* out /*[nframes][L]*/, long long utt_id, unsigned long long seed, int frame0, int nframes, int L,
                            void* stream);
 /* compute-vad over log_energy [B][Tcap] (T[b] frames): vad[b][t] in {0, 1} (0 past T), idx[b][0 .. count[b]) = the voiced

@@ -8,6 +8,12 @@
 // M = P/2 points of the even/odd samples plus the real-split post-pass, power, sparse mel sum, log.  The log-mel values of the
 // tile are transposed through LDS and stored as runs of FT frames per mel row ([B][F][Tcap], time innermost).
 // The host builds the window, the twiddles exp(-2 pi i k / P) and the mel weights in fp64 and passes them rounded to fp32.
+//
+// spk_mfcc_fwd (compute-mfcc-feats; reference: local/make_mfcc.sh:107,126 and kaldi.py:550-650): the same
+// kernel template, instantiated with the cepstral epilogue.  The frame pipeline up to the log-mel values is the fbank's, operation
+// for operation; a wave then keeps its F log-mels in its own FFT buffer (free once the real split has been read), and lane k sums
+// row k of the DCT (staged once per workgroup in LDS, row stride odd) over them in ascending order, applies the lifter, and the
+// energy / HTK order rules pick the output row.  The tile has C + 1 rows: the cepstra, then the log energies.
 #include "spk_common.h"
 
 namespace {
@@ -73,9 +79,16 @@ struct FbankArgs {
     float* loge;      // [B][Tcap]
     int* T_out;       // [B]
     int Tcap;
+    // cepstral epilogue (the MFCC instantiation only)
+    const float* dct;         // [C][F] DCT-II rows, row 0 = sqrt(1 / F)
+    const float* lifter;      // [C] 1 + Q / 2 sin(pi k / Q) (ones for Q == 0)
+    int C, Fp, use_energy, htk;     // Fp: row stride of the DCT copy in LDS (odd)
 };
 
-__global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
+// one tile of one utterance.  MFCC = false: the log-mel tile (fbank_kernel); true: its DCT, liftered (mfcc_kernel).  R output
+// rows of a.feats
+template <bool MFCC>
+__device__ __forceinline__ void frontend_tile(const FbankArgs& a) {
     extern __shared__ float fe_lds[];
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * a.FT;
@@ -83,10 +96,11 @@ __global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
     const long long N = min((long long)a.nsamp[b], a.Nmax);
     const int T = N > 0 ? fe_frames(N, a.L, a.S, a.snip) : 0;
     if (blockIdx.x == 0 && tid == 0) a.T_out[b] = T;
-    float* frow = a.feats + (size_t)b * a.F * a.Tcap;
+    const int R = MFCC ? a.C : a.F;
+    float* frow = a.feats + (size_t)b * R * a.Tcap;
     const int nt = min(a.FT, a.Tcap - t0);
     if (t0 >= T) {        // tile entirely past the utterance: zeros only (block-uniform)
-        for (int i = tid; i < a.F * nt; i += FE_THREADS) frow[(size_t)(i / nt) * a.Tcap + t0 + i % nt] = 0.f;
+        for (int i = tid; i < R * nt; i += FE_THREADS) frow[(size_t)(i / nt) * a.Tcap + t0 + i % nt] = 0.f;
         for (int i = tid; i < nt; i += FE_THREADS) a.loge[(size_t)b * a.Tcap + t0 + i] = 0.f;
         return;
     }
@@ -95,7 +109,8 @@ __global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
     float2* zbuf = (float2*)fe_lds;                         // [4][M]   FFT
     float* fbuf = (float*)(zbuf + FE_WAVES * M);            // [4][P]   frame samples, then power spectrum
     float* span = fbuf + FE_WAVES * a.P;                    // [span]
-    float* otile = span + a.span;                           // [F + 1][FT]: log-mel rows, then the log energies
+    float* otile = span + a.span;                           // [R + 1][FT]: feature rows, then the log energies
+    float* dct = otile + (R + 1) * a.FT;                    // [C][Fp] (MFCC only)
     const float* wv = a.wave + (size_t)b * a.Nmax;
     const long long s0 = (long long)t0 * a.S - (a.snip ? 0 : (a.L / 2 - a.S / 2));
     for (int i = tid; i < a.span; i += FE_THREADS) {
@@ -105,6 +120,8 @@ __global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
         s = s < 0 ? 0 : (s >= N ? N - 1 : s);       // only reached for N < L, which the API refuses: stay in bounds
         span[i] = wv[s];
     }
+    if constexpr (MFCC)
+        for (int i = tid; i < a.C * a.F; i += FE_THREADS) dct[(i / a.F) * a.Fp + i % a.F] = a.dct[i];
     const unsigned long long key = a.dither != 0.f ? fe_utt_key(a.seed, a.utt_ids[b]) : 0ull;
     float* fb = fbuf + w * a.P;
     float2* z = zbuf + w * M;
@@ -173,20 +190,54 @@ __global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) {
             const int lo = a.mel_lo[m], o0 = a.mel_off[m], cnt = a.mel_off[m + 1] - o0;
             float s = 0.f;
             for (int q = 0; q < cnt; ++q) s = fmaf(a.mel_w[o0 + q], fb[lo + q], s);
-            otile[m * a.FT + tl] = fe_log_floor_eps(s);
+            if constexpr (MFCC) ((float*)z)[m] = fe_log_floor_eps(s);      // z is free since the real split (F <= P floats)
+            else otile[m * a.FT + tl] = fe_log_floor_eps(s);
         }
-        if (lane == 0) otile[a.F * a.FT + tl] = fmaxf(fe_log_floor_eps(e), a.log_floor);
+        const float le = fmaxf(fe_log_floor_eps(e), a.log_floor);
+        if (lane == 0) otile[R * a.FT + tl] = le;
         wave_lds_sync();
+        if constexpr (MFCC) {
+            // cepstra: c[k] = sum_n D[k][n] lm[n] (n ascending), times the lifter; C0 replaced by the energy; HTK order: C0 last
+            const float* lm = (const float*)z;
+            for (int k = lane; k < a.C; k += 64) {
+                const float* d = dct + k * a.Fp;
+                float c = 0.f;
+                int n = 0;
+                for (; n + 8 <= a.F; n += 8) {      // eight LDS reads of each operand in flight, summed in the same order
+                    float dv[8], lv[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        dv[q] = d[n + q];
+                        lv[q] = lm[n + q];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) c = fmaf(dv[q], lv[q], c);
+                }
+                for (; n < a.F; ++n) c = fmaf(d[n], lm[n], c);
+                c *= a.lifter[k];
+                int row = k;
+                if (k == 0 && a.use_energy) c = le;
+                if (a.htk) {
+                    row = k > 0 ? k - 1 : a.C - 1;
+                    if (k == 0 && !a.use_energy) c *= 1.41421356237309505f;
+                }
+                otile[row * a.FT + tl] = c;
+            }
+            wave_lds_sync();        // the next round overwrites z
+        }
     }
     __syncthreads();                                // the otile columns of every wave are complete
-    // transposed store: each mel row gets a run of nt consecutive frames; zeros past T
-    for (int i = tid; i < (a.F + 1) * nt; i += FE_THREADS) {
+    // transposed store: each feature row gets a run of nt consecutive frames; zeros past T
+    for (int i = tid; i < (R + 1) * nt; i += FE_THREADS) {
         const int m = i / nt, tl = i - m * nt, t = t0 + tl;
         const float v = t < T ? otile[m * a.FT + tl] : 0.f;
-        if (m < a.F) frow[(size_t)m * a.Tcap + t] = v;
+        if (m < R) frow[(size_t)m * a.Tcap + t] = v;
         else a.loge[(size_t)b * a.Tcap + t] = v;
     }
 }
+
+__global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) { frontend_tile<false>(a); }
+__global__ __launch_bounds__(FE_THREADS) void mfcc_kernel(FbankArgs a) { frontend_tile<true>(a); }
 
 // the noise fbank_kernel adds (before scaling by dither) to frames frame0 .. frame0 + nframes - 1 of utterance utt_id
 __global__ __launch_bounds__(256) void dither_noise_kernel(float* out, long long utt_id, unsigned long long seed, int frame0,
@@ -296,6 +347,30 @@ int fe_lds_bytes(int FT, int L, int S, int P, int F) {
     return (FE_WAVES * P /* z */ + FE_WAVES * P /* fb */ + span + (F + 1) * FT) * 4;
 }
 
+// the MFCC tile: C + 1 output rows, and the DCT copy [C][F | 1] behind them (in long long: C * F of a refused call may be large)
+long long fe_mfcc_lds_bytes(int FT, int L, int S, int P, int F, int C) {
+    return (long long)fe_lds_bytes(FT, L, S, P, C) + (long long)C * (F | 1) * 4;
+}
+
+// the arguments fbank_kernel and mfcc_kernel share (checked by the caller); the cepstral fields are left empty
+FbankArgs fe_args(const float* wave, const int* nsamp, const long long* utt_ids, long long Nmax, const float* window,
+                  const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P, int F,
+                  int snip_edges, float dither, float preemph, int remove_dc, float energy_floor, unsigned long long seed, float* feats,
+                  float* log_energy, int* T_out, int Tcap, int FT) {
+    FbankArgs a;
+    a.wave = wave; a.nsamp = nsamp; a.utt_ids = utt_ids; a.Nmax = Nmax;
+    a.window = window; a.twiddle = twiddle; a.mel_w = mel_w; a.mel_lo = mel_lo; a.mel_off = mel_off;
+    a.L = L; a.S = S; a.P = P; a.F = F; a.snip = snip_edges ? 1 : 0; a.FT = FT; a.span = (FT - 1) * S + L;
+    int lg = 0;
+    while ((1 << lg) < P / 2) ++lg;
+    a.logM = lg;
+    a.dither = dither; a.preemph = preemph; a.remove_dc = remove_dc ? 1 : 0;
+    a.log_floor = energy_floor > 0.f ? logf(energy_floor) : -__builtin_inff();
+    a.seed = seed; a.feats = feats; a.loge = log_energy; a.T_out = T_out; a.Tcap = Tcap;
+    a.dct = nullptr; a.lifter = nullptr; a.C = 0; a.Fp = 0; a.use_energy = 0; a.htk = 0;
+    return a;
+}
+
 }  // namespace
 
 constexpr int FE_LDS_LIMIT = 64 * 1024;
@@ -304,6 +379,12 @@ constexpr int FE_LDS_LIMIT = 64 * 1024;
 extern "C" int spk_fbank_tile_frames(int L, int S, int P, int F) {
     for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
         if (fe_lds_bytes(FT, L, S, P, F) <= FE_LDS_LIMIT) return FT;
+    return 0;
+}
+
+extern "C" int spk_mfcc_tile_frames(int L, int S, int P, int F, int C) {
+    for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
+        if (fe_mfcc_lds_bytes(FT, L, S, P, F, C) <= FE_LDS_LIMIT) return FT;
     return 0;
 }
 
@@ -323,19 +404,38 @@ extern "C" int spk_fbank_fwd(const float* wave, const int* nsamp, const long lon
                 "spk_fbank_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
     const int FT = spk_fbank_tile_frames(L, S, P, F);
     SPK_REQUIRE(FT > 0, "spk_fbank_fwd: L=%d S=%d P=%d F=%d do not fit the LDS tile", L, S, P, F);
-    FbankArgs a;
-    a.wave = wave; a.nsamp = nsamp; a.utt_ids = utt_ids; a.Nmax = Nmax;
-    a.window = window; a.twiddle = twiddle; a.mel_w = mel_w; a.mel_lo = mel_lo; a.mel_off = mel_off;
-    a.L = L; a.S = S; a.P = P; a.F = F; a.snip = snip_edges ? 1 : 0; a.FT = FT; a.span = (FT - 1) * S + L;
-    int lg = 0;
-    while ((1 << lg) < P / 2) ++lg;
-    a.logM = lg;
-    a.dither = dither; a.preemph = preemph; a.remove_dc = remove_dc ? 1 : 0;
-    a.log_floor = energy_floor > 0.f ? logf(energy_floor) : -__builtin_inff();
-    a.seed = seed; a.feats = feats; a.loge = log_energy; a.T_out = T_out; a.Tcap = Tcap;
+    FbankArgs a = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
+                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
     const int lds = fe_lds_bytes(FT, L, S, P, F);
     hipLaunchKernelGGL(fbank_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds, (hipStream_t)stream, a);
     SPK_LAUNCH_CHECK("spk_fbank_fwd");
+    return 0;
+}
+
+extern "C" int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax,
+                            const float* window, const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off,
+                            const float* dct, const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither,
+                            float preemph, int remove_dc, float energy_floor, int use_energy, int htk_compat,
+                            unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
+    SPK_REQUIRE(wave && nsamp && window && twiddle && mel_w && mel_lo && mel_off && dct && lifter && feats && log_energy && T_out,
+                "spk_mfcc_fwd: null pointer");
+    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_mfcc_fwd: dither != 0 needs utt_ids");
+    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_mfcc_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
+    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_mfcc_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
+    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_mfcc_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
+    SPK_REQUIRE(F >= 1 && F <= P, "spk_mfcc_fwd: num_mel_bins F=%d (the log-mels of a frame reuse its FFT buffer of P=%d floats)", F, P);
+    SPK_REQUIRE(C >= 1 && C <= F, "spk_mfcc_fwd: num_ceps C=%d must be in [1, num_mel_bins F=%d]", C, F);
+    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
+                "spk_mfcc_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
+    const int FT = spk_mfcc_tile_frames(L, S, P, F, C);
+    SPK_REQUIRE(FT > 0, "spk_mfcc_fwd: L=%d S=%d P=%d F=%d C=%d do not fit the LDS tile", L, S, P, F, C);
+    FbankArgs a = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
+                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
+    a.dct = dct; a.lifter = lifter; a.C = C; a.Fp = F | 1; a.use_energy = use_energy ? 1 : 0; a.htk = htk_compat ? 1 : 0;
+    const int lds = (int)fe_mfcc_lds_bytes(FT, L, S, P, F, C);
+    hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
+                       (hipStream_t)stream, a);
+    SPK_LAUNCH_CHECK("spk_mfcc_fwd");
     return 0;
 }
 

@@ -1,8 +1,8 @@
-"""Kaldi-compatible feature front end on the GPU: fbank (compute-fbank-feats), energy VAD (compute-vad), centred sliding CMN
-(apply-cmvn-sliding --norm-vars=false --center=true) and voiced-frame selection (select-voiced-frames) - the Kaldi binaries of
+"""Kaldi-compatible feature front end on the GPU: fbank (compute-fbank-feats), MFCC (compute-mfcc-feats), energy VAD (compute-vad),
+centred sliding CMN (apply-cmvn-sliding --norm-vars=false --center=true) and voiced-frame selection (select-voiced-frames) - the Kaldi binaries of
 stage 1 of the reference's feature_pre.sh:77-104 and of local/nnet3/xvector/prepare_feats_for_egs.sh:68-70.
 
-The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_vad_count, spk_cmn_select) and csrc/resample.hip
+The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_mfcc_fwd, spk_vad_count, spk_cmn_select) and csrc/resample.hip
 (spk_resample_fwd: Kaldi's LinearResample, for audio at another sample rate and for speed perturbation) and csrc/augment.hip
 (spk_augment_fwd: reverberation and additive noise, the wav-reverberate entries of the recipe's augmented wav.scp); this module parses Kaldi
 config files, builds the window / twiddle / mel / resampling tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
@@ -63,6 +63,24 @@ class _KaldiOptions:
         return cls(**kw)
 
 
+def _check_frame_and_mel_options(name, o):
+    """the refusals FbankOptions and MfccOptions share (`name` is the class in the messages)"""
+    if o.window_type not in WINDOWS:
+        raise ValueError("%s: window_type %r (one of %s)" % (name, o.window_type, ", ".join(WINDOWS)))
+    if o.num_mel_bins <= 3:
+        raise ValueError("%s: num_mel_bins must be > 3" % name)
+    if o.frame_len < 2 or o.frame_sh < 1:
+        raise ValueError("%s: frame length %d / shift %d samples" % (name, o.frame_len, o.frame_sh))
+    if o.padded_len > 1024:
+        raise ValueError("%s: padded window of %d samples > 1024 is not supported" % (name, o.padded_len))
+    if not 0.0 <= o.preemphasis_coefficient <= 1.0 or o.dither < 0 or o.energy_floor < 0:
+        raise ValueError("%s: preemphasis_coefficient in [0, 1], dither >= 0, energy_floor >= 0" % name)
+    nyq = 0.5 * o.sample_frequency
+    hf = o.high_freq + nyq if o.high_freq <= 0 else o.high_freq
+    if not (0.0 <= o.low_freq < nyq and 0.0 < hf <= nyq and o.low_freq < hf):
+        raise ValueError("%s: low_freq %g / high_freq %g vs. Nyquist %g" % (name, o.low_freq, o.high_freq, nyq))
+
+
 @dataclasses.dataclass
 class FbankOptions(_KaldiOptions):
     """compute-fbank-feats options (Kaldi names and defaults)."""
@@ -98,20 +116,7 @@ class FbankOptions(_KaldiOptions):
         for name, bad in refuse:
             if bad:
                 raise ValueError("FbankOptions: %s is not supported by the GPU front end" % name)
-        if self.window_type not in WINDOWS:
-            raise ValueError("FbankOptions: window_type %r (one of %s)" % (self.window_type, ", ".join(WINDOWS)))
-        if self.num_mel_bins <= 3:
-            raise ValueError("FbankOptions: num_mel_bins must be > 3")
-        if self.frame_len < 2 or self.frame_sh < 1:
-            raise ValueError("FbankOptions: frame length %d / shift %d samples" % (self.frame_len, self.frame_sh))
-        if self.padded_len > 1024:
-            raise ValueError("FbankOptions: padded window of %d samples > 1024 is not supported" % self.padded_len)
-        if not 0.0 <= self.preemphasis_coefficient <= 1.0 or self.dither < 0 or self.energy_floor < 0:
-            raise ValueError("FbankOptions: preemphasis_coefficient in [0, 1], dither >= 0, energy_floor >= 0")
-        nyq = 0.5 * self.sample_frequency
-        hf = self.high_freq + nyq if self.high_freq <= 0 else self.high_freq
-        if not (0.0 <= self.low_freq < nyq and 0.0 < hf <= nyq and self.low_freq < hf):
-            raise ValueError("FbankOptions: low_freq %g / high_freq %g vs. Nyquist %g" % (self.low_freq, self.high_freq, nyq))
+        _check_frame_and_mel_options("FbankOptions", self)
 
     @property
     def frame_len(self):
@@ -130,6 +135,55 @@ class FbankOptions(_KaldiOptions):
         """frame count of an utterance of nsamp samples (nsamp >= frame length)"""
         L, S = self.frame_len, self.frame_sh
         return 1 + (nsamp - L) // S if self.snip_edges else (nsamp + S // 2) // S
+
+
+@dataclasses.dataclass
+class MfccOptions(_KaldiOptions):
+    """compute-mfcc-feats options (Kaldi names and defaults): the frame and mel options of FbankOptions, and the cepstral ones.
+    The mel banks do not depend on htk_compat."""
+    sample_frequency: float = 16000.0
+    frame_length: float = 25.0
+    frame_shift: float = 10.0
+    dither: float = 1.0
+    preemphasis_coefficient: float = 0.97
+    remove_dc_offset: bool = True
+    window_type: str = "povey"
+    round_to_power_of_two: bool = True
+    blackman_coeff: float = 0.42
+    snip_edges: bool = True
+    num_mel_bins: int = 23
+    low_freq: float = 20.0
+    high_freq: float = 0.0
+    vtln_low: float = 100.0
+    vtln_high: float = -500.0
+    vtln_warp: float = 1.0
+    num_ceps: int = 13
+    use_energy: bool = True
+    energy_floor: float = 0.0
+    raw_energy: bool = True
+    cepstral_lifter: float = 22.0
+    htk_compat: bool = False
+    subtract_mean: bool = False
+
+    def __post_init__(self):
+        refuse = [("vtln_warp", self.vtln_warp != 1.0), ("subtract_mean", self.subtract_mean),
+                  ("raw_energy=false", not self.raw_energy), ("round_to_power_of_two=false", not self.round_to_power_of_two)]
+        for name, bad in refuse:
+            if bad:
+                raise ValueError("MfccOptions: %s is not supported by the GPU front end" % name)
+        _check_frame_and_mel_options("MfccOptions", self)
+        if self.num_ceps < 1 or self.num_ceps > self.num_mel_bins:
+            raise ValueError("MfccOptions: num_ceps %d must be in [1, num_mel_bins %d]" % (self.num_ceps, self.num_mel_bins))
+        if not self.cepstral_lifter >= 0:
+            raise ValueError("MfccOptions: cepstral_lifter %r must be >= 0" % (self.cepstral_lifter,))
+        if self.num_mel_bins > self.padded_len:
+            raise ValueError("MfccOptions: num_mel_bins %d above the padded window of %d samples" % (self.num_mel_bins, self.padded_len))
+
+    # the derived sizes are FbankOptions' own: Frontend, wav_scp_batches and the resampler take either options object
+    frame_len = FbankOptions.frame_len
+    frame_sh = FbankOptions.frame_sh
+    padded_len = FbankOptions.padded_len
+    num_frames = FbankOptions.num_frames
 
 
 @dataclasses.dataclass
@@ -202,6 +256,23 @@ def mel_banks(opts):
     return np.maximum(0.0, np.minimum(up, down))
 
 
+def dct_matrix(opts):
+    """[C][F] rows of Kaldi's DCT-II (ComputeDctMatrix): D[0][n] = sqrt(1 / F), D[k][n] = sqrt(2 / F) cos(pi / F (n + 0.5) k) (fp64)"""
+    C, F = opts.num_ceps, opts.num_mel_bins
+    k = np.arange(C, dtype=np.float64)[:, None]
+    n = np.arange(F, dtype=np.float64)[None, :]
+    d = math.sqrt(2.0 / F) * np.cos(math.pi / F * (n + 0.5) * k)
+    d[0, :] = math.sqrt(1.0 / F)
+    return d
+
+
+def lifter_coeffs(opts):
+    """[C] 1 + Q / 2 sin(pi k / Q) for cepstral_lifter Q != 0, else ones (fp64)"""
+    Q = float(opts.cepstral_lifter)
+    k = np.arange(opts.num_ceps, dtype=np.float64)
+    return 1.0 + 0.5 * Q * np.sin(math.pi * k / Q) if Q != 0 else np.ones(opts.num_ceps)
+
+
 class _Tables:
     def __init__(self, opts, device):
         P = opts.padded_len
@@ -220,13 +291,16 @@ class _Tables:
         self.mel_w = torch.from_numpy(np.concatenate(ws + [np.zeros(1)]).astype(np.float32)).to(device)
         self.mel_lo = torch.tensor(lo, dtype=torch.int32, device=device)
         self.mel_off = torch.tensor(off, dtype=torch.int32, device=device)
+        if isinstance(opts, MfccOptions):
+            self.dct = torch.from_numpy(dct_matrix(opts).astype(np.float32)).to(device)
+            self.lifter = torch.from_numpy(lifter_coeffs(opts).astype(np.float32)).to(device)
 
 
 _TABLES = {}
 
 
 def _tables(opts, device):
-    key = (dataclasses.astuple(opts), str(device))
+    key = (type(opts).__name__, dataclasses.astuple(opts), str(device))
     t = _TABLES.get(key)
     if t is None:
         t = _TABLES[key] = _Tables(opts, device)
@@ -740,42 +814,76 @@ def augment_inputs(table, idx):
 
 
 # ---- functional API ----
-def fbank(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None):
-    """wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or device ints, each >= frame length).
-    Returns (feats [B, F, Tcap] cuda (zeros past T[b]), T int64 host array, log_energy [B, Tcap] cuda (raw log energy))."""
+def _frame_inputs(what, wave, nsamp, opts, utt_ids, Tcap):
+    """the argument checks and device inputs fbank and mfcc share (`what` names the caller in the messages):
+    (wave, B, Nmax, T, Tcap, ns, ids, tables)"""
     if wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
-        raise ValueError("fbank: wave must be a float32 cuda tensor [B, Nmax]")
+        raise ValueError("%s: wave must be a float32 cuda tensor [B, Nmax]" % what)
     wave = wave.contiguous()
     B, Nmax = wave.shape
     n = _host_ints(nsamp)
     if n.size != B:
-        raise ValueError("fbank: %d sample counts for %d rows" % (n.size, B))
+        raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
     L = opts.frame_len
     if (n < L).any() or (n > Nmax).any():
         bad = int(np.nonzero((n < L) | (n > Nmax))[0][0])
-        raise ValueError("fbank: row %d has %d samples, outside [frame length %d, Nmax %d]" % (bad, int(n[bad]), L, Nmax))
+        raise ValueError("%s: row %d has %d samples, outside [frame length %d, Nmax %d]" % (what, bad, int(n[bad]), L, Nmax))
     T = np.asarray([opts.num_frames(int(v)) for v in n], dtype=np.int64)
     Tcap = int(T.max()) if Tcap is None else int(Tcap)
     if Tcap < T.max():
-        raise ValueError("fbank: Tcap %d < longest utterance %d frames" % (Tcap, int(T.max())))
+        raise ValueError("%s: Tcap %d < longest utterance %d frames" % (what, Tcap, int(T.max())))
     if opts.dither != 0 and utt_ids is None:
-        raise ValueError("fbank: dither != 0 needs utt_ids (the key of each row's noise)")
+        raise ValueError("%s: dither != 0 needs utt_ids (the key of each row's noise)" % what)
     dev = wave.device
     tab = _tables(opts, dev)
     ns = torch.from_numpy(n.astype(np.int32)).to(dev)
     ids = torch.as_tensor(_host_ints(utt_ids), dtype=torch.int64).to(dev) if utt_ids is not None else None
+    return wave, B, Nmax, T, Tcap, ns, ids, tab
+
+
+def fbank(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None):
+    """wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or device ints, each >= frame length).
+    Returns (feats [B, F, Tcap] cuda (zeros past T[b]), T int64 host array, log_energy [B, Tcap] cuda (raw log energy))."""
+    wave, B, Nmax, T, Tcap, ns, ids, tab = _frame_inputs("fbank", wave, nsamp, opts, utt_ids, Tcap)
+    dev = wave.device
     feats = torch.empty(B, opts.num_mel_bins, Tcap, device=dev)
     loge = torch.empty(B, Tcap, device=dev)
     tdev = torch.empty(B, dtype=torch.int32, device=dev)
     hip.call("spk_fbank_fwd", hip.ptr(wave), hip.ptr(ns), hip.ptr(ids), B, Nmax, hip.ptr(tab.window), hip.ptr(tab.twiddle),
-             hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off), L, opts.frame_sh, opts.padded_len, opts.num_mel_bins,
-             int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient), int(opts.remove_dc_offset),
-             float(opts.energy_floor), int(seed) & (2 ** 64 - 1), hip.ptr(feats), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
+             hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off), opts.frame_len, opts.frame_sh, opts.padded_len,
+             opts.num_mel_bins, int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient),
+             int(opts.remove_dc_offset), float(opts.energy_floor), int(seed) & (2 ** 64 - 1), hip.ptr(feats), hip.ptr(loge),
+             hip.ptr(tdev), Tcap, hip.stream())
     return feats, T, loge
 
 
+def mfcc(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None, out=None):
+    """compute-mfcc-feats (opts: MfccOptions).  wave, nsamp, utt_ids, seed, Tcap as for fbank; the frames, the dither draws and the
+    raw log energy are the fbank's for the same framing options.  Returns (feats [B, C, Tcap] cuda, C = num_ceps (zeros past T[b]),
+    T int64 host array, log_energy [B, Tcap] cuda - the raw log energy, floored by log(energy_floor), whatever use_energy says:
+    the VAD's input).  out: a preallocated contiguous float32 cuda tensor [B, C, Tcap] to write the features into."""
+    if not isinstance(opts, MfccOptions):
+        raise ValueError("mfcc: opts must be an MfccOptions")
+    wave, B, Nmax, T, Tcap, ns, ids, tab = _frame_inputs("mfcc", wave, nsamp, opts, utt_ids, Tcap)
+    dev = wave.device
+    C = opts.num_ceps
+    if out is None:
+        out = torch.empty(B, C, Tcap, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, C, Tcap) or not out.is_cuda
+          or not out.is_contiguous()):
+        raise ValueError("mfcc: out must be a contiguous float32 cuda tensor [%d, %d, %d]" % (B, C, Tcap))
+    loge = torch.empty(B, Tcap, device=dev)
+    tdev = torch.empty(B, dtype=torch.int32, device=dev)
+    hip.call("spk_mfcc_fwd", hip.ptr(wave), hip.ptr(ns), hip.ptr(ids), B, Nmax, hip.ptr(tab.window), hip.ptr(tab.twiddle),
+             hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off), hip.ptr(tab.dct), hip.ptr(tab.lifter), opts.frame_len,
+             opts.frame_sh, opts.padded_len, opts.num_mel_bins, C, int(opts.snip_edges), float(opts.dither),
+             float(opts.preemphasis_coefficient), int(opts.remove_dc_offset), float(opts.energy_floor), int(opts.use_energy),
+             int(opts.htk_compat), int(seed) & (2 ** 64 - 1), hip.ptr(out), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
+    return out, T, loge
+
+
 def dither_noise(utt, seed, frame0, nframes, L, device="cuda"):
-    """[nframes, L] the N(0,1) noise spk_fbank_fwd adds (times dither) to frames frame0 .. of the utterance with id `utt`"""
+    """[nframes, L] the N(0,1) noise spk_fbank_fwd / spk_mfcc_fwd adds (times dither) to frames frame0 .. of the utterance with id `utt`"""
     out = torch.empty(nframes, L, device=device)
     hip.call("spk_fbank_dither_noise", hip.ptr(out), int(utt), int(seed) & (2 ** 64 - 1), int(frame0), int(nframes), int(L),
              hip.stream())
@@ -825,7 +933,7 @@ def select_voiced(x, T, idx, count, cmn=None):
 
 
 class Frontend:
-    """wav -> model input: (optional) resampling, fbank, then (optional) sliding CMN over all frames and voiced-frame selection, as the
+    """wav -> model input: (optional) resampling, fbank (MFCC when fbank_opts is an MfccOptions), then (optional) sliding CMN over all frames and voiced-frame selection, as the
     recipe's prepare_feats_for_egs.sh.  Frontend(fbank_opts, vad=None, cmn=None, input_rate=None, speed=None)(wave [B, Nmax] cuda,
     nsamp, utt_ids, seed, input_rate=None) -> (feats [B, F, T] cuda, lengths int64 host array): the input predict(x, lengths=...)
     takes.  A row without voiced frames has length 0 (its column block is all zero): the caller reports and skips it.
@@ -852,7 +960,7 @@ class Frontend:
         fi, fo = self.rates(input_rate)
         if fi != fo:
             wave, nsamp = resample(wave, nsamp, fi, fo)
-        feats, T, loge = fbank(wave, nsamp, self.fbank_opts, utt_ids, seed)
+        feats, T, loge = (mfcc if isinstance(self.fbank_opts, MfccOptions) else fbank)(wave, nsamp, self.fbank_opts, utt_ids, seed)
         if self.vad_opts is None:
             if self.cmn_opts is not None:
                 feats = sliding_cmn(feats, T, self.cmn_opts)
@@ -861,10 +969,16 @@ class Frontend:
         return select_voiced(feats, T, idx, cnt, self.cmn_opts)
 
 
-# ---- wav.scp helpers of scripts/compute_fbank.py and scripts/decode.py --wav-scp ----
-def options_from_configs(fbank_config=None, vad_config=None, cmn_window=0):
-    """(FbankOptions, VadOptions or None, CmnOptions or None) from Kaldi config files and an apply-cmvn-sliding window (0: no CMN)"""
-    fb = FbankOptions.from_kaldi_config(fbank_config) if fbank_config else FbankOptions()
+# ---- wav.scp helpers of scripts/compute_fbank.py, scripts/compute_mfcc.py and scripts/decode.py --wav-scp ----
+def options_from_configs(fbank_config=None, vad_config=None, cmn_window=0, mfcc_config=None):
+    """(FbankOptions, VadOptions or None, CmnOptions or None) from Kaldi config files and an apply-cmvn-sliding window (0: no CMN);
+    mfcc_config (instead of fbank_config; "" for compute-mfcc-feats' defaults): MfccOptions in place of the FbankOptions"""
+    if mfcc_config is not None and fbank_config:
+        raise ValueError("options_from_configs: fbank_config and mfcc_config are mutually exclusive")
+    if mfcc_config is not None:
+        fb = MfccOptions.from_kaldi_config(mfcc_config) if mfcc_config else MfccOptions()
+    else:
+        fb = FbankOptions.from_kaldi_config(fbank_config) if fbank_config else FbankOptions()
     vad_opts = VadOptions.from_kaldi_config(vad_config) if vad_config else None
     cmn = CmnOptions(cmn_window=cmn_window) if cmn_window and cmn_window > 0 else None
     return fb, vad_opts, cmn

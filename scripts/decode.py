@@ -46,12 +46,14 @@ parser.add_argument("--pad-batches", action="store_true",
                          "common length (at most 10%% padded frames, T rounded up to 8) and run through the length-masked "
                          "predict(x, lengths=...): each embedding is that of its utterance alone")
 parser.add_argument("--wav-scp", help="extract from audio: a wav.scp of PCM 16-bit mono files (instead of --decode-scp); the "
-                    "Kaldi fbank (+ sliding CMN, + energy VAD frame selection) runs on the GPU (pytorch_kaldi_resnet_amd.features)")
+                    "Kaldi fbank (or, with --mfcc-config, MFCC; + sliding CMN, + energy VAD frame selection) runs on the GPU (pytorch_kaldi_resnet_amd.features)")
 parser.add_argument("--allow-downsample", action="store_true",
                     help="with --wav-scp: resample files above the fbank's --sample-frequency on the GPU instead of refusing them")
 parser.add_argument("--allow-upsample", action="store_true",
                     help="with --wav-scp: resample files below the fbank's --sample-frequency on the GPU instead of refusing them")
 parser.add_argument("--fbank-config", help="with --wav-scp: Kaldi compute-fbank-feats config (conf/fbank.conf)")
+parser.add_argument("--mfcc-config", help="with --wav-scp: Kaldi compute-mfcc-feats config (conf/mfcc.conf): the model input is the "
+                    "MFCC (--input-dim = its num-ceps) instead of the fbank; not together with --fbank-config")
 parser.add_argument("--vad-config", help="with --wav-scp: Kaldi compute-vad config (conf/vad.conf): keep voiced frames only")
 parser.add_argument("--cmn-window", type=int, default=0,
                     help="with --wav-scp: apply-cmvn-sliding --norm-vars=false --center=true window (0: none; the recipe uses 300)")
@@ -66,6 +68,19 @@ def main():
         parser.error("--wav-scp and --decode-scp are mutually exclusive")
     if (args.fbank_config or args.vad_config or args.cmn_window or args.allow_downsample or args.allow_upsample) and not args.wav_scp:
         parser.error("--fbank-config / --vad-config / --cmn-window / --allow-downsample / --allow-upsample need --wav-scp")
+    if args.mfcc_config and args.fbank_config:
+        parser.error("--mfcc-config and --fbank-config are mutually exclusive")
+    if args.mfcc_config and not args.wav_scp:
+        parser.error("--mfcc-config needs --wav-scp")
+    if args.mfcc_config:        # before the model is built: a config whose num-ceps is not the model's input dimension
+        import pytorch_kaldi_resnet_amd  # noqa: F401
+        from pytorch_kaldi_resnet_amd import features
+        try:
+            num_ceps = features.MfccOptions.from_kaldi_config(args.mfcc_config).num_ceps
+        except (OSError, ValueError) as e:
+            parser.error("--mfcc-config: %s" % e)
+        if num_ceps != args.input_dim:
+            parser.error("--input-dim %d differs from the num-ceps %d of --mfcc-config %s" % (args.input_dim, num_ceps, args.mfcc_config))
     if args.pad_batches and not args.native_reader:
         parser.error("--pad-batches needs --native-reader")
     if args.pad_batches and args.chunk_size >= 0:
@@ -260,7 +275,8 @@ def wav_generator(model, args):
     format as native_generator; utterances shorter than one frame or without voiced frames are reported and skipped."""
     from concurrent.futures import ThreadPoolExecutor
     from pytorch_kaldi_resnet_amd import features, ingest, kaldi_io
-    fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window)
+    fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window,
+                                                      mfcc_config=args.mfcc_config or None)
     frontend = features.Frontend(fb, vad_opts, cmn)
     keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size, args.allow_downsample,
                                                            args.allow_upsample)
