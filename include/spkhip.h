@@ -213,6 +213,19 @@ int spk_stem_conv_fwd_len(const float* x, const float* w, float* out, float* sta
 int spk_stem_wgrad_blocks(int B, int F, int T);
 int spk_stem_conv_wgrad(const float* x, const float* draw, float* dw, float* partial, int B, int F, int T,
                         int accumulate, void* stream);
+/* Training forward without reading raw0 back (the convolution is cheaper to compute twice than its output is to read once):
+ * spk_stem_stats writes the rows spk_stem_conv_fwd(SPK_EPI_STATS) writes, bit for bit, and stores nothing else;
+ * spk_stem_fwd_apply recomputes the convolution and writes raw_out, act_out = relu(raw*scale + shift), the sign words of act_out
+ * (optional; [B*F*T] words, 32 channels each, as spk_bn_apply's mask_out) and atomicMax'es the float bits of |act_out| into
+ * amax_out (optional) - every value bit-equal to spk_stem_conv_fwd followed by spk_bn_apply. */
+int spk_stem_stats(const float* x, const float* w, float* stats, int B, int F, int T, void* stream);
+int spk_stem_fwd_apply(const float* x, const float* w, const float* scale, const float* shift, float* raw_out, float* act_out,
+                       unsigned* mask_out, unsigned* amax_out, int B, int F, int T, void* stream);
+/* spk_bn_bwd_apply(MASK_RAW) of d fused into spk_stem_conv_wgrad: the gradient wrt raw is formed in registers and never stored
+ * (d is only read); dw is bit-equal to the two calls.  coef: the [3][32] rows of spk_bn_bwd_finalize; partial as above. */
+int spk_stem_bwd_wgrad(const float* x, const float* d, const float* raw, const float* mean, const float* invstd,
+                       const float* scale, const float* shift, const float* coef, float* dw, float* partial, int B, int F, int T,
+                       int accumulate, void* stream);
 
 /* ---- batch normalisation (nn.BatchNorm2d/1d, scripts/model.py:41,44,212,235,361) ------------------- */
 /* x viewed as [N][C], C a power of two in [4,1024] */
@@ -326,6 +339,11 @@ int spk_stats_pool_fwd(const float* x /*[B][H][W][C]*/, float* out /*[B][C*H*(1+
 int spk_stats_pool_fwd_len(const float* x, float* out, const int* wlen, int B, int H, int W, int C, int mode, void* stream);
 int spk_stats_pool_bwd(const float* x, const float* gout, float* dx, int B, int H, int W, int C, int mode,
                        unsigned* amax_out /* optional: atomicMax of the float bits of |dx| */, void* stream);
+/* Up to W = spk_stats_pool_row_cap() the two forward entries above load each row into registers once and run the same arithmetic
+ * on it (bit-equal results); spk_stats_pool_row_form(0) selects the serial two-pass kernel at every width (A/B, tests), (1) gives
+ * the default back.  Process-wide; returns the previous value. */
+int spk_stats_pool_row_form(int on);
+int spk_stats_pool_row_cap(void);
 
 /* ---- GEMM (fc1 = nn.Linear(5120,256) scripts/model.py:357; cosine F.linear :485; their gradients) ------ */
 /* C[m][n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]) (+ C[m][n]).  64x64 tiles on the fp32 matrix

@@ -79,13 +79,71 @@ __global__ __launch_bounds__(256) void stats_pool_bwd_kernel(const float* __rest
     if (amax_out) spk_wave_amax_commit(mx, amax_out);     // every lane of the wave takes part (no early return above)
 }
 
+// ---- the row read once: W <= POOL_ROW_CAP ------------------------------------------------------------------------------------
+// stats_pool_fwd_kernel walks a row of W values serially, twice, one dependent load at a time.  Here a thread loads its whole row
+// into registers first, every load in flight at once, and then runs the same serial arithmetic on the registers: the same order,
+// fmaf and divisions, so the results are bit-equal.  38 frames is the 300-frame step, 50 the 400-frame chunk.  Forward only: the
+// same form of the backward kernel was measured and was not faster.
+#define POOL_ROW_CAP 64
+
+template <bool LEN>
+__global__ __launch_bounds__(256) void stats_pool_fwd_row_kernel(const float* __restrict__ x, float* __restrict__ out, int B,
+                                                                 int H, int Wp, int C, int mode, const int* __restrict__ wlen) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long total = (long long)B * H * C;
+    if (idx >= total) return;
+    const int c = (int)(idx % C);
+    const long long bh = idx / C;
+    const int h = (int)(bh % H);
+    const int b = (int)(bh / H);
+    const float* p = x + (size_t)bh * Wp * C + c;
+    const int W = LEN ? max(1, min(wlen[b], Wp)) : Wp;
+    float r[POOL_ROW_CAP];
+#pragma unroll
+    for (int w = 0; w < POOL_ROW_CAP; ++w)
+        if (w < Wp) r[w] = p[(size_t)w * C];      // Wp is uniform: the loads follow one another without a wait
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < POOL_ROW_CAP; ++w)
+        if (w < W) s += r[w];
+    const float mean = s / (float)W;
+    if (mode == 0) {
+        out[(size_t)b * C * H + (size_t)c * H + h] = mean;
+        return;
+    }
+    float m2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < POOL_ROW_CAP; ++w)
+        if (w < W) {
+            const float d = r[w] - mean;
+            m2 = fmaf(d, d, m2);
+        }
+    float* o = out + (size_t)b * C * 2 * H + (size_t)c * 2 * H;
+    o[h] = m2 / (float)(W - 1);
+    o[H + h] = sqrtf(mean);
+}
+
+// A/B and test switch: 0 = the serial two-pass forward kernel at every width, 1 (default) = rows in registers up to POOL_ROW_CAP.
+// Process-wide; returns the previous value.
+static int g_pool_row_form = 1;
+extern "C" int spk_stats_pool_row_form(int on) {
+    const int prev = g_pool_row_form;
+    g_pool_row_form = on ? 1 : 0;
+    return prev;
+}
+extern "C" int spk_stats_pool_row_cap(void) { return POOL_ROW_CAP; }
+
 extern "C" int spk_stats_pool_fwd(const float* x, float* out, int B, int H, int W, int C, int mode, void* stream) {
     SPK_REQUIRE(x && out, "spk_stats_pool_fwd: null pointer");
     SPK_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "spk_stats_pool_fwd: empty input");
     SPK_REQUIRE(mode == 0 || mode == 1, "spk_stats_pool_fwd: mode=%d", mode);
     const long long total = (long long)B * H * C;
-    hipLaunchKernelGGL(stats_pool_fwd_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                       out, B, H, W, C, mode, nullptr);
+    if (g_pool_row_form && W <= POOL_ROW_CAP)
+        hipLaunchKernelGGL(stats_pool_fwd_row_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, x, out, B, H, W, C, mode, nullptr);
+    else
+        hipLaunchKernelGGL(stats_pool_fwd_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                           out, B, H, W, C, mode, nullptr);
     SPK_LAUNCH_CHECK("spk_stats_pool_fwd");
     return 0;
 }
@@ -96,8 +154,12 @@ extern "C" int spk_stats_pool_fwd_len(const float* x, float* out, const int* wle
     SPK_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "spk_stats_pool_fwd_len: empty input");
     SPK_REQUIRE(mode == 0 || mode == 1, "spk_stats_pool_fwd_len: mode=%d", mode);
     const long long total = (long long)B * H * C;
-    hipLaunchKernelGGL(stats_pool_fwd_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                       out, B, H, W, C, mode, wlen);
+    if (g_pool_row_form && W <= POOL_ROW_CAP)
+        hipLaunchKernelGGL(stats_pool_fwd_row_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, x, out, B, H, W, C, mode, wlen);
+    else
+        hipLaunchKernelGGL(stats_pool_fwd_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                           out, B, H, W, C, mode, wlen);
     SPK_LAUNCH_CHECK("spk_stats_pool_fwd_len");
     return 0;
 }

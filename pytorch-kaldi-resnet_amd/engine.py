@@ -156,6 +156,12 @@ class Engine:
         self.fuse_apply_1x1 = os.environ.get("SPK_FUSE_APPLY_1X1", "0") == "1"
         # gradients wrt raw conv outputs travel as f16 pair tensors (include/spkhip.h) in the f16x3 mode
         self.pair_draw = os.environ.get("SPK_PAIR_DRAW", "1") == "1"
+        # the stem without two tensor passes (csrc/stem.hip): forward = statistics with no store, then one writer of raw0, a and
+        # the sign bits that recomputes the convolution; backward = the BatchNorm-backward apply inside the weight gradient.
+        # 0 gives the two-kernel paths back (A/B, identity tests); "fwd" / "bwd" switch one half on (per-part A/B)
+        stem_fused = os.environ.get("SPK_STEM_FUSED", "1")
+        self.stem_fused_fwd = stem_fused in ("1", "fwd")
+        self.stem_fused_bwd = stem_fused in ("1", "bwd")
         # diagnostics (tests / bench, never the timed path): when a [4] int64 device tensor, every tensor that an f16x3
         # matrix-core kernel stages is also run through spk_f16_window_count under the scale slot its consumer uses
         # The blocks of the LAST stage sit between the pooling layer and the first BatchNorm backward + convolution that bound the
@@ -390,13 +396,19 @@ class Engine:
         saved["gen"] = self._fwd_gen
         take = (lambda: pool.take()) if pool is not None else (lambda: None)
         f16 = ops.split_for(3) == 3
-        raw0, st = ops.stem_fwd(x, self.stem_conv.h.weight.data, stats=True)
-        B, F, T, _ = raw0.shape
-        t4 = self.stem_bn.finalize(st, B * F * T, keep=save)
+        B, F, T = x.shape
         use_masks = save and self.use_sign_masks
-        a_amax = take()
-        a = ops.bn_apply(raw0, t4[2], t4[3], relu=True, mask=use_masks, amax_out=a_amax)
-        a, amask = a if use_masks else (a, None)
+        w0 = self.stem_conv.h.weight.data
+        if self.stem_fused_fwd:
+            t4 = self.stem_bn.finalize(ops.stem_stats(x, w0), B * F * T, keep=save)
+            a_amax = take()
+            raw0, a, amask = ops.stem_fwd_apply(x, w0, t4[2], t4[3], mask=use_masks, amax_out=a_amax)
+        else:
+            raw0, st = ops.stem_fwd(x, w0, stats=True)
+            t4 = self.stem_bn.finalize(st, B * F * T, keep=save)
+            a_amax = take()
+            a = ops.bn_apply(raw0, t4[2], t4[3], relu=True, mask=use_masks, amax_out=a_amax)
+            a, amask = a if use_masks else (a, None)
         saved["raw0"] = raw0
         for b in self.blocks:
             # in_amax[i]: slot with the absmax (or its upper estimate) of the values conv_i STAGES - the block input itself,
@@ -552,9 +564,17 @@ class Engine:
                     on_stage_done("layer%d" % stage_of[bi])
             # stem: d is the gradient wrt relu(bn(raw0))
             bn = self.stem_bn
-            draw0 = ops.bn_backward(d, saved["raw0"], None, bn.t4, bn.h.weight.data, bn.h.weight.grad, bn.h.bias.grad,
-                                    MASK_RAW, draw_out=d, accumulate=acc, partial=part)
-            ops.stem_wgrad(saved["x"], draw0, self.stem_conv.h.weight.grad, accumulate=acc)
+            if self.stem_fused_bwd:
+                raw0 = saved["raw0"]
+                if part is None:
+                    part = ops.bn_bwd_partial(d, raw0, None, bn.t4, MASK_RAW)
+                coef = ops.bn_bwd_coef(part, raw0.numel() // raw0.shape[-1], bn.h.weight.data, bn.t4, bn.h.weight.grad,
+                                       bn.h.bias.grad, accumulate=acc)
+                ops.stem_bwd_wgrad(saved["x"], d, raw0, bn.t4, coef, self.stem_conv.h.weight.grad, accumulate=acc)
+            else:
+                draw0 = ops.bn_backward(d, saved["raw0"], None, bn.t4, bn.h.weight.data, bn.h.weight.grad, bn.h.bias.grad,
+                                        MASK_RAW, draw_out=d, accumulate=acc, partial=part)
+                ops.stem_wgrad(saved["x"], draw0, self.stem_conv.h.weight.grad, accumulate=acc)
             self._join_wgrad()
             if on_stage_done:
                 on_stage_done("stem")

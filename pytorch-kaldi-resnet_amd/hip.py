@@ -45,6 +45,9 @@ _SIGS = {
     "spk_stem_conv_fwd_len": [_P] * 6 + [_I] * 4 + [_P, _P, _P],
     "spk_stem_wgrad_blocks": [_I, _I, _I],
     "spk_stem_conv_wgrad": [_P] * 4 + [_I] * 4 + [_P],
+    "spk_stem_stats": [_P] * 3 + [_I] * 3 + [_P],
+    "spk_stem_fwd_apply": [_P] * 8 + [_I] * 3 + [_P],
+    "spk_stem_bwd_wgrad": [_P] * 10 + [_I] * 4 + [_P],
     "spk_bn_stats_blocks": [_L, _I],
     "spk_bn_stats_partial": [_P, _P, _L, _I, _P],
     "spk_bn_finalize": [_P, _I, _I, _D] + [_P] * 9 + [_F, _F, _P, _P, _P, _P],
@@ -67,6 +70,8 @@ _SIGS = {
     "spk_stats_pool_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stats_pool_fwd_len": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "spk_stats_pool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "spk_stats_pool_row_form": [_I],
+    "spk_stats_pool_row_cap": [],
     "spk_gemm_f32": [_P] * 4 + [_I] * 3 + [_L] * 5 + [_F, _I, _P, _P],
     "spk_gemm_splitk": [_I, _I, _I],
     "spk_colsum": [_P, _P, _I, _I, _I, _P],
@@ -143,6 +148,8 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
+        if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
+            l.spk_stats_pool_row_form(0)
         _lib = l
     return _lib
 

@@ -700,6 +700,37 @@ def stem_wgrad(x, draw, dw, accumulate=False):
     return dw
 
 
+def stem_stats(x, w):
+    """The statistics rows of stem_fwd(x, w, stats=True), bit for bit, without the output tensor (spk_stem_stats)."""
+    B, F, T = x.shape
+    st = torch.empty(hip.lib().spk_stem_fwd_blocks(B, F, T), 32, 2, device=x.device, dtype=torch.float32)
+    call("spk_stem_stats", ptr(x), ptr(w), ptr(st), B, F, T, stream(), nbytes=4.0 * x.numel())
+    return st
+
+
+def stem_fwd_apply(x, w, scale, shift, mask=False, amax_out=None):
+    """-> (raw0, a, sign words or None): stem_fwd followed by bn_apply(relu=True, mask=, amax_out=) in one launch that
+    recomputes the convolution instead of reading raw0 back (spk_stem_fwd_apply); every value bit-equal to the two launches."""
+    B, F, T = x.shape
+    raw = torch.empty(B, F, T, 32, device=x.device, dtype=torch.float32)
+    act = torch.empty_like(raw)
+    mk = torch.empty(B * F * T, device=x.device, dtype=torch.int32) if mask else None
+    call("spk_stem_fwd_apply", ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(raw), ptr(act), ptr(mk), ptr(amax_out), B, F, T,
+         stream(), nbytes=4.0 * (x.numel() + 2 * raw.numel()) + (raw.numel() / 8 if mask else 0))
+    return raw, act, mk
+
+
+def stem_bwd_wgrad(x, d, raw, bn4, coef, dw, accumulate=False):
+    """stem_wgrad of the BatchNorm-backward apply (MASK_RAW) of d, formed in registers: d is only read and the gradient wrt raw
+    is never stored (spk_stem_bwd_wgrad).  coef: the rows of bn_bwd_coef.  dw is bit-equal to the two launches."""
+    B, F, T = x.shape
+    nblk = hip.lib().spk_stem_wgrad_blocks(B, F, T)
+    ws = _workspace(nblk * 288 * 4, x.device)
+    call("spk_stem_bwd_wgrad", ptr(x), ptr(d), ptr(raw), ptr(bn4[0]), ptr(bn4[1]), ptr(bn4[2]), ptr(bn4[3]), ptr(coef), ptr(dw),
+         ptr(ws), B, F, T, 1 if accumulate else 0, stream(), nbytes=4.0 * (x.numel() + 2 * raw.numel()))
+    return dw
+
+
 def bn_stats_partial(x2d):
     N, C = x2d.shape
     nblk = hip.lib().spk_bn_stats_blocks(N, C)
