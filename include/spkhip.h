@@ -522,6 +522,44 @@ int spk_cm_decode(const unsigned char* codes, const float* colhdr, const int* le
 int spk_cm_compress(const float* x, const int* T, int B, int F, int Tcap, float* ws, float* minrange, int* hdr, unsigned char* codes,
                     void* stream);
 
+/* ---- PLDA back end (csrc/plda.hip) ---------------------------------------------------------------------
+ * The passes over embedding tables and the trial loop of Kaldi's ivector-compute-lda, transform-vec, ivector-normalize-length,
+ * ivector-compute-plda and ivector-plda-scoring.  All sums in fp64 in a fixed order (no floating-point atomics); the two matrix
+ * kernels run on v_mfma_f64_16x16x4_f64.  1 <= D, Di, Do <= 512.  The D x D factorisations stay on the host. */
+/* rows per slab of spk_scatter_f64 for N rows (0: N out of range), and the bytes of its workspace (0: bad arguments) */
+int spk_scatter_slab_rows(long long N);
+size_t spk_scatter_f64_workspace(long long N, int D);
+/* C[D][D] = sum_i w[i] (x_i - mu)(x_i - mu)^T over the rows X[N][ld] (float, or double with x_f64; ld >= D); mu double[D] or NULL
+ * (zero), w double[N] or NULL (ones).  Kaldi: the total covariance and the class-mean scatter of CovarianceStats::AccStats
+ * (ivector-compute-lda.cc) and the offset scatter of PldaStats::AddSamples (plda.cc).  Output tiles come from the upper triangle
+ * and are mirrored (C == C^T bit for bit); rows are split into slabs of spk_scatter_slab_rows(N) whose partial sums a second pass
+ * adds in slab order.  ws: spk_scatter_f64_workspace(N, D) bytes. */
+int spk_scatter_f64(const void* X, int x_f64, long long ld, const double* mu, const double* w, double* C, void* ws, long long N, int D,
+                    void* stream);
+/* out[k][d] = sum of X[r][d] over r = rows[seg_off[k] .. seg_off[k + 1]) in list order (rows NULL: r itself), in fp64, divided by the
+ * number of rows when mean != 0; count[k] (or NULL) = the number of rows.  X float or double (x_f64), row pitch ld.  Kaldi: the per-speaker sums of CovarianceStats::AccStats
+ * and PldaStats::AddSamples.  (spk_segment_mean keeps the float32 accumulator of the reference's cohort script.) */
+int spk_segment_sum_f64(const void* X, int x_f64, long long ld, const int* rows, const int* seg_off /*[K+1]*/, double* out /*[K][D]*/,
+                        int* count /*[K]*/, int mean, int K, int D, void* stream);
+/* Y[i] = s_i (A x_i + b): A double[Do][Di] (NULL: the identity, Di == Do), b double[Do] or NULL; scale = 0: s_i = 1; else
+ * s_i = sqrt(Do / sum_j y_j^2 q_j) with y = A x_i + b and q double[Do] (NULL: ones), and a row whose sum is 0 keeps s_i = 1.
+ * X [N][ldx] float or double (x_f64); Y [N][Do] float (rounded once from fp64) or double (y_f64).  Kaldi: transform-vec,
+ * ivector-normalize-length, Plda::TransformIvector with its normalisation factor (q_j = 1 / (psi_j + 1 / n)). */
+int spk_affine_lennorm(const void* X, int x_f64, long long ldx, const double* A, const double* b, const double* q, int scale, void* Y,
+                       int y_f64, long long N, int Di, int Do, void* stream);
+/* One EM iteration of PldaEstimator::GetStatsFromClassMeans in the basis where W = I and B = diag(psi): for class k with count[k]
+ * utterances and centred mean mt[k], w_out[k][j] = count[k] psi[j] / (count[k] psi[j] + 1) * mt[k][j] and r_out = mt - w_out. */
+int spk_plda_posterior_rows(const double* mt /*[K][D]*/, const int* count, const double* psi, double* w_out, double* r_out, int K,
+                            int D, void* stream);
+/* Plda::LogLikelihoodRatio per trial: with e = en[ia[t]], x = te[ib[t]], n = count[ia[t]] (count NULL: 1),
+ * c_j = n psi_j / (n psi_j + 1), v_j = 1 + psi_j / (n psi_j + 1):
+ *   out[t] = (float)(sum_j 0.5 (x_j^2 / (psi_j + 1) - (x_j - c_j e_j)^2 / v_j) + 0.5 (L1 - L0)),
+ * (L0, L1) = tab_log[u] = (sum_j log v_j, sum_j log(psi_j + 1)) of the entry with tab_count[u] == n (U entries, built by the host;
+ * NaN when n is not in the table).  psi_j = 0 contributes exactly 0. */
+int spk_plda_llr(const double* en /*[n_en][D]*/, const double* te /*[n_te][D]*/, const int* ia, const int* ib, const double* psi,
+                 const int* count /*[n_en]*/, const int* tab_count /*[U]*/, const double* tab_log /*[U][2]*/, int U, float* out,
+                 int T, int D, int n_en, int n_te, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,12 @@ _SIGS = {
     "spk_trial_snorm": [_P, _I] + [_P] * 7 + [_I, _P],
     "spk_sort_trials": [_P, _P, _P, _I, _P],
     "spk_error_sweep": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P],
+    "spk_scatter_slab_rows": [_L],
+    "spk_scatter_f64": [_P, _I, _L, _P, _P, _P, _P, _L, _I, _P],
+    "spk_segment_sum_f64": [_P, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P],
+    "spk_affine_lennorm": [_P, _I, _L, _P, _P, _P, _I, _P, _I, _L, _I, _I, _P],
+    "spk_plda_posterior_rows": [_P] * 5 + [_I, _I, _P],
+    "spk_plda_llr": [_P] * 8 + [_I, _P, _I, _I, _I, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
@@ -144,6 +150,8 @@ def lib():
         l.spk_sort_trials_workspace.argtypes = [_I]
         l.spk_error_sweep_workspace.restype = ctypes.c_size_t
         l.spk_error_sweep_workspace.argtypes = [_I, _I]
+        l.spk_scatter_f64_workspace.restype = ctypes.c_size_t
+        l.spk_scatter_f64_workspace.argtypes = [_L, _I]
         for name, sig in _SIGS.items():
             fn = getattr(l, name)
             fn.argtypes = sig
@@ -161,7 +169,7 @@ def has_experimental():
 
 def exported_symbols():
     return ["spk_version", "spk_last_error", "spk_conv_wgrad_workspace", "spk_bn_finalize_workspace", "spk_gemm_workspace",
-            "spk_sort_trials_workspace", "spk_error_sweep_workspace"] + list(_SIGS)
+            "spk_sort_trials_workspace", "spk_error_sweep_workspace", "spk_scatter_f64_workspace"] + list(_SIGS)
 
 
 def ptr(t):

@@ -1131,3 +1131,94 @@ def error_sweep(score, label, order, costs):
     call("spk_error_sweep", ptr(score), ptr(label), ptr(order), ptr(cd) if P else None, P, ptr(out_d), ptr(out_i), ptr(ws), T,
          stream())
     return out_d, out_i
+
+
+# ---- PLDA back end (csrc/plda.hip) ---------------------------------------------------------------------------------------------
+def _f64_flag(t):
+    assert t.dtype in (torch.float32, torch.float64), t.dtype
+    return 1 if t.dtype == torch.float64 else 0
+
+
+def _f64_or_none(t, n):
+    assert t is None or (t.dtype == torch.float64 and t.numel() == n and t.is_contiguous()), "a double[%d] table or None" % n
+    return ptr(t)
+
+
+def _rows_ld(t):
+    """(device pointer, row pitch) of a 2-D float table whose rows are contiguous but may be pitched; one row has no pitch"""
+    if t.shape[0] == 1:
+        assert t.is_cuda and t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1), "libspkhip takes rows of unit stride only"
+        return t.data_ptr(), t.shape[1]
+    return _ptr_rows(t), t.stride(0)
+
+
+def scatter_slab_rows(N):
+    """rows per slab of spk_scatter_f64 for N rows"""
+    return hip.lib().spk_scatter_slab_rows(int(N))
+
+
+def scatter_f64(X, mu=None, w=None):
+    """X [N][D] float32 / float64 (rows may be pitched), mu [D] and w [N] float64 or None -> C [D][D] float64 =
+    sum_i w_i (x_i - mu)(x_i - mu)^T, symmetric bit for bit and the same bits on every run."""
+    N, D = X.shape
+    ws_bytes = hip.lib().spk_scatter_f64_workspace(N, D)
+    if ws_bytes == 0:
+        raise ValueError("scatter_f64: N=%d, D=%d out of range (1 <= D <= 512)" % (N, D))
+    C = torch.empty(D, D, device=X.device, dtype=torch.float64)
+    ws = torch.empty(ws_bytes // 8, device=X.device, dtype=torch.float64)
+    call("spk_scatter_f64", _rows_ld(X)[0], _f64_flag(X), _rows_ld(X)[1], _f64_or_none(mu, D),
+         _f64_or_none(w, N), ptr(C), ptr(ws), N, D, stream(), flops=2.0 * N * D * D, nbytes=float(N * D * X.element_size()))
+    return C
+
+
+def segment_sum_f64(X, seg_off, rows=None, mean=False):
+    """X [N][D] float32 / float64, seg_off [K+1] int32, rows int32 (grouped row indices) or None (the rows themselves) ->
+    (sums - with `mean` the means - [K][D] float64, counts [K] int32)"""
+    N, D = X.shape
+    K = seg_off.numel() - 1
+    assert seg_off.dtype == torch.int32 and (rows is None or rows.dtype == torch.int32)
+    out = torch.empty(K, D, device=X.device, dtype=torch.float64)
+    count = torch.empty(K, device=X.device, dtype=torch.int32)
+    call("spk_segment_sum_f64", _rows_ld(X)[0], _f64_flag(X), _rows_ld(X)[1], ptr(rows), ptr(seg_off), ptr(out), ptr(count),
+         1 if mean else 0, K, D, stream())
+    return out, count
+
+
+def affine_lennorm(X, A=None, b=None, q=None, scale=False, out_dtype=torch.float32, out=None):
+    """Y[i] = s_i (A x_i + b): X [N][Di] float32 / float64, A [Do][Di] float64 (None: identity), b [Do], q [Do] float64 or None;
+    scale: s_i = sqrt(Do / sum_j y_j^2 q_j) (1 for a row whose sum is 0) -> Y [N][Do] of out_dtype (float32 / float64), written into
+    `out` (a contiguous [N][Do] tensor, e.g. a row range of a larger table) when given."""
+    N, Di = X.shape
+    Do = Di if A is None else A.shape[0]
+    assert A is None or (A.dtype == torch.float64 and A.shape == (Do, Di))
+    assert out_dtype in (torch.float32, torch.float64)
+    Y = torch.empty(N, Do, device=X.device, dtype=out_dtype) if out is None else out
+    assert Y.shape == (N, Do) and Y.dtype == out_dtype and Y.is_contiguous()
+    call("spk_affine_lennorm", _rows_ld(X)[0], _f64_flag(X), _rows_ld(X)[1], ptr(A), _f64_or_none(b, Do), _f64_or_none(q, Do),
+         1 if scale else 0, ptr(Y), 1 if out_dtype == torch.float64 else 0, N, Di, Do, stream(),
+         flops=0.0 if A is None else 2.0 * N * Di * Do)
+    return Y
+
+
+def plda_posterior_rows(mt, count, psi):
+    """mt [K][D] float64, count [K] int32, psi [D] float64 -> (w, mt - w) float64 [K][D] (include/spkhip.h)"""
+    K, D = mt.shape
+    assert mt.dtype == torch.float64 and count.dtype == torch.int32 and count.numel() == K and psi.dtype == torch.float64
+    w, r = torch.empty_like(mt), torch.empty_like(mt)
+    call("spk_plda_posterior_rows", ptr(mt), ptr(count), ptr(psi), ptr(w), ptr(r), K, D, stream())
+    return w, r
+
+
+def plda_llr(en, te, ia, ib, psi, count, tab_count, tab_log):
+    """en [n_en][D], te [n_te][D], psi [D] float64; ia / ib int32 [T] (validated by the caller); count int32 [n_en] or None (1);
+    tab_count int32 [U], tab_log float64 [U][2] -> float32 [T]"""
+    T, D = ia.numel(), en.shape[1]
+    assert en.dtype == torch.float64 and te.dtype == torch.float64 and psi.dtype == torch.float64 and te.shape[1] == D
+    assert ia.dtype == torch.int32 and ib.dtype == torch.int32 and ib.numel() == T and psi.numel() == D
+    assert count is None or (count.dtype == torch.int32 and count.numel() == en.shape[0])
+    U = tab_count.numel()
+    assert tab_count.dtype == torch.int32 and tab_log.dtype == torch.float64 and tab_log.numel() == 2 * U
+    out = torch.empty(T, device=en.device, dtype=torch.float32)
+    call("spk_plda_llr", ptr(en), ptr(te), ptr(ia), ptr(ib), ptr(psi), ptr(count), ptr(tab_count), ptr(tab_log), U, ptr(out), T, D,
+         en.shape[0], te.shape[0], stream())
+    return out

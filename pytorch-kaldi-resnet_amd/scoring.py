@@ -348,10 +348,24 @@ def min_dcf(scores, labels, p_target=0.01, c_miss=1, c_fa=1, backend="host"):
 
 
 def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_stats=None, costs=DEFAULT_COSTS, backend="host",
-                     score_path=None):
+                     score_path=None, plda=None, transform=None, num_utts=None):
     """The whole scoring stage in one process: cosine per trial, adaptive S-norm when both statistics tables are given
     (utt -> (mean, std), topk_mean_std / read_mean_std), error-rate sweep.  -> the error_rates report.  On `hip` the embeddings
-    and the index arrays go up and only the report comes down (and the scores, if score_path asks for them)."""
+    and the index arrays go up and only the report comes down (and the scores, if score_path asks for them).
+    plda = (mean, transform, psi) with the LDA `transform` (and optionally num_utts: utt -> enrolment count) scores the trials with
+    the PLDA back end instead of the cosine (plda.plda_score); S-norm does not apply to it."""
+    if plda is not None:
+        from . import plda as plda_mod
+        assert transform is not None, "the plda back end needs the LDA transform"
+        assert enroll_stats is None and test_stats is None, "S-norm is a cosine back end"
+        scores, labels = plda_mod.plda_score(enroll, test, trials_path, mean, transform, plda, num_utts=num_utts,
+                                             score_path=score_path, backend=backend, return_device=True)
+        if backend == "hip":
+            import torch
+            scores = scores.to(torch.float64)            # (widening: exact)
+        else:
+            scores = scores.astype(np.float64)
+        return error_rates(scores, labels, costs, backend)
     pairs, labels, ia, ib, me, mt = _read_trials(trials_path, enroll, test, mean)
     snorm = enroll_stats is not None or test_stats is not None
     if snorm:

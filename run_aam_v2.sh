@@ -36,3 +36,9 @@ python scripts/compute_topk_mean_std.py --backend $impl --mean $dir/backend/mean
   --ark-file $dir/backend/test.iv --mean-std-file $dir/backend/topk_mean_std > $dir/log/compute_topk_mean_std.log
 ./test.sh $dir/backend $dir/backend cosine 12 $datadir/trials
 ./test.sh $dir/backend $dir/backend snorm 12 $datadir/trials
+# the PLDA back end of the reference (LDA to 200 dimensions, PLDA on the projected, length-normalised training embeddings):
+python scripts/compute_lda.py --backend $impl --total-covariance-factor 0.0 --dim 200 --mean $dir/backend/mean.vec \
+  $dir/backend/train.iv $datadir/utt2spk $dir/backend/transform.mat > $dir/log/lda.log
+python scripts/compute_plda.py --backend $impl --mean $dir/backend/mean.vec $dir/backend/train.iv $datadir/utt2spk \
+  $dir/backend/transform.mat $dir/backend/plda > $dir/log/plda.log
+./test.sh $dir/backend $dir/backend plda 12 $datadir/trials

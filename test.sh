@@ -1,9 +1,11 @@
 #!/bin/bash
 # Scoring and report of the reference's test.sh (steps 12 and 13): cosine scores, optional adaptive S-norm, then the
 # three-line report eer_<backend>[_adapt_snorm] (EER, minDCF at p-target 0.01 and 0.001).
-# usage: ./test.sh <modeldir> <dir> <backend: cosine|snorm> <stage> [trials]
-#   <modeldir> holds mean.vec and test.iv; <dir> receives the scores and the report and, for snorm, holds topk_mean_std.
-#   SPK_SCORE_BACKEND=hip runs every step on the GPU (default host: the same files, byte for byte).
+# usage: ./test.sh <modeldir> <dir> <backend: cosine|snorm|plda> <stage> [trials]
+#   <modeldir> holds mean.vec and test.iv (for plda also transform.mat and plda, from scripts/compute_lda.py and
+#   scripts/compute_plda.py); <dir> receives the scores and the report and, for snorm, holds topk_mean_std.
+#   SPK_SCORE_BACKEND=hip runs every step on the GPU (default host: the same files, byte for byte; plda: the same
+#   scores to the rounding of its float32 stages).
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
 
@@ -15,18 +17,30 @@ voxceleb1_trials=${5:-data/test/trials_e}
 impl=${SPK_SCORE_BACKEND:-host}
 
 if [ "$backend" == "plda" ]; then
-  echo "plda scoring is not part of this project: see DESIGN.md section 7" >&2
-  exit 1
-fi
-if [ "$backend" != "cosine" ] && [ "$backend" != "snorm" ]; then
-  echo "usage: $0 <modeldir> <dir> <cosine|snorm> <stage> [trials]" >&2
+  if [ ! -f "$modeldir/plda" ] || [ ! -f "$modeldir/transform.mat" ]; then
+    echo "plda scoring needs $modeldir/transform.mat and $modeldir/plda: train them with scripts/compute_lda.py and" >&2
+    echo "scripts/compute_plda.py (Kaldi's own binaries stay out of this project: see DESIGN.md section 7)" >&2
+    exit 1
+  fi
+elif [ "$backend" != "cosine" ] && [ "$backend" != "snorm" ]; then
+  echo "usage: $0 <modeldir> <dir> <cosine|snorm|plda> <stage> [trials]" >&2
   exit 1
 fi
 
 score_file=scores_$backend
 eer_file=eer_$backend
 mkdir -p $dir/log
-if [ $stage -le 12 ]; then
+if [ $stage -le 12 ] && [ $backend == 'plda' ]; then
+  echo "plda scoring..."
+  python $here/scripts/plda_score.py \
+      --mean $modeldir/mean.vec \
+      --transform $modeldir/transform.mat \
+      --plda $modeldir/plda \
+      --enroll $modeldir/test.iv \
+      --test $modeldir/test.iv \
+      --trials $voxceleb1_trials \
+      --score-file $dir/$score_file --backend $impl > $dir/log/test_scoring.log
+elif [ $stage -le 12 ]; then
   echo "cosine scoring..."
   python $here/scripts/cosine_score.py \
       --mean $modeldir/mean.vec \
