@@ -197,6 +197,23 @@ int spk_conv_wgrad(const float* x, const float* dy, float* dw, float* partial, c
                    SPK_DY_PRESPLIT) */, const unsigned* x_amax /* split 3, required: the same for the (transformed) x operand:
                    its absmax or a bound (spk_bn_finalize est_out / spk_affine_estimate) */, void* stream);
 
+/* Which instance of its kernel a launch takes.  The flag combinations of the training step are compiled as variants in which the
+ * flag word is a template argument (the per-pass and per-item branches fold away, results bit-identical); everything else runs
+ * the generic instance that reads the word from its argument block.  These are the pure host functions the launchers themselves
+ * call (no GPU needed).  Return value: the variant's template argument (>= 0), or -1 = generic.  Environment SPK_FL_VARIANTS=0
+ * (read once per process; default 1) makes every launch generic: A/B runs and identity tests on one build.
+ * spk_conv_variant_of: MT, NT, split, flags as given to spk_conv_mfma / spk_conv_mfma_len; ptrs: which optional operands are
+ * given (SPK_PTR_* bits).  spk_wgrad_variant_of: arguments as given to spk_conv_wgrad; conv_wgrad_split_kernel only (launches of
+ * the other weight-gradient kernels return -1). */
+#define SPK_PTR_ADD_MASK 1
+#define SPK_PTR_BN_MASK 2
+#define SPK_PTR_IN_MASK 4
+#define SPK_PTR_IN_ACT 8
+#define SPK_PTR_BN_ACT 16
+#define SPK_PTR_SIDE_DZ 32
+int spk_conv_variant_of(int MT, int NT, int split, int flags, int ptrs);
+int spk_wgrad_variant_of(int ksize, int stride, int TH, int TW, int WN, int split, int flags);
+
 /* Stem Conv2d(1,32,3,1,1,bias=False) (scripts/model.py:210,249): x [B][F][T] -> out [B][F][T][32];
  * stats (EPI_STATS): [spk_stem_fwd_blocks()][32][2]. */
 int spk_stem_fwd_blocks(int B, int F, int T);

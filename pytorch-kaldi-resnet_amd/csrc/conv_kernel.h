@@ -104,6 +104,12 @@ struct ConvArgs {
                       // per 32-channel chunk is too short to amortise a staging phase
 };
 
+// pointer pattern of a launch (spk_common.h, SPK_PTR_*): the second key, beside the flag word, of the variant selection
+static inline int conv_ptr_pattern(const ConvArgs& a) {
+    return (a.add_mask ? SPK_PTR_ADD_MASK : 0) | (a.bn_mask ? SPK_PTR_BN_MASK : 0) | (a.in_mask ? SPK_PTR_IN_MASK : 0) |
+           (a.in_act ? SPK_PTR_IN_ACT : 0) | (a.bn_act ? SPK_PTR_BN_ACT : 0) | (a.side_dz ? SPK_PTR_SIDE_DZ : 0);
+}
+
 // PIPE (f16x3, nine taps, one plane per chunk): the staging of chunk ch + 1 is woven into the K loop of chunk ch IN THE SAME
 // WAVE - after the matrix instructions of tap t the wave converts and writes staging item t of the next chunk into the other
 // half of a two-slot LDS tile (its global load was issued PIPE_D taps earlier), one barrier per chunk.  Why in the same wave:

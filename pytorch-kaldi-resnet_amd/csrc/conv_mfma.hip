@@ -212,6 +212,16 @@ static int conv_mfma_entry(const float* in, const float* wpk, float* out, const 
     return -1;
 }
 
+// which compile-time flag instance (conv_kernel.h, FL) a spk_conv_mfma / spk_conv_mfma_len launch with this tile, operand mode,
+// flag word and pointer pattern (SPK_PTR_* bits) takes, routed as the entry routes the launch: FL, or -1 = the generic instance
+extern "C" int spk_conv_variant_of(int MT, int NT, int split, int flags, int ptrs) {
+    if (flags & SPK_CONV_WS) return -1;
+    const int ck = (flags & SPK_CONV_CK32) ? 32 : SPK_SPLIT_CK;
+    flags &= ~SPK_CONV_CK32;
+    if (flags & SPK_CONV_PIPE) return split == 3 ? spk_pipe_variant_of(MT, NT, flags & ~SPK_CONV_PIPE, ptrs) : -1;
+    return split ? spk_split_variant_of(MT, NT, split, ck, flags, ptrs) : -1;
+}
+
 extern "C" int spk_conv_mfma(const float* in, const float* wpk, float* out, const float* in_scale,
                              const float* in_shift, const float* epi_scale, const float* epi_shift,
                              const float* epi_add, const float* in_raw, const float* in_act, const float* in_bn4,

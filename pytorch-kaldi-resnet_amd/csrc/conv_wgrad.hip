@@ -220,14 +220,35 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a) {
     }
 }
 
-// partial [nslab][ntaps][Cin][Cout] -> dW OIHW [Cout][Cin][ntaps]; optional accumulate
+// partial [nslab][ntaps][Cin][Cout] -> dW OIHW [Cout][Cin][ntaps]; optional accumulate.
+// One thread per weight walks the slabs: four chains, s_j += slab[k] for k = j (mod 4) in ascending k, leftover slabs (nslab not
+// a multiple of 4) to s_0, result (s0 + s1) + (s2 + s3).  The walk is bound by the latency of its dependent trips, not by bytes,
+// so WGRAD_REDUCE_NF slab loads (a multiple of 4) are issued before they are consumed - the additions keep their order.
+#ifndef WGRAD_REDUCE_NF
+#define WGRAD_REDUCE_NF 16
+#endif
 __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int nslab, int ntaps,
                                     int Cin, int Cout, int accumulate) {
+    static_assert(WGRAD_REDUCE_NF % 4 == 0, "the four chains take k = j (mod 4)");
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int total = ntaps * Cin * Cout;
     if (idx >= total) return;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int k = 0;
+    if constexpr (WGRAD_REDUCE_NF > 4) {
+        for (; k + WGRAD_REDUCE_NF <= nslab; k += WGRAD_REDUCE_NF) {
+            float v[WGRAD_REDUCE_NF];
+#pragma unroll
+            for (int u = 0; u < WGRAD_REDUCE_NF; ++u) v[u] = partial[(size_t)(k + u) * total + idx];
+#pragma unroll
+            for (int u = 0; u < WGRAD_REDUCE_NF; u += 4) {
+                s0 += v[u + 0];
+                s1 += v[u + 1];
+                s2 += v[u + 2];
+                s3 += v[u + 3];
+            }
+        }
+    }
     for (; k + 4 <= nslab; k += 4) {
         s0 += partial[(size_t)(k + 0) * total + idx];
         s1 += partial[(size_t)(k + 1) * total + idx];
@@ -270,6 +291,13 @@ extern "C" int spk_wgrad_reduce(const float* partial, float* dw, int nslab, int 
                        ntaps, Cin, Cout, accumulate);
     SPK_LAUNCH_CHECK("spk_wgrad_reduce");
     return 0;
+}
+
+// which instance of conv_wgrad_split_kernel a spk_conv_wgrad launch with these arguments takes: its VAR, or -1 = the generic
+// instance (also for the launches that go to another kernel family: grouped, 16x16x32, opt-in forms, fp32 operands)
+extern "C" int spk_wgrad_variant_of(int ksize, int stride, int TH, int TW, int WN, int split, int flags) {
+    if (flags & (SPK_WGRAD_GROUPS | SPK_WGRAD_M16 | SPK_CONV_PIPE | SPK_CONV_WS)) return -1;
+    return spk_wgrad_split_variant_of(ksize, WN, split, flags, ((TH - 1) * stride + ksize) * ((TW - 1) * stride + ksize));
 }
 
 extern "C" int spk_conv_wgrad(const float* x, const float* dy, float* dw, float* partial, const float* in_scale,

@@ -584,6 +584,47 @@ int spk_launch_wgrad_ws(const WgradArgs& a, int WN, hipStream_t st) {
 
 #endif   // SPK_EXPERIMENTAL
 
+// ---- compile-time variants of the staging switches (VAR), f16x3 mode: the weight gradients of the training step that this
+// kernel family runs.  3x3, WN 1, the large prefetch window: layer 1 (32 channels) with pair dY, with and without the fused
+// input BatchNorm + ReLU.  3x3 stride 2, WN 2, the large window, pair dY, and 1x1 stride 2, WN 2, the small window, plain dY:
+// the first convolution and the shortcut of a downsample block.
+static constexpr bool wgrad_split_has_var(int ntaps, int WN, bool small, int var) {
+    if (ntaps == 9 && WN == 1 && !small) return var == 2 || var == 3;
+    if (ntaps == 9 && WN == 2 && !small) return var == 2;
+    if (ntaps == 1 && WN == 2 && small) return var == 0;
+    return false;
+}
+
+int spk_wgrad_split_variant_of(int ksize, int WN, int split, int flags, int halo_pix) {
+#ifdef SPK_NO_FL_VARIANTS
+    return -1;
+#else
+    if (!spk_fl_variants_enabled() || split != 3) return -1;
+    const int var = ((flags & SPK_IN_AFFINE_RELU) ? 1 : 0) | ((flags & SPK_DY_PRESPLIT) ? 2 : 0);
+    return wgrad_split_has_var(ksize * ksize, WN, halo_pix <= 32 * 4, var) ? var : -1;
+#endif
+}
+
+template <int NTAPS, int WK, int WN, bool SMALL>
+static bool launch_var(int var, const WgradArgs& a, dim3 grid, size_t lds_bytes, hipStream_t st) {
+#ifndef SPK_NO_FL_VARIANTS
+#define VAR_CASE(V)                                                                                                              \
+    case V:                                                                                                                      \
+        if constexpr (wgrad_split_has_var(NTAPS, WN, SMALL, V)) {                                                                \
+            hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, SMALL ? 4 : WGRAD_NX, V>), grid, dim3(256), lds_bytes, st, a); \
+            return true;                                                                                                         \
+        }                                                                                                                        \
+        break;
+    switch (var) {
+        VAR_CASE(0)
+        VAR_CASE(2)
+        VAR_CASE(3)
+    }
+#undef VAR_CASE
+#endif
+    return false;
+}
+
 template <int NTAPS, int WK, int WN>
 static int launch_one(const WgradArgs& a, int split, hipStream_t st) {
     const int npix_pad = ((a.TH * a.TW + 15) >> 4) << 4;
@@ -595,21 +636,13 @@ static int launch_one(const WgradArgs& a, int split, hipStream_t st) {
     dim3 grid(a.nsplit * (a.Cin / 32) * (a.Cout / (32 * WN)));       // see wgrad_block
     const bool small = a.halo_h * a.halo_w <= 32 * 4;
     if (split == 3) {
-        const int var = ((a.flags & SPK_IN_AFFINE_RELU) ? 1 : 0) | ((a.flags & SPK_DY_PRESPLIT) ? 2 : 0);
-        // the layer-1 weight gradients of the training step (3x3, 32 channels: WK 4, WN 1, the large prefetch window) with pair dY
-        if constexpr (NTAPS == 9 && WK == 4 && WN == 1) {
-            if (!small && var == 3) {
-                hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, WGRAD_NX, 3>), grid, dim3(256), lds_bytes, st, a);
-                SPK_LAUNCH_CHECK("spk_conv_wgrad(split)");
-                return 0;
+        const int var = spk_wgrad_split_variant_of(a.KW, WN, split, a.flags, a.halo_h * a.halo_w);
+        if (var >= 0) {
+            if (!(small ? launch_var<NTAPS, WK, WN, true>(var, a, grid, lds_bytes, st) : launch_var<NTAPS, WK, WN, false>(var, a, grid, lds_bytes, st))) {
+                spk_set_error("spk_conv_wgrad(split): no instance of variant %d for %d taps, WN=%d", var, NTAPS, WN);
+                return -1;
             }
-            if (!small && var == 2) {
-                hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, WGRAD_NX, 2>), grid, dim3(256), lds_bytes, st, a);
-                SPK_LAUNCH_CHECK("spk_conv_wgrad(split)");
-                return 0;
-            }
-        }
-        if (small) hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, 4>), grid, dim3(256), lds_bytes, st, a);
+        } else if (small) hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, 4>), grid, dim3(256), lds_bytes, st, a);
         else hipLaunchKernelGGL((conv_wgrad_split_kernel<NTAPS, WK, WN, 3, WGRAD_NX>), grid, dim3(256), lds_bytes, st, a);
     } else if constexpr (NTAPS == 9) {
         if (split == 6) {

@@ -53,6 +53,26 @@ enum {
 
 static inline int spk_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- which compile-time instance a launch takes (host).  The launchers and the C ABI (spk_conv_variant_of /
+// spk_wgrad_variant_of) call the same pure functions: (tile, flag word, pointer pattern) -> the FL / VAR template argument, or -1
+// = the generic instance that reads everything from the argument block.
+// pointer pattern of a convolution launch beside its flag word: which optional operands are given
+enum {
+    SPK_PTR_ADD_MASK = 1,
+    SPK_PTR_BN_MASK = 2,
+    SPK_PTR_IN_MASK = 4,
+    SPK_PTR_IN_ACT = 8,
+    SPK_PTR_BN_ACT = 16,
+    SPK_PTR_SIDE_DZ = 32
+};
+bool spk_fl_variants_enabled();      // err.cpp: environment SPK_FL_VARIANTS != "0", read once per process
+// conv_split.hip: conv_mfma_kernel<MT, NT, ., split, FL, ck>; flags: the word the kernel sees (no SPK_CONV_CK32)
+int spk_split_variant_of(int MT, int NT, int split, int ck, int flags, int ptrs);
+// conv_pipe.hip: conv_pipe_kernel<MT, NT, ..., FL>; flags: the entry's word without SPK_CONV_PIPE (SPK_CONV_M16 still in it)
+int spk_pipe_variant_of(int MT, int NT, int flags, int ptrs);
+// conv_wgrad_split.hip: conv_wgrad_split_kernel<ksize^2, 4 / WN, WN, split, NX, VAR>
+int spk_wgrad_split_variant_of(int ksize, int WN, int split, int flags, int halo_pix);
+
 // ---- bf16 operand splitting (device): an fp32 value is the exact sum of three bf16 terms (3 x 8 significand bits)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #ifdef __HIPCC__

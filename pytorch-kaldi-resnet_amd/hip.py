@@ -17,6 +17,7 @@ CONV_CK32 = 1 << 23     # fused BatchNorm-backward data gradient at Cin = 32 (f1
 WGRAD_NOSHIFT = 1 << 18  # 3x3 grouped weight gradient: plain K loop instead of the shifted-window form (A/B)
 WGRAD_M16 = 1 << 19      # 3x3 grouped weight gradient on 16x16x32 with dy (a pair tensor) staged by LDS DMA
 EPI_WMASK = 1 << 24     # length-masked epilogue: outputs at width x >= wlen[b] stored as 0 (spk_conv_mfma_len, spk_stem_conv_fwd_len)
+PTR_ADD_MASK, PTR_BN_MASK, PTR_IN_MASK, PTR_IN_ACT, PTR_BN_ACT, PTR_SIDE_DZ = 1, 2, 4, 8, 16, 32   # spk_conv_variant_of `ptrs`
 MASK_NONE, MASK_ACT, MASK_RAW, MASK_BITS = 0, 1, 2, 3
 
 _P = ctypes.c_void_p
@@ -40,6 +41,8 @@ _SIGS = {
     "spk_conv_wgrad": [_P] * 6 + [_I] * 16 + [_P, _P, _P],
     "spk_conv_wgrad_limits": [_I, _IP, _IP],
     "spk_wgrad_reduce": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "spk_conv_variant_of": [_I, _I, _I, _I, _I],       # host only: the FL / VAR instance a launch takes, -1 = generic
+    "spk_wgrad_variant_of": [_I, _I, _I, _I, _I, _I, _I],
     "spk_stem_fwd_blocks": [_I, _I, _I],
     "spk_stem_conv_fwd": [_P] * 6 + [_I] * 4 + [_P, _P],
     "spk_stem_conv_fwd_len": [_P] * 6 + [_I] * 4 + [_P, _P, _P],
