@@ -464,6 +464,33 @@ int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long* utt_ids, 
                  const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither, float preemph, int remove_dc,
                  float energy_floor, int use_energy, int htk_compat, unsigned long long seed, float* feats, float* log_energy,
                  int* T_out, int Tcap, void* stream);
+/* The span form of the two launches above, for training from audio.  Replaces the feature directories that
+ * stages 3 and 4 of the reference's feature_pre.sh:178-196 write (fbank of the augmented copies, then the combined set once more
+ * through local/nnet3/xvector/prepare_feats_for_egs.sh:68-71) only for the training loader to crop them: the frames of a crop are
+ * computed from the audio of the crop.  Row b of wave [B][Nmax] holds samples first[b] .. first[b] + nsamp[b] - 1 of an utterance
+ * of total[b] samples; the launch computes frames frame0[b] .. frame0[b] + nframes[b] - 1 OF THAT UTTERANCE into columns
+ * 0 .. nframes[b] - 1 (nframes clipped to the utterance's frame count; T_out[b] = the columns written, zeros up to Tcap).  The
+ * snip_edges = false reflection is about 0 and total[b], the dither is keyed by the frame's index in the utterance: column j equals
+ * column frame0[b] + j of the whole-utterance launch bit for bit.  A computed frame must not touch a sample outside the row after
+ * reflection (the caller checks; the kernel clamps such a read into the row).  first / total: int64, frame0 / nframes: int32,
+ * all device arrays of B. */
+int spk_fbank_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
+                       const int* nframes, const long long* utt_ids, int B, long long Nmax, const float* window, const float* twiddle,
+                       const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P, int F, int snip_edges,
+                       float dither, float preemph, int remove_dc, float energy_floor, unsigned long long seed, float* feats,
+                       float* log_energy, int* T_out, int Tcap, void* stream);
+/* the MFCC of a span (feature_pre.sh:178-196 run with local/make_mfcc.sh, prepare_feats_for_egs.sh:68-71): as above, with the
+ * cepstral arguments of spk_mfcc_fwd */
+int spk_mfcc_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
+                      const int* nframes, const long long* utt_ids, int B, long long Nmax, const float* window, const float* twiddle,
+                      const float* mel_w, const int* mel_lo, const int* mel_off, const float* dct, const float* lifter, int L, int S,
+                      int P, int F, int C, int snip_edges, float dither, float preemph, int remove_dc, float energy_floor,
+                      int use_energy, int htk_compat, unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap,
+                      void* stream);
+/* 16-bit PCM as it lies in a WAV file (what the readers of compute-fbank-feats in feature_pre.sh:178-196 convert on the host):
+ * out[b][s] = (float) pcm[b][s] for s < count[b], 0 up to Nmax - float32 at int16 scale, the input of the launches above */
+int spk_pcm16_to_f32(const short* pcm /*[B][Nmax]*/, const int* count /*[B]*/, int B, long long Nmax, float* out /*[B][Nmax]*/,
+                     void* stream);
 /* out[f][j] = the N(0,1) draw spk_fbank_fwd / spk_mfcc_fwd adds (times dither) at position j of frame frame0 + f of utterance utt_id */
 int spk_fbank_dither_noise(float* out /*[nframes][L]*/, long long utt_id, unsigned long long seed, int frame0, int nframes, int L,
                            void* stream);

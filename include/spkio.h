@@ -62,6 +62,12 @@ int spk_wav_probe(int n, const char* const* paths, int expect_rate, int32_t* rat
 /* out[b][s] = sample s of file b at int16 scale for s < nsamp[b], 0 up to Nmax; pread() on `nthreads` threads */
 int spk_wav_read_padded(int B, const char* const* paths, const int64_t* data_offsets, const int64_t* nsamp, int64_t Nmax, float* out,
                         int nthreads);
+/* the reader of training from audio (ingest.WavTrainLoader; replaces the feature directories that stages 3 and 4 of the reference's
+ * feature_pre.sh:170-197 write only to be cropped): out[b][s] = sample first[b] + s of file b as it lies in the file (int16) for
+ * s < count[b], 0 up to Nmax.  Only the span is read, pread() on `nthreads` threads.  first < 0, first + count > nsamp and
+ * count > Nmax are refused with an error naming the file. */
+int spk_wav_read_span(int B, const char* const* paths, const int64_t* data_offsets, const int64_t* nsamp, const int64_t* first,
+                      const int64_t* count, int64_t Nmax, int16_t* out, int nthreads);
 #ifdef __cplusplus
 }
 #endif

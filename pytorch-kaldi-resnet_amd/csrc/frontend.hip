@@ -14,6 +14,11 @@
 // for operation; a wave then keeps its F log-mels in its own FFT buffer (free once the real split has been read), and lane k sums
 // row k of the DCT (staged once per workgroup in LDS, row stride odd) over them in ascending order, applies the lifter, and the
 // energy / HTK order rules pick the output row.  The tile has C + 1 rows: the cepstra, then the log energies.
+//
+// spk_fbank_span_fwd / spk_mfcc_span_fwd (training from audio; they replace the feature directories of the
+// reference's feature_pre.sh:178-196 and prepare_feats_for_egs.sh:68-71): the same template again, for rows that hold a span of
+// samples of an utterance; a frame is computed from its position in the utterance, so column j is bit for bit column frame0 + j of
+// the whole-utterance launch.  spk_pcm16_to_f32 converts the 16-bit samples as read from the file.
 #include "spk_common.h"
 
 namespace {
@@ -85,16 +90,38 @@ struct FbankArgs {
     int C, Fp, use_energy, htk;     // Fp: row stride of the DCT copy in LDS (odd)
 };
 
+// the span form (spk_fbank_span_fwd, spk_mfcc_span_fwd): row b of `wave` holds samples [first[b], first[b] + nsamp[b]) of an
+// utterance of total[b] samples, and the launch computes frames frame0[b] .. frame0[b] + nframes[b] - 1 of THAT utterance.  The
+// fields of FbankArgs keep their place, so the kernel arguments of the whole-utterance kernels are what they were
+struct SpanArgs : FbankArgs {
+    const long long* first;   // [B] sample of the utterance that row b starts with
+    const long long* total;   // [B] samples of the utterance
+    const int* frame0;        // [B] first frame computed (column 0 of the output)
+    const int* nframes;       // [B] frames computed (clipped to the utterance's frame count)
+};
+
 // one tile of one utterance.  MFCC = false: the log-mel tile (fbank_kernel); true: its DCT, liftered (mfcc_kernel).  R output
-// rows of a.feats
-template <bool MFCC>
-__device__ __forceinline__ void frontend_tile(const FbankArgs& a) {
+// rows of a.feats.  SPAN: A is SpanArgs, the tile's frames are frames f0 + t of the utterance (reflection about 0 and total[b],
+// dither keyed by the absolute frame) and column t of the output is frame f0 + t; per frame the same operations in the same order
+template <bool MFCC, bool SPAN = false, class A = FbankArgs>
+__device__ __forceinline__ void frontend_tile(const A& a) {
     extern __shared__ float fe_lds[];
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * a.FT;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long long N = min((long long)a.nsamp[b], a.Nmax);
-    const int T = N > 0 ? fe_frames(N, a.L, a.S, a.snip) : 0;
+    long long N, first = 0, navail = 0;     // N: samples of the utterance; the row holds [first, first + navail) of them
+    int T, f0 = 0;                          // T: frames this row computes, f0: the frame of the utterance that column 0 is
+    if constexpr (SPAN) {
+        N = a.total[b];
+        first = a.first[b];
+        navail = min((long long)a.nsamp[b], a.Nmax);
+        f0 = a.frame0[b];
+        const int Tu = N > 0 ? fe_frames(N, a.L, a.S, a.snip) : 0;
+        T = (navail > 0 && f0 >= 0) ? max(min(a.nframes[b], Tu - f0), 0) : 0;
+    } else {
+        N = min((long long)a.nsamp[b], a.Nmax);
+        T = N > 0 ? fe_frames(N, a.L, a.S, a.snip) : 0;
+    }
     if (blockIdx.x == 0 && tid == 0) a.T_out[b] = T;
     const int R = MFCC ? a.C : a.F;
     float* frow = a.feats + (size_t)b * R * a.Tcap;
@@ -112,12 +139,17 @@ __device__ __forceinline__ void frontend_tile(const FbankArgs& a) {
     float* otile = span + a.span;                           // [R + 1][FT]: feature rows, then the log energies
     float* dct = otile + (R + 1) * a.FT;                    // [C][Fp] (MFCC only)
     const float* wv = a.wave + (size_t)b * a.Nmax;
-    const long long s0 = (long long)t0 * a.S - (a.snip ? 0 : (a.L / 2 - a.S / 2));
+    const long long s0 = ((long long)t0 + f0) * a.S - (a.snip ? 0 : (a.L / 2 - a.S / 2));
     for (int i = tid; i < a.span; i += FE_THREADS) {
         long long s = s0 + i;
         if (s < 0) s = -s - 1;                      // reflected once (snip_edges = false)
         if (s >= N) s = 2 * N - 1 - s;
-        s = s < 0 ? 0 : (s >= N ? N - 1 : s);       // only reached for N < L, which the API refuses: stay in bounds
+        if constexpr (SPAN) {                       // the utterance's sample s lies at s - first of the row; a sample outside the
+            s -= first;                             // row is only reached for frames the host wrapper refuses: stay in bounds
+            s = s < 0 ? 0 : (s >= navail ? navail - 1 : s);
+        } else {
+            s = s < 0 ? 0 : (s >= N ? N - 1 : s);   // only reached for N < L, which the API refuses: stay in bounds
+        }
         span[i] = wv[s];
     }
     if constexpr (MFCC)
@@ -135,7 +167,7 @@ __device__ __forceinline__ void frontend_tile(const FbankArgs& a) {
         float sum = 0.f;
         for (int j = lane; j < a.L; j += 64) {
             float v = x0[j];
-            if (a.dither != 0.f) v = fmaf(a.dither, fe_gauss(key, t, j), v);
+            if (a.dither != 0.f) v = fmaf(a.dither, fe_gauss(key, t + f0, j), v);      // keyed by the frame of the utterance
             fb[j] = v;
             sum += v;
         }
@@ -238,6 +270,35 @@ __device__ __forceinline__ void frontend_tile(const FbankArgs& a) {
 
 __global__ __launch_bounds__(FE_THREADS) void fbank_kernel(FbankArgs a) { frontend_tile<false>(a); }
 __global__ __launch_bounds__(FE_THREADS) void mfcc_kernel(FbankArgs a) { frontend_tile<true>(a); }
+__global__ __launch_bounds__(FE_THREADS) void fbank_span_kernel(SpanArgs a) { frontend_tile<false, true>(a); }
+__global__ __launch_bounds__(FE_THREADS) void mfcc_span_kernel(SpanArgs a) { frontend_tile<true, true>(a); }
+
+// 16-bit PCM as it lies in a WAV file -> float32 at int16 scale: out[b][s] = in[b][s] for s < count[b], 0 up to Nmax.  A thread
+// converts 8 samples (one 16-byte load, two 16-byte stores) when the row pitch and the bases allow, else one at a time
+__global__ __launch_bounds__(256) void pcm16_to_f32_kernel(const short* __restrict__ in, const int* __restrict__ count, long long Nmax,
+                                                           float* __restrict__ out, int vec) {
+    const int b = blockIdx.y;
+    const long long n = min(max((long long)count[b], 0ll), Nmax);
+    const short* src = in + (size_t)b * Nmax;
+    float* dst = out + (size_t)b * Nmax;
+    const long long s = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (s >= Nmax) return;
+    if (vec && s + 8 <= n) {                        // vec: Nmax % 8 == 0 and both bases 16-byte aligned, so every row is
+        const int4 q = *(const int4*)(src + s);
+        const int v[4] = {q.x, q.y, q.z, q.w};
+        float f[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f[2 * i] = (float)(short)(v[i] & 0xffff);
+            f[2 * i + 1] = (float)(short)(v[i] >> 16);
+        }
+        *(float4*)(dst + s) = make_float4(f[0], f[1], f[2], f[3]);
+        *(float4*)(dst + s + 4) = make_float4(f[4], f[5], f[6], f[7]);
+        return;
+    }
+    const long long e = min(s + 8, Nmax);
+    for (long long i = s; i < e; ++i) dst[i] = i < n ? (float)src[i] : 0.f;
+}
 
 // the noise fbank_kernel adds (before scaling by dither) to frames frame0 .. frame0 + nframes - 1 of utterance utt_id
 __global__ __launch_bounds__(256) void dither_noise_kernel(float* out, long long utt_id, unsigned long long seed, int frame0,
@@ -436,6 +497,79 @@ extern "C" int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long
     hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
                        (hipStream_t)stream, a);
     SPK_LAUNCH_CHECK("spk_mfcc_fwd");
+    return 0;
+}
+
+// the span fields of a checked FbankArgs
+static SpanArgs fe_span_args(const FbankArgs& f, const long long* first, const long long* total, const int* frame0, const int* nframes) {
+    SpanArgs a;
+    static_cast<FbankArgs&>(a) = f;
+    a.first = first; a.total = total; a.frame0 = frame0; a.nframes = nframes;
+    return a;
+}
+
+extern "C" int spk_fbank_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
+                                  const int* nframes, const long long* utt_ids, int B, long long Nmax, const float* window,
+                                  const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P,
+                                  int F, int snip_edges, float dither, float preemph, int remove_dc, float energy_floor,
+                                  unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
+    SPK_REQUIRE(wave && nsamp && first && total && frame0 && nframes && window && twiddle && mel_w && mel_lo && mel_off && feats &&
+                log_energy && T_out, "spk_fbank_span_fwd: null pointer");
+    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_fbank_span_fwd: dither != 0 needs utt_ids");
+    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_fbank_span_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
+    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_fbank_span_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
+    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_fbank_span_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
+    SPK_REQUIRE(F >= 1 && F <= 1024, "spk_fbank_span_fwd: num_mel_bins F=%d", F);
+    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
+                "spk_fbank_span_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
+    const int FT = spk_fbank_tile_frames(L, S, P, F);
+    SPK_REQUIRE(FT > 0, "spk_fbank_span_fwd: L=%d S=%d P=%d F=%d do not fit the LDS tile", L, S, P, F);
+    SpanArgs a = fe_span_args(fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither,
+                                      preemph, remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT),
+                              first, total, frame0, nframes);
+    const int lds = fe_lds_bytes(FT, L, S, P, F);
+    hipLaunchKernelGGL(fbank_span_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
+                       (hipStream_t)stream, a);
+    SPK_LAUNCH_CHECK("spk_fbank_span_fwd");
+    return 0;
+}
+
+extern "C" int spk_mfcc_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
+                                 const int* nframes, const long long* utt_ids, int B, long long Nmax, const float* window,
+                                 const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, const float* dct,
+                                 const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither, float preemph,
+                                 int remove_dc, float energy_floor, int use_energy, int htk_compat, unsigned long long seed,
+                                 float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
+    SPK_REQUIRE(wave && nsamp && first && total && frame0 && nframes && window && twiddle && mel_w && mel_lo && mel_off && dct && lifter &&
+                feats && log_energy && T_out, "spk_mfcc_span_fwd: null pointer");
+    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_mfcc_span_fwd: dither != 0 needs utt_ids");
+    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_mfcc_span_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
+    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_mfcc_span_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
+    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_mfcc_span_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
+    SPK_REQUIRE(F >= 1 && F <= P, "spk_mfcc_span_fwd: num_mel_bins F=%d (the log-mels of a frame reuse its FFT buffer of P=%d floats)", F, P);
+    SPK_REQUIRE(C >= 1 && C <= F, "spk_mfcc_span_fwd: num_ceps C=%d must be in [1, num_mel_bins F=%d]", C, F);
+    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
+                "spk_mfcc_span_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
+    const int FT = spk_mfcc_tile_frames(L, S, P, F, C);
+    SPK_REQUIRE(FT > 0, "spk_mfcc_span_fwd: L=%d S=%d P=%d F=%d C=%d do not fit the LDS tile", L, S, P, F, C);
+    FbankArgs f = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
+                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
+    f.dct = dct; f.lifter = lifter; f.C = C; f.Fp = F | 1; f.use_energy = use_energy ? 1 : 0; f.htk = htk_compat ? 1 : 0;
+    SpanArgs a = fe_span_args(f, first, total, frame0, nframes);
+    const int lds = (int)fe_mfcc_lds_bytes(FT, L, S, P, F, C);
+    hipLaunchKernelGGL(mfcc_span_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
+                       (hipStream_t)stream, a);
+    SPK_LAUNCH_CHECK("spk_mfcc_span_fwd");
+    return 0;
+}
+
+extern "C" int spk_pcm16_to_f32(const short* pcm, const int* count, int B, long long Nmax, float* out, void* stream) {
+    SPK_REQUIRE(pcm && count && out, "spk_pcm16_to_f32: null pointer");
+    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Nmax < (1ll << 31), "spk_pcm16_to_f32: B=%d Nmax=%lld", B, Nmax);
+    const int vec = (Nmax % 8 == 0) && ((size_t)pcm % 16 == 0) && ((size_t)out % 16 == 0);
+    hipLaunchKernelGGL(pcm16_to_f32_kernel, dim3((unsigned)((Nmax + 2047) / 2048), (unsigned)B), dim3(256), 0, (hipStream_t)stream, pcm,
+                       count, Nmax, out, vec);
+    SPK_LAUNCH_CHECK("spk_pcm16_to_f32");
     return 0;
 }
 

@@ -189,3 +189,55 @@ extern "C" int spk_wav_read_padded(int B, const char* const* paths, const int64_
     for (auto& th : pool) th.join();
     return fail.load() ? -8 : 0;
 }
+
+// out[b][s] = sample first[b] + s of file b, as it lies in the file (int16), for s < count[b]; 0 for count[b] <= s < Nmax.  Only the
+// span is read (pread on nthreads threads): the reader of training from audio, where a batch needs a few seconds of each file
+extern "C" int spk_wav_read_span(int B, const char* const* paths, const int64_t* data_off, const int64_t* nsamp, const int64_t* first,
+                                 const int64_t* count, int64_t Nmax, int16_t* out, int nthreads) {
+    if (B <= 0 || Nmax <= 0 || !paths || !data_off || !nsamp || !first || !count || !out) {
+        wav_err("spk_wav_read_span: bad arguments");
+        return -1;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (first[b] < 0 || count[b] < 0 || first[b] > nsamp[b] || count[b] > nsamp[b] - first[b]) {
+            wav_err("spk_wav_read_span: %s: span of %lld samples from sample %lld lies outside the file's %lld samples", paths[b],
+                    (long long)count[b], (long long)first[b], (long long)nsamp[b]);
+            return -7;
+        }
+        if (count[b] > Nmax) {
+            wav_err("spk_wav_read_span: %s: span of %lld samples is longer than the row of Nmax=%lld", paths[b], (long long)count[b],
+                    (long long)Nmax);
+            return -7;
+        }
+    }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > B) nthreads = B;
+    std::atomic<int> next(0), fail(0);
+    auto work = [&]() {
+        for (;;) {
+            const int b = next.fetch_add(1);
+            if (b >= B || fail.load()) break;
+            const int fd = open(paths[b], O_RDONLY);
+            if (fd < 0) {
+                wav_err("%s: cannot open", paths[b]);
+                fail.store(1);
+                break;
+            }
+            const int64_t n = count[b];
+            int16_t* dst = out + (size_t)b * Nmax;
+            const bool ok = n == 0 || pread_full(fd, dst, (size_t)n * 2, data_off[b] + 2 * first[b]);     // little-endian host
+            close(fd);
+            if (!ok) {
+                wav_err("%s: short read of %lld samples from sample %lld", paths[b], (long long)n, (long long)first[b]);
+                fail.store(1);
+                break;
+            }
+            if (n < Nmax) memset(dst + n, 0, (size_t)(Nmax - n) * sizeof(int16_t));
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int i = 1; i < nthreads; ++i) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return fail.load() ? -8 : 0;
+}

@@ -6,6 +6,9 @@ The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_mfcc_fwd
 (spk_resample_fwd: Kaldi's LinearResample, for audio at another sample rate and for speed perturbation) and csrc/augment.hip
 (spk_augment_fwd: reverberation and additive noise, the wav-reverberate entries of the recipe's augmented wav.scp); this module parses Kaldi
 config files, builds the window / twiddle / mel / resampling tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
+Training from audio adds the span form of the two frame kernels (fbank_span / mfcc_span: the frames of a part of
+an utterance, bit for bit the frames of the whole), pcm16_to_f32, AugmentPool (the device-resident form of WavAugmentation) and
+ChunkFrontend, which ingest.WavTrainLoader runs on its copy stream.
 The one deliberate difference from Kaldi: dither is a counter-based N(0,1) draw keyed by (seed, utt_id, frame, position), and the VAD
 sees the same dithered frames as the fbank (Kaldi draws a second dither for its MFCC pass).
 """
@@ -813,6 +816,247 @@ def augment_inputs(table, idx):
     return table.augmentation.inputs(idx)
 
 
+AUX_POOL_BYTES = 2 << 30        # samples of impulse-response and noise files kept on the device by an AugmentPool
+
+
+class _Arena:
+    """a growing float32 device buffer; what is added keeps its offset until reset()"""
+
+    def __init__(self, device):
+        self.device, self.buf, self.used = device, None, 0
+
+    def add(self, v):
+        need = self.used + v.size
+        if self.buf is None or need > self.buf.numel():
+            new = torch.empty(max(need, 2 * (self.buf.numel() if self.buf is not None else 1 << 18)), device=self.device)
+            if self.used:
+                new[:self.used].copy_(self.buf[:self.used])
+            self.buf = new
+        self.buf[self.used:need].copy_(torch.from_numpy(v), non_blocking=True)
+        off, self.used = self.used, need
+        return off
+
+
+class AugmentBatch:
+    """the descriptors of one batch for AugmentPool.apply: host arrays in terms of the pool's file numbers (AugmentPool.plan)"""
+    __slots__ = ("rows", "rir_file", "desc_ptr", "desc_file", "desc_len", "desc_snr", "files")
+
+
+class AugmentPool:
+    """The device-resident form of WavAugmentation, for a caller that augments batch after batch (training from audio): every
+    distinct impulse-response or noise file is read and uploaded once, on first use, into one of two device buffers that are kept
+    (up to cap_bytes together; beyond it the pool is emptied and refilled from the batch in hand).  plan(idx) builds the
+    descriptors of a batch with numpy array operations over tables made once per wav.scp - on any thread, it touches no device -
+    and apply(wave, nsamp, plan) uploads what the pool lacks and runs spk_augment_fwd, the launch of features.augment, on the
+    current stream: no host synchronisation, and the counts of clipped samples stay on the device (self.clipped accumulates them
+    per call: an int64 scalar tensor, None before the first call).  Everything features.augment refuses is refused here: the values of the entries when the pool
+    is made, a file's content when it is first read."""
+
+    def __init__(self, augmentation, device, sample_rate, cap_bytes=AUX_POOL_BYTES):
+        self.aug, self.device, self.fs, self.cap = augmentation, torch.device(device), float(sample_rate), int(cap_bytes)
+        aux, index, entries = augmentation.aux, augmentation.index, augmentation.entries
+        n = len(entries)
+        self.ent_rir = np.full(n, -1, dtype=np.int64)
+        ptr, dfile, ddur, dstart, dsnr, dent = [0], [], [], [], [], []
+        for i, e in enumerate(entries):           # once per wav.scp
+            if e.rir_path:
+                self.ent_rir[i] = index[e.rir_path]
+            for p, d, st, snr in e.noises:
+                dfile.append(index[p])
+                ddur.append(np.nan if d is None else d)
+                dstart.append(st)
+                dsnr.append(snr)
+                dent.append(i)
+            ptr.append(len(dfile))
+        self.ent_ptr = np.asarray(ptr, dtype=np.int64)
+        self.d_file = np.asarray(dfile, dtype=np.int64)
+        dur, start = np.asarray(ddur, dtype=np.float64), np.asarray(dstart, dtype=np.float64)
+        self.d_snr = np.asarray(dsnr, dtype=np.float64)
+        raw = aux.nsamp[self.d_file] if self.d_file.size else np.zeros(0, dtype=np.int64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            fill = np.where(np.isnan(dur), raw.astype(np.float64), np.where(np.isfinite(dur), np.trunc(self.fs * dur), 0.0))
+            bad = ~np.isfinite(self.d_snr) | ~np.isfinite(start) | (start < 0) | ~(fill >= 1) | ~(fill < 2 ** 30) | (start * self.fs >= 2 ** 30)
+        if bad.any():
+            d = int(np.nonzero(bad)[0][0])
+            raise ValueError("augment: a noise of %s (%s) has SNR %r, duration %r s, start %r s: not finite, negative or too long"
+                             % (entries[dent[d]].path, aux.paths[self.d_file[d]], self.d_snr[d], ddur[d], dstart[d]))
+        self.d_len = np.stack([raw, fill.astype(np.int64), np.trunc(start * self.fs).astype(np.int64)], 1).astype(np.int32) \
+            if self.d_file.size else np.zeros((0, 3), dtype=np.int32)
+        # per file: the descriptors that add it (for the all-zero check at first read), its place in the pool, the early window
+        self._by_file = np.argsort(self.d_file, kind="stable")
+        self._file_lo = np.searchsorted(self.d_file[self._by_file], np.arange(len(aux.paths) + 1))
+        self.off = np.full(len(aux.paths), -1, dtype=np.int64)
+        self.rir_meta = np.zeros((len(aux.paths), 4), dtype=np.int32)
+        self.is_rir = np.zeros(len(aux.paths), dtype=bool)
+        self.is_rir[self.ent_rir[self.ent_rir >= 0]] = True
+        self.is_noise = np.zeros(len(aux.paths), dtype=bool)
+        self.is_noise[self.d_file] = True
+        self.rirs, self.noises = _Arena(self.device), _Arena(self.device)
+        self.noise_off = np.full(len(aux.paths), -1, dtype=np.int64)
+        self.clipped = None             # made by the first apply(): nothing is launched here
+        lib = hip.lib()
+        self.max_rir, self.max_early = lib.spk_augment_max_rir(), lib.spk_augment_max_early()
+
+    @property
+    def reads(self):
+        """files read so far (a file is read again only after the host cache dropped it and the pool was emptied)"""
+        return self.aug.reads
+
+    def plan(self, idx):
+        """descriptors of the rows idx of the wav.scp (numpy only): None when no row is augmented"""
+        idx = np.asarray(idx, dtype=np.int64)
+        rir = self.ent_rir[idx]
+        cnt = self.ent_ptr[idx + 1] - self.ent_ptr[idx]
+        rows = np.nonzero((rir >= 0) | (cnt > 0))[0]
+        if rows.size == 0:
+            return None
+        p = AugmentBatch()
+        p.rows = rows
+        p.rir_file = rir[rows]
+        cnt = cnt[rows]
+        p.desc_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+        d = np.repeat(self.ent_ptr[idx[rows]] - p.desc_ptr[:-1], cnt) + np.arange(int(p.desc_ptr[-1]))
+        p.desc_file, p.desc_len, p.desc_snr = self.d_file[d], self.d_len[d], self.d_snr[d]
+        p.files = np.unique(np.concatenate([p.rir_file[p.rir_file >= 0], p.desc_file]))
+        return p
+
+    def _check_file(self, f, v):
+        path = self.aug.aux.paths[f]
+        if self.is_rir[f]:
+            if v.size > self.max_rir:
+                raise ValueError("augment: the impulse response %s has %d samples, more than the %d the kernel is built for"
+                                 % (path, v.size, self.max_rir))
+            s, e0, e1 = early_window(v, self.fs)
+            if not 1 <= e1 - e0 <= self.max_early:
+                raise ValueError("augment: the early part of the impulse response %s has %d samples at %g Hz, outside [1, %d]"
+                                 % (path, e1 - e0, self.fs, self.max_early))
+            self.rir_meta[f] = (v.size, s, e0, e1 - e0)
+        ds = self._by_file[self._file_lo[f]:self._file_lo[f + 1]]
+        for fill in np.unique(np.minimum(self.d_len[ds, 1], v.size)):
+            if not np.any(v[:fill]):
+                raise ValueError("augment: the noise %s is all zero over the %d samples that are added (its power scales the SNR)"
+                                 % (path, int(fill)))
+
+    def _resident(self, files):
+        def missing():
+            return [int(f) for f in files if (self.is_rir[f] and self.off[f] < 0) or (self.is_noise[f] and self.noise_off[f] < 0)]
+        todo = missing()
+        if not todo:
+            return
+        new = 4 * sum(int(self.aug.aux.nsamp[f]) * (int(self.is_rir[f]) + int(self.is_noise[f])) for f in todo)
+        if 4 * (self.rirs.used + self.noises.used) + new > self.cap:
+            self.off[:] = -1
+            self.noise_off[:] = -1
+            self.rirs.used = self.noises.used = 0
+            todo = missing()
+            new = 4 * sum(int(self.aug.aux.nsamp[f]) * (int(self.is_rir[f]) + int(self.is_noise[f])) for f in todo)
+            if new > self.cap:
+                raise ValueError("augment: one batch needs %d bytes of impulse responses and noises, above the pool's cap of %d"
+                                 % (new, self.cap))
+        for f in todo:
+            v = self.aug.samples(self.aug.aux.paths[f])
+            self._check_file(f, v)
+            if self.is_rir[f] and self.off[f] < 0:
+                self.off[f] = self.rirs.add(v)
+            if self.is_noise[f] and self.noise_off[f] < 0:
+                self.noise_off[f] = self.noises.add(v)
+
+    def apply(self, wave, nsamp, plan, quantize=True):
+        """wave: float32 cuda [B', Nmax], the rows plan.rows of the batch the plan was made for, nsamp: int32 cuda [B'] -> the
+        augmented rows [B', Nmax], as features.augment(wave, nsamp, ..., quantize) gives them, bit for bit"""
+        B, Nmax = wave.shape
+        if B != plan.rows.size:
+            raise ValueError("AugmentPool.apply: %d rows for a plan of %d" % (B, plan.rows.size))
+        self._resident(plan.files)
+        dev = self.device
+        has = plan.rir_file >= 0
+        rf = np.where(has, plan.rir_file, 0)
+        rir_row = np.where(has[:, None], self.rir_meta[rf], 0).astype(np.int32)
+        rir_off = np.where(has, self.off[rf], 0).astype(np.int64)
+        nd = int(plan.desc_file.size)
+        if B + nd > 65535:
+            raise ValueError("augment: %d rows with %d noises in one call (at most 65535 together)" % (B, nd))
+        Rmax, Emax = int(rir_row[:, 0].max()), int(rir_row[:, 3].max())
+        Fmax = int(plan.desc_len[:, 1].max()) if nd else 0
+        sizes = (ctypes.c_longlong * 3)()
+        hip.call("spk_augment_workspace", B, Nmax, Rmax, Emax, Fmax, nd, sizes)
+
+        def dv(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev, non_blocking=True)
+        t_off, t_row, t_ptr = dv(rir_off, np.int64), dv(rir_row, np.int32), dv(plan.desc_ptr, np.int32)
+        t_doff = dv(self.noise_off[plan.desc_file], np.int64) if nd else None
+        t_dlen = dv(plan.desc_len.reshape(-1), np.int32) if nd else None
+        t_dsnr = dv(plan.desc_snr, np.float64) if nd else None
+        spectra = torch.empty(2 * sizes[0], device=dev) if sizes[0] else None
+        y = torch.empty(max(sizes[1], 1), device=dev)
+        work = torch.empty(max(sizes[2], 1), dtype=torch.float64, device=dev)
+        out = torch.empty(B, Nmax, device=dev)
+        clipped = torch.zeros(B, dtype=torch.int64, device=dev)
+        hip.call("spk_augment_fwd", hip.ptr(wave.contiguous()), hip.ptr(nsamp), B, Nmax, hip.ptr(self.rirs.buf) if Rmax else None,
+                 self.rirs.used, hip.ptr(t_off), hip.ptr(t_row), Rmax, Emax, hip.ptr(self.noises.buf) if nd else None,
+                 self.noises.used, hip.ptr(t_ptr), hip.ptr(t_doff), hip.ptr(t_dlen), hip.ptr(t_dsnr), nd, Fmax,
+                 hip.ptr(_aug_twiddle(dev)) if Rmax else None, hip.ptr(spectra), hip.ptr(y), hip.ptr(work), int(bool(quantize)),
+                 hip.ptr(out), hip.ptr(clipped), hip.stream())
+        self.clipped = clipped.sum() if self.clipped is None else self.clipped + clipped.sum()
+        return out
+
+
+class ChunkFrontend:
+    """Audio of a batch of training chunks -> the chunks, on the current stream: spk_pcm16_to_f32, the augmentation of the rows
+    that have one (AugmentPool), the span fbank / MFCC (fbank_opts: FbankOptions or MfccOptions) and spk_cmn_select with
+    span-relative frame indices.  Every argument of a call is a device tensor made by the caller (ingest.WavTrainLoader plans the
+    spans on the host and uploads the numbers with the audio): nothing is read back, no .cpu(), no synchronisation.
+    ChunkFrontend(fbank_opts, cmn, seed=0, pool=None)(pcm, count, first, total, frame0, nframes, rel, T, utt_ids, plan) -> [B, F, T]
+        pcm int16 [B, Nmax]: row b = samples first[b] .. + count[b] of an utterance of total[b] samples (int32 / int64 / int64 [B])
+        frame0, nframes int32 [B]: the frames of the utterance that are computed; rel int32 [B, Tcap], Tcap >= max nframes: in its
+        first T columns the T selected frames, counted from frame0; plan: AugmentPool.plan of the batch or None
+    times: None, or a dict that gets (start, end) event pairs per stage ("convert", "augment", "frontend", "cmn")."""
+
+    def __init__(self, fbank_opts, cmn=None, seed=0, pool=None):
+        self.opts, self.cmn, self.seed, self.pool = fbank_opts, cmn, seed, pool
+        self.dim = fbank_opts.num_ceps if isinstance(fbank_opts, MfccOptions) else fbank_opts.num_mel_bins
+
+    def __call__(self, pcm, count, first, total, frame0, nframes, rel, T, utt_ids=None, plan=None, times=None):
+        B, Nmax = pcm.shape
+        Tcap = rel.shape[1]
+        dev = pcm.device
+        if self.opts.dither != 0 and utt_ids is None:
+            raise ValueError("ChunkFrontend: dither != 0 needs utt_ids")
+        if plan is not None and self.pool is None:
+            raise ValueError("ChunkFrontend: augmented rows need an AugmentPool")
+
+        def stage(name, fn):
+            if times is None:
+                return fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn()
+            e1.record()
+            times[name] = (e0, e1)
+            return r
+        wave = stage("convert", lambda: pcm16_to_f32(pcm, count))
+        if plan is not None:
+            def aug():
+                if plan.rows.size == B:
+                    return self.pool.apply(wave, count, plan)
+                rows = torch.from_numpy(plan.rows).to(dev, non_blocking=True)
+                wave.index_copy_(0, rows, self.pool.apply(wave.index_select(0, rows), count.index_select(0, rows), plan))
+                return wave
+            wave = stage("augment", aug)
+        feats, _ = stage("frontend", lambda: _span_launch(self.opts, wave, count, first, total, frame0, nframes, utt_ids, self.seed, Tcap))
+        W = int(self.cmn.cmn_window) if self.cmn is not None else 0
+        F = feats.shape[1]
+
+        def cmn():
+            pre = torch.empty(B * F * (Tcap + 1), dtype=torch.float64, device=dev) if W > 0 else None
+            out = torch.empty(B, F, T, device=dev)
+            cnt = torch.full((B,), T, dtype=torch.int32, device=dev)
+            hip.call("spk_cmn_select", hip.ptr(feats), hip.ptr(nframes), hip.ptr(rel), hip.ptr(cnt), hip.ptr(pre), hip.ptr(out), B, F,
+                     Tcap, T, W, hip.stream())
+            return out
+        return stage("cmn", cmn)
+
+
 # ---- functional API ----
 def _frame_inputs(what, wave, nsamp, opts, utt_ids, Tcap):
     """the argument checks and device inputs fbank and mfcc share (`what` names the caller in the messages):
@@ -880,6 +1124,132 @@ def mfcc(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None, out=None):
              float(opts.preemphasis_coefficient), int(opts.remove_dc_offset), float(opts.energy_floor), int(opts.use_energy),
              int(opts.htk_compat), int(seed) & (2 ** 64 - 1), hip.ptr(out), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
     return out, T, loge
+
+
+# ---- the span form: frames of a part of an utterance, equal to the frames of the whole ----
+def span_samples(opts, frame_lo, frame_hi, total):
+    """(first, last): the samples [first, last) of utterances of `total` samples that their frames [frame_lo, frame_hi) read, the
+    snip_edges=false reflection about 0 and `total` included (integer arrays, numpy only; frame_hi > frame_lo)"""
+    L, S = opts.frame_len, opts.frame_sh
+    lo, hi, N = (np.asarray(v, dtype=np.int64) for v in (frame_lo, frame_hi, total))
+    off = 0 if opts.snip_edges else L // 2 - S // 2
+    a, b = lo * S - off, (hi - 1) * S - off + L
+    first, last = np.maximum(a, 0), np.minimum(b, N)
+    last = np.where(a < 0, np.maximum(last, np.minimum(-a, N)), last)          # s < 0 reads -s - 1
+    first = np.where(b > N, np.minimum(first, np.maximum(2 * N - b, 0)), first)  # s >= N reads 2N - 1 - s
+    return first, last
+
+
+def pcm16_to_f32(pcm, count, out=None):
+    """16-bit samples as they lie in a WAV file -> float32 at int16 scale on the GPU.  pcm: int16 cuda [B, Nmax], count: int32 cuda
+    [B] (samples per row); zeros past the count.  Nothing is read back."""
+    if not isinstance(pcm, torch.Tensor) or pcm.dim() != 2 or pcm.dtype != torch.int16 or not pcm.is_cuda:
+        raise ValueError("pcm16_to_f32: pcm must be an int16 cuda tensor [B, Nmax]")
+    B, Nmax = pcm.shape
+    if B == 0 or Nmax == 0:
+        raise ValueError("pcm16_to_f32: empty batch [%d, %d]" % (B, Nmax))
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.numel() == B):
+        raise ValueError("pcm16_to_f32: count must be an int32 cuda tensor of %d rows" % B)
+    if out is None:
+        out = torch.empty(B, Nmax, device=pcm.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Nmax) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("pcm16_to_f32: out must be a contiguous float32 cuda tensor [%d, %d]" % (B, Nmax))
+    hip.call("spk_pcm16_to_f32", hip.ptr(pcm.contiguous()), hip.ptr(count), B, Nmax, hip.ptr(out), hip.stream())
+    return out
+
+
+def _span_launch(opts, wave, ns, first, total, frame0, nframes, ids, seed, Tcap, out=None):
+    """the span launch on device arguments alone (no check of their values, nothing read back): (feats [B, R, Tcap], log_energy)"""
+    B, Nmax = wave.shape
+    dev = wave.device
+    tab = _tables(opts, dev)
+    is_mfcc = isinstance(opts, MfccOptions)
+    R = opts.num_ceps if is_mfcc else opts.num_mel_bins
+    feats = torch.empty(B, R, Tcap, device=dev) if out is None else out
+    loge = torch.empty(B, Tcap, device=dev)
+    tdev = torch.empty(B, dtype=torch.int32, device=dev)
+    head = (hip.ptr(wave), hip.ptr(ns), hip.ptr(first), hip.ptr(total), hip.ptr(frame0), hip.ptr(nframes), hip.ptr(ids), B, Nmax,
+            hip.ptr(tab.window), hip.ptr(tab.twiddle), hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off))
+    tail = (int(seed) & (2 ** 64 - 1), hip.ptr(feats), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
+    if is_mfcc:
+        hip.call("spk_mfcc_span_fwd", *head, hip.ptr(tab.dct), hip.ptr(tab.lifter), opts.frame_len, opts.frame_sh, opts.padded_len,
+                 opts.num_mel_bins, R, int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient),
+                 int(opts.remove_dc_offset), float(opts.energy_floor), int(opts.use_energy), int(opts.htk_compat), *tail)
+    else:
+        hip.call("spk_fbank_span_fwd", *head, opts.frame_len, opts.frame_sh, opts.padded_len, R, int(opts.snip_edges),
+                 float(opts.dither), float(opts.preemphasis_coefficient), int(opts.remove_dc_offset), float(opts.energy_floor), *tail)
+    return feats, loge
+
+
+def check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax):
+    """the refusals of the span form, on host arrays, before any launch: every computed frame exists in the utterance and, after
+    reflection, touches only samples that the row holds.  Returns the arrays as int64."""
+    n, f, N, f0, nf = (_host_ints(v) for v in (nsamp, first, total, frame0, nframes))
+    B = n.size
+    if not (f.size == N.size == f0.size == nf.size == B):
+        raise ValueError("%s: nsamp, first, total, frame0 and nframes must have one entry per row (%d rows)" % (what, B))
+    L = opts.frame_len
+
+    def bad(mask, msg):
+        if mask.any():
+            b = int(np.nonzero(mask)[0][0])
+            raise ValueError("%s: row %d (first %d, %d samples, utterance of %d samples, frames %d .. +%d): %s"
+                             % (what, b, int(f[b]), int(n[b]), int(N[b]), int(f0[b]), int(nf[b]), msg))
+    bad((n < 1) | (n > Nmax), "sample count outside [1, Nmax %d]" % Nmax)
+    bad(N < L, "the utterance is shorter than one frame (%d samples)" % L)
+    bad((f < 0) | (f + n > N), "the row is not a part of the utterance")
+    Tu = np.asarray([opts.num_frames(int(v)) for v in N], dtype=np.int64)
+    bad((f0 < 0) | (nf < 0) | (f0 + nf > Tu), "frames outside the utterance's")
+    need_first, need_last = span_samples(opts, f0, np.maximum(f0 + nf, f0 + 1), N)
+    bad((nf > 0) & ((need_first < f) | (need_last > f + n)), "a frame touches a sample outside the row")
+    return n, f, N, f0, nf
+
+
+def _span(what, wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out=None):
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+        raise ValueError("%s: wave must be a float32 cuda tensor [B, Nmax]" % what)
+    wave = wave.contiguous()
+    B, Nmax = wave.shape
+    n, f, N, f0, nf = check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax)
+    if n.size != B:
+        raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
+    Tcap = max(int(nf.max()), 1) if Tcap is None else int(Tcap)
+    if Tcap < nf.max() or Tcap < 1:
+        raise ValueError("%s: Tcap %d < longest span %d frames" % (what, Tcap, int(nf.max())))
+    if opts.dither != 0 and utt_ids is None:
+        raise ValueError("%s: dither != 0 needs utt_ids (the key of each row's noise)" % what)
+    dev = wave.device
+
+    def dv(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+    ids = dv(_host_ints(utt_ids), np.int64) if utt_ids is not None else None
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                            or not out.is_contiguous() or out.dim() != 3 or out.shape[0] != B or out.shape[2] != Tcap):
+        raise ValueError("%s: out must be a contiguous float32 cuda tensor [%d, rows, %d]" % (what, B, Tcap))
+    feats, loge = _span_launch(opts, wave, dv(n, np.int32), dv(f, np.int64), dv(N, np.int64), dv(f0, np.int32), dv(nf, np.int32), ids,
+                               seed, Tcap, out)
+    return feats, nf, loge
+
+
+def fbank_span(wave, nsamp, first, total, frame0, nframes, opts, utt_ids=None, seed=0, Tcap=None):
+    """The frames of a span of each utterance, equal bit for bit to the same frames of fbank() on the whole utterance.  Row b of
+    wave (float32 cuda [B, Nmax], int16 scale) holds samples first[b] .. first[b] + nsamp[b] - 1 of an utterance of total[b]
+    samples; computed are frames frame0[b] .. frame0[b] + nframes[b] - 1 of that utterance: the reflection of snip_edges=false is
+    about 0 and total[b], the dither draw is keyed by the frame's index in the utterance.  All five are host integers per row.
+    Returns (feats [B, F, Tcap] cuda, column j = frame frame0[b] + j, zeros from nframes[b]; nframes int64 host array; log_energy
+    [B, Tcap]).  Refused before any launch: a frame outside the utterance, a frame that after reflection touches a sample outside
+    its row (span_samples gives the samples a frame range needs)."""
+    if isinstance(opts, MfccOptions):
+        raise ValueError("fbank_span: opts must be a FbankOptions (mfcc_span takes MfccOptions)")
+    return _span("fbank_span", wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap)
+
+
+def mfcc_span(wave, nsamp, first, total, frame0, nframes, opts, utt_ids=None, seed=0, Tcap=None, out=None):
+    """fbank_span for compute-mfcc-feats (opts: MfccOptions): feats [B, num_ceps, Tcap], equal bit for bit to mfcc() on the whole
+    utterance"""
+    if not isinstance(opts, MfccOptions):
+        raise ValueError("mfcc_span: opts must be an MfccOptions")
+    return _span("mfcc_span", wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out)
 
 
 def dither_noise(utt, seed, frame0, nframes, L, device="cuda"):

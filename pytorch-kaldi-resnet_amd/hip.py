@@ -93,7 +93,10 @@ _SIGS = {
     "spk_fbank_fwd": [_P, _P, _P, _I, _L] + [_P] * 5 + [_I] * 5 + [_F, _F, _I, _F, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
     "spk_mfcc_tile_frames": [_I, _I, _I, _I, _I],
     "spk_mfcc_fwd": [_P, _P, _P, _I, _L] + [_P] * 7 + [_I] * 6 + [_F, _F, _I, _F, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
-    "spk_fbank_dither_noise": [_P, _L, ctypes.c_ulonglong, _I, _I, _I, _P],
+    "spk_fbank_span_fwd": [_P] * 7 + [_I, _L] + [_P] * 5 + [_I] * 5 + [_F, _F, _I, _F, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
+    "spk_mfcc_span_fwd": [_P] * 7 + [_I, _L] + [_P] * 7 + [_I] * 6 + [_F, _F, _I, _F, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
+    "spk_pcm16_to_f32": [_P, _P, _I, _L, _P, _P],
+    "spk_fbank_dither_noise":[_P, _L, ctypes.c_ulonglong, _I, _I, _I, _P],
     "spk_vad_count": [_P, _P, _I, _I, _D, _D, _I, _D, _P, _P, _P, _P],
     "spk_cmn_select": [_P] * 6 + [_I] * 5 + [_P],
     "spk_resample_tile": [_I, _I, _I],

@@ -74,12 +74,33 @@ parser.add_argument("--chunk-quantum", default=8, type=int, help="step between t
 parser.add_argument("--no-graph", action="store_true",
                     help="launch kernels eagerly instead of replaying the step as hipGraph(s); both forms overlap the "
                          "stage-bucketed gradient all-reduce with backward")
+parser.add_argument("--wav-scp", type=str,
+                    help="train from audio: the recipe's wav.scp of train_combined (16-bit PCM mono WAV paths and its wav-reverberate "
+                         "entries) instead of --train-list; the chunks are computed on the GPU as they are drawn and equal the columns "
+                         "of the archive compute_fbank.py / compute_mfcc.py --egs --vad-scp --cmn-window writes; --dataset v1 only")
+parser.add_argument("--vad-scp", type=str, help="with --wav-scp: vad.scp of 0/1 vectors per key (without it every frame is voiced)")
+parser.add_argument("--fbank-config", type=str, help="with --wav-scp: Kaldi config file of compute-fbank-feats options")
+parser.add_argument("--mfcc-config", type=str, help="with --wav-scp: Kaldi config file of compute-mfcc-feats options (instead of --fbank-config)")
+parser.add_argument("--cmn-window", default=300, type=int, help="with --wav-scp: apply-cmvn-sliding --cmn-window (0: no CMN)")
+parser.add_argument("--feat-seed", default=0, type=int, help="with --wav-scp: dither seed (compute_fbank.py --seed)")
+parser.add_argument("--cv-wav-scp", type=str, help="with --wav-scp: validate from audio too (unshuffled) instead of --cv-list")
 
 best_acc1 = 0
 
 
 def main():
     args = parser.parse_args()
+    if args.wav_scp:
+        if args.dataset == "v2":
+            parser.error("--wav-scp does not combine with --dataset v2")
+        if args.fbank_config and args.mfcc_config:
+            parser.error("--fbank-config and --mfcc-config are alternatives")
+        if args.train_list:
+            parser.error("--wav-scp replaces --train-list")
+        if not args.cv_wav_scp and not args.cv_list:
+            parser.error("--wav-scp needs --cv-wav-scp or --cv-list")
+    elif args.vad_scp or args.cv_wav_scp or args.fbank_config or args.mfcc_config:
+        parser.error("--vad-scp, --cv-wav-scp, --fbank-config and --mfcc-config need --wav-scp")
     if args.seed is not None:
         random.seed(args.seed)
         torch.manual_seed(args.seed)
@@ -124,6 +145,35 @@ def main_worker(gpu, ngpus_per_node, args):
         # reproduce the --gpu run with the same --seed
         torch.manual_seed(args.seed)
     torch.cuda.set_device(args.gpu)
+    wav_train_loader = wav_val_loader = None
+    if args.wav_scp:
+        # training from audio: the tables are made and everything about the files is refused here, before the model is built and
+        # before anything is launched
+        from pytorch_kaldi_resnet_amd import features
+        from pytorch_kaldi_resnet_amd.ingest import WavTrainLoader
+        try:
+            feat_opts, _, cmn_opts = features.options_from_configs(args.fbank_config, None, args.cmn_window,
+                                                                   mfcc_config=args.mfcc_config)
+        except ValueError as e:
+            sys.exit("train_resnet: %s" % e)
+        dim = feat_opts.num_ceps if isinstance(feat_opts, features.MfccOptions) else feat_opts.num_mel_bins
+        if dim != args.input_dim:
+            sys.exit("train_resnet: --input-dim %d differs from the feature dimension %d of %s" % (
+                args.input_dim, dim, args.mfcc_config or args.fbank_config or "the default compute-fbank-feats options"))
+        var_chunk = (args.min_chunk_size, args.max_chunk_size, args.chunk_quantum) if args.var_chunk else None
+
+        def wav_loader(scp, **kw):
+            try:
+                return WavTrainLoader(scp, args.utt2spkid, args.max_chunk_size,
+                                      int(args.batch_size / ngpus_per_node) if args.distributed else args.batch_size, feat_opts,
+                                      cmn_opts, vad_scp=args.vad_scp, feat_seed=args.feat_seed, seed=args.seed or 0,
+                                      threads=max(1, args.workers), device="cuda:%d" % args.gpu, **kw)
+            except ValueError as e:
+                sys.exit("train_resnet: %s" % e)
+        wav_train_loader = wav_loader(args.wav_scp, rank=max(args.rank, 0), world=args.world_size if args.distributed else 1,
+                                      chunk_range=var_chunk)
+        if args.cv_wav_scp:
+            wav_val_loader = wav_loader(args.cv_wav_scp, shuffle=False)
     print("=> creating model '{}'".format(args.arch))
     model = NeuralSpeakerModel(spk_num=args.spk_num, feat_dim=args.input_dim, pooling=args.pooling, loss=args.loss_type,
                                m=args.margin, s=args.scale, arch=args.arch)
@@ -174,7 +224,9 @@ def main_worker(gpu, ngpus_per_node, args):
     if var is not None:
         assert 0 < var[0] <= var[1], "--var-chunk needs 0 < --min-chunk-size <= --max-chunk-size"
         print("=> variable-length training: one chunk length per batch in [{}, {}] step {}".format(*var))
-    if args.native_reader and args.dataset != "v2":
+    if args.wav_scp:
+        train_loader = train_sampler = wav_train_loader          # set_epoch() reshuffles
+    elif args.native_reader and args.dataset != "v2":
         from pytorch_kaldi_resnet_amd.ingest import NativeTrainLoader
         train_loader = NativeTrainLoader(args.train_list, args.utt2spkid, args.max_chunk_size, args.batch_size,
                                          rank=max(args.rank, 0), world=world, seed=args.seed or 0,
@@ -198,9 +250,12 @@ def main_worker(gpu, ngpus_per_node, args):
                                                        pin_memory=True, sampler=train_sampler, drop_last=False)
     print("=> args.world_size: {}, args.rank: {}, args.batch_size: {}, train_loader samples: {}".format(
         args.world_size, args.rank, args.batch_size, len(train_loader)))
-    val = DS(scp_file=args.cv_list, utt2spkid_file=args.utt2spkid, chunk_size=chunk)
-    val_loader = torch.utils.data.DataLoader(val, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
-                                             pin_memory=True)
+    if wav_val_loader is not None:
+        val_loader = wav_val_loader
+    else:
+        val = DS(scp_file=args.cv_list, utt2spkid_file=args.utt2spkid, chunk_size=chunk)
+        val_loader = torch.utils.data.DataLoader(val, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
+                                                 pin_memory=True)
     if args.evaluate:
         validate(val_loader, model, args)
         return
