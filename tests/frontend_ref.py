@@ -106,6 +106,8 @@ def vad(loge, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5, vad_frames_co
     """compute-vad decisions [T] (int32 0/1) from raw log energies [T]"""
     e = np.asarray(loge)
     T = len(e)
+    if T == 0:                  # an utterance without frames: no decisions (and no mean to divide for)
+        return np.zeros(0, dtype=np.int32)
     thr = vad_energy_threshold + vad_energy_mean_scale * float(np.asarray(e, dtype=np.float64).sum()) / T
     above = e.astype(np.float64) > thr
     out = np.zeros(T, dtype=np.int32)
