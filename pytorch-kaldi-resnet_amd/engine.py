@@ -13,6 +13,15 @@ SEBasicBlock (arch "se_resnet34", scripts/model.py:67-97): the last line becomes
 - one more read of raw2.  Backward: e = dout*[out > 0] is the shortcut gradient, bn2 sees dz = g*e + dq/HW; one pass reduces
 (sum e, sum e*raw2) per utterance, the gate kernels turn those [B][C] tables into dW1, dW2, dq and bn2's backward statistics,
 one pass writes draw2 (csrc/se.hip).  The data-gradient fusions that assume dz = d*[out > 0] are off around that BatchNorm.
+
+Block backward (Engine._block_bwd), the rules every block follows.  A block has at least two convolutions.  A saved training
+forward always writes the sign words of every block output, so the backward always has rec["mask"] and rec["xmask"].  Gradients
+wrt raw conv outputs are f16 pair tensors exactly in the f16x3 backward mode.  The BatchNorm backward of conv_i runs in one of
+three forms: fused into conv_i's stride-1 data gradient (up to fuse_apply_max_c output channels), as a stand-alone pass, or -
+the last BatchNorm of an SE block, always - on the SE kernels.  The shortcut gradient dz = dout*[out > 0] is stored only in
+downsample blocks (the 1x1 branch reads it); an identity-shortcut block never stores it: its first convolution's data gradient
+re-forms it from dout and the mask bits.  The stand-alone and SE passes read the mask of the last BatchNorm from the bits; the
+fused form reduces it from the block output (MASK_ACT) and stages it from the bits.
 """
 import torch
 
@@ -86,6 +95,7 @@ class _Block:
         self.kind = bp.kind
         self.convs = [_Conv(bp.conv1), _Conv(bp.conv2)] + ([_Conv(bp.conv3)] if bp.kind == "bottleneck" else [])
         self.bns = [_BN(bp.bn1), _BN(bp.bn2)] + ([_BN(bp.bn3)] if bp.kind == "bottleneck" else [])
+        assert len(self.convs) >= 2      # Engine._block_bwd: the first conv re-forms the shortcut gradient the last one left out
         self.ds = None
         if bp.downsample is not None:
             self.ds = (_Conv(bp.downsample[0]), _BN(bp.downsample[1]))
@@ -120,9 +130,11 @@ class Engine:
         self.stem_conv = _Conv(r.conv1)
         self.stem_bn = _BN(r.bn1)
         self.blocks = []
+        self.stage_of = []             # ResNet stage (1..4) of every block
         for li in range(1, 5):
             for bp in getattr(r, "layer%d" % li):
                 self.blocks.append(_Block(bp))
+                self.stage_of.append(li)
         self.head_bn = _BN(model.bn1) if hasattr(model, "bn1") else None
         self.pool_mode = 1 if model.pooling == "mean+std" else 0
         self.dirty = True
@@ -136,34 +148,20 @@ class Engine:
         # HBM-bound BatchNorm-backward passes of the main dgrad chain
         self.wgrad_stream = None
         self.use_side_stream = True
-        # BatchNorm-backward reductions come out of the producing data-gradient epilogue (EPI_BNBWD) where possible
-        self.fuse_bn_reduce = True
-        # ... and the BatchNorm-backward apply runs inside the stride-1 data gradients' input staging (IN_BNBWD)
-        self.fuse_bn_apply = True
-        # the forward BN+residual+ReLU pass also emits 1-bit sign masks of the block outputs; the fused backward kernels read
-        # those instead of the activated tensors
-        import os
-        self.use_sign_masks = os.environ.get("SPK_SIGN_MASKS", "1") == "1"
-        self.fuse_apply_min_c = int(os.environ.get("SPK_FUSE_APPLY_MINC", "0"))   # experiment knob: skip the fusion below C channels
-        # ... and above.  f16x3 default: the fusion only on the 32-channel layer, which is HBM-bound (the fusion saves one tensor
+        # BatchNorm-backward reductions come out of the producing data-gradient epilogue (EPI_BNBWD) where possible, and the
+        # BatchNorm-backward apply runs inside the stride-1 data gradients' input staging (IN_BNBWD) - up to fuse_apply_max_c
+        # output channels.  f16x3 default: the fusion only on the 32-channel layer, which is HBM-bound (the fusion saves one tensor
         # read there); from 64 channels on the BatchNorm backward runs as its own pass that writes the gradient ONCE as an f16
         # pair tensor, and the data gradient (in-wave pipelined kernel) and the weight gradient stage it by plain copy
         # (None = by operand mode: 32 in the f16x3 mode with pair tensors, no limit otherwise; SPK_FUSE_APPLY_MAXC overrides)
+        import os
         self._fuse_apply_max_c = int(os.environ["SPK_FUSE_APPLY_MAXC"]) if "SPK_FUSE_APPLY_MAXC" in os.environ else None
-        # opt-in: 1x1 convolutions (Bottleneck blocks) keep the fusion at every width.  They are HBM-bound and the fusion saves a
-        # tensor pass, but the fused 1x1 kernel is VALU-bound: ResNet-101 with one chunk length per step in [200, 400], same box:
-        # 105.7-106.2 ms without it, 110.6-110.9 ms with it, 112.3 ms with every convolution fused (profiles/r03_c4_policy.log)
-        self.fuse_apply_1x1 = os.environ.get("SPK_FUSE_APPLY_1X1", "0") == "1"
-        # gradients wrt raw conv outputs travel as f16 pair tensors (include/spkhip.h) in the f16x3 mode
-        self.pair_draw = os.environ.get("SPK_PAIR_DRAW", "1") == "1"
         # the stem without two tensor passes (csrc/stem.hip): forward = statistics with no store, then one writer of raw0, a and
         # the sign bits that recomputes the convolution; backward = the BatchNorm-backward apply inside the weight gradient.
         # 0 gives the two-kernel paths back (A/B, identity tests); "fwd" / "bwd" switch one half on (per-part A/B)
         stem_fused = os.environ.get("SPK_STEM_FUSED", "1")
         self.stem_fused_fwd = stem_fused in ("1", "fwd")
         self.stem_fused_bwd = stem_fused in ("1", "bwd")
-        # diagnostics (tests / bench, never the timed path): when a [4] int64 device tensor, every tensor that an f16x3
-        # matrix-core kernel stages is also run through spk_f16_window_count under the scale slot its consumer uses
         # The blocks of the LAST stage sit between the pooling layer and the first BatchNorm backward + convolution that bound the
         # gradient's range again: sqrt'(mean) of scripts/model.py:453 is unbounded (1e8 x the rest for a row mean of 1e-20) and
         # travels down the identity shortcuts as dout.  There the BatchNorm-backward scale bound pairs every channel's own absmax
@@ -171,6 +169,8 @@ class Engine:
         # overshoots the values by the ratio of the two and pushes the whole pair tensor out of its fp16 window.  Costs the
         # stand-alone reduction pass for two more 100 MB tensors per step (their statistics no longer come from an epilogue).
         self.chan_amax = os.environ.get("SPK_CHAN_AMAX", "1") == "1"
+        # diagnostics (tests / bench, never the timed path): when a [4] int64 device tensor, every tensor that an f16x3
+        # matrix-core kernel stages is also run through spk_f16_window_count under the scale slot its consumer uses
         self.window_counts = None
         self.bound_log = None          # diagnostics: when a list, (Cout, k, bound slot, true-absmax slot) of every BatchNorm-backward scale
 
@@ -179,7 +179,7 @@ class Engine:
     def fuse_apply_max_c(self):
         if self._fuse_apply_max_c is not None:
             return self._fuse_apply_max_c
-        return 32 if (self.pair_draw and ops.split_for(3, True) == 3) else 1000000
+        return 32 if ops.split_for(3, True) == 3 else 1000000
 
     @fuse_apply_max_c.setter
     def fuse_apply_max_c(self, v):
@@ -244,7 +244,6 @@ class Engine:
         self._repack(False)
         pool = self._fwd_pool(x.device)
         take = (lambda: pool.take()) if pool is not None else (lambda: None)
-        f16 = ops.split_for(3) == 3
         e = self.stem_bn.eval_coeffs()
         a_amax = take()
         a, _ = ops.stem_fwd(x, self.stem_conv.h.weight.data, epi_affine=(e[0], e[1]), relu=True, amax_out=a_amax,
@@ -395,20 +394,18 @@ class Engine:
             self._fwd_gen += 1                 # this forward now owns the per-engine records (BN statistics rows, scale slots)
         saved["gen"] = self._fwd_gen
         take = (lambda: pool.take()) if pool is not None else (lambda: None)
-        f16 = ops.split_for(3) == 3
         B, F, T = x.shape
-        use_masks = save and self.use_sign_masks
         w0 = self.stem_conv.h.weight.data
         if self.stem_fused_fwd:
             t4 = self.stem_bn.finalize(ops.stem_stats(x, w0), B * F * T, keep=save)
             a_amax = take()
-            raw0, a, amask = ops.stem_fwd_apply(x, w0, t4[2], t4[3], mask=use_masks, amax_out=a_amax)
+            raw0, a, amask = ops.stem_fwd_apply(x, w0, t4[2], t4[3], mask=save, amax_out=a_amax)
         else:
             raw0, st = ops.stem_fwd(x, w0, stats=True)
             t4 = self.stem_bn.finalize(st, B * F * T, keep=save)
             a_amax = take()
-            a = ops.bn_apply(raw0, t4[2], t4[3], relu=True, mask=use_masks, amax_out=a_amax)
-            a, amask = a if use_masks else (a, None)
+            a = ops.bn_apply(raw0, t4[2], t4[3], relu=True, mask=save, amax_out=a_amax)
+            a, amask = a if save else (a, None)
         saved["raw0"] = raw0
         for b in self.blocks:
             # in_amax[i]: slot with the absmax (or its upper estimate) of the values conv_i STAGES - the block input itself,
@@ -430,31 +427,29 @@ class Engine:
                 raws.append(raw)
                 h, aff, h_amax = raw, (t4[2], t4[3]), est
             out_amax = take()
-            gate = None
             if b.se is not None:
                 rec["se"], gate = self._se_gate(b, h, aff)
+            res, res_affine = a, None
             if b.ds is not None:
                 rawd, st = ops.conv_fwd(a, b.ds[0].wpk, b.ds[0].cout, 1, b.ds[0].stride, stats=True,
                                         in_amax=a_amax if ops.split_for(1) == 3 else None)
                 td = b.ds[1].finalize(st, rawd.shape[0] * rawd.shape[1] * rawd.shape[2], keep=save)
-                if gate is not None:
-                    out = ops.se_apply(h, aff, gate, res=rawd, res_affine=(td[2], td[3]), relu=True, mask=use_masks,
-                                       amax_out=out_amax)
-                else:
-                    out = ops.bn_apply(h, aff[0], aff[1], res=rawd, res_affine=(td[2], td[3]), relu=True, mask=use_masks,
-                                       amax_out=out_amax)
+                res, res_affine = rawd, (td[2], td[3])
                 rec["rawd"] = rawd
-            elif gate is not None:
-                out = ops.se_apply(h, aff, gate, res=a, relu=True, mask=use_masks, amax_out=out_amax)
+            # a saved forward also writes the 1-bit sign words of the block output: the backward kernels read those instead of
+            # the activated tensor wherever they only need [out > 0]
+            if b.se is not None:
+                out = ops.se_apply(h, aff, gate, res=res, res_affine=res_affine, relu=True, mask=save, amax_out=out_amax)
             else:
-                out = ops.bn_apply(h, aff[0], aff[1], res=a, relu=True, mask=use_masks, amax_out=out_amax)
-            out, amask = out if use_masks else (out, None)
+                out = ops.bn_apply(h, aff[0], aff[1], res=res, res_affine=res_affine, relu=True, mask=save, amax_out=out_amax)
+            out, amask = out if save else (out, None)
             rec["raws"] = raws
             rec["out"] = out
             rec["mask"] = amask
             if save:
                 saved["blocks"].append(rec)
             a, a_amax = out, out_amax
+            res = None                  # (a forward that saves nothing frees the block input here, not a block later)
         return a, saved
 
     def _embed_train(self, x, save):
@@ -537,26 +532,11 @@ class Engine:
             d = ops.stats_pool_bwd(saved["feat"], dpooled, self.pool_mode, amax_out=d_amax)
             if on_stage_done:
                 on_stage_done("head")
-            nblk = len(self.blocks)
-            stage_of = []
-            for li in range(1, 5):
-                stage_of += [li] * len(getattr(m.res, "layer%d" % li))
+            stage_of = self.stage_of
             part = None      # BatchNorm-backward partial sums of `d`, when the producing dgrad epilogue made them
-            last_stage = stage_of[-1]
-            for bi in range(nblk - 1, -1, -1):
-                # the gradient this block hands down is the gradient wrt the previous block's (or the stem's)
-                # BN+ReLU output: let the data-gradient epilogue reduce that BatchNorm's backward statistics
-                if bi > 0:
-                    prev = (saved["blocks"][bi - 1]["raws"][-1], self.blocks[bi - 1].bns[-1].t4)
-                else:
-                    prev = (saved["raw0"], self.stem_bn.t4)
-                chan = self.chan_amax and amx is not None and stage_of[bi] == last_stage
-                if chan and bi > 0 and stage_of[bi - 1] == last_stage:
-                    prev = None            # that BatchNorm's statistics come from its own reduction pass, with per-channel absmax
-                if bi > 0 and self.blocks[bi - 1].se is not None:
-                    # below an SE block the gradient wrt that BatchNorm's output is g e + dq / HW, not d [out > 0]: the epilogue
-                    # reduction (EPI_BNBWD) does not apply - its statistics come from the block's own tables (se_bwd_gate)
-                    prev = None
+            for bi in range(len(self.blocks) - 1, -1, -1):
+                chan = self.chan_amax and amx is not None and stage_of[bi] == stage_of[-1]
+                prev = self._bn_below(saved, bi, chan)
                 d, part, d_amax = self._block_bwd(self.blocks[bi], saved["blocks"][bi], d, acc, part, prev, d_amax, amx, chan)
                 saved["blocks"][bi] = None
                 if on_stage_done and (bi == 0 or stage_of[bi - 1] != stage_of[bi]):
@@ -579,17 +559,35 @@ class Engine:
             if on_stage_done:
                 on_stage_done("stem")
 
+    def _bn_below(self, saved, bi, chan):
+        """The gradient block `bi` hands down is the gradient wrt the BN+ReLU output below it - the last BatchNorm of the previous
+        block, or the stem's.  -> (raw, t4) of that BatchNorm when the block's last data gradient may reduce its backward
+        statistics in its epilogue (EPI_BNBWD), None when they have to come from a pass of their own.  chan: block `bi` takes
+        per-channel absmax rows (Engine.chan_amax: the f16x3 backward, last stage)."""
+        if bi == 0:
+            return saved["raw0"], self.stem_bn.t4
+        below = self.blocks[bi - 1]
+        if below.se is not None:
+            # below an SE block the gradient wrt that BatchNorm's output is g e + dq / HW, not d [out > 0]: the epilogue
+            # reduction does not apply - its statistics come from the block's own tables (se_bwd_gate)
+            return None
+        if chan and self.stage_of[bi - 1] == self.stage_of[bi]:
+            return None                    # that BatchNorm's statistics come from its own reduction pass, with per-channel absmax
+        return saved["blocks"][bi - 1]["raws"][-1], below.bns[-1].t4
+
     def _block_bwd(self, b, rec, dout, acc, dout_partial=None, prev=None, dout_amax=None, amx=None, chan=False):
         """Backward of one residual block.  -> (gradient wrt the block input, BN-backward partial sums of it or None,
         absmax slot of it or None).
 
         Walks the convs last to first.  `g` is the gradient wrt the OUTPUT of bn_i (+ReLU): dout for the last BN (mask
         = block output > 0), the data gradient of conv_{i+1} for the inner ones (mask recomputed from raw_i).  For a
-        stride-1 conv_i the BatchNorm backward of bn_i is applied inside the data-gradient kernel's input staging
-        (IN_BNBWD): no separate apply pass; the kernel writes draw_i (for the weight gradient) and, for the last BN,
-        dz (the shortcut gradient) as side products.  Stride-2 convs (parity-class launches) keep the separate pass.
-        amx (f16x3 backward): the step's absmax slot table; g / draw / dx each carry a slot (see Engine.backward).
-        chan: the last BatchNorm's scale bound uses the per-channel absmax of dz (Engine.chan_amax; dout_partial must be None)."""
+        stride-1 conv_i of up to fuse_apply_max_c channels the BatchNorm backward of bn_i is applied inside the data-gradient
+        kernel's input staging (IN_BNBWD): no separate apply pass; the kernel writes draw_i (for the weight gradient) and, for
+        the last BN of a downsample block, dz (the shortcut gradient) as side products.  Stride-2 convs (parity-class launches),
+        wider ones and the last BN of an SE block keep a separate pass.
+        prev: Engine._bn_below.  amx (f16x3 backward): the step's absmax slot table; g / draw / dx each carry a slot (see
+        Engine.backward).  chan: the last BatchNorm's scale bound uses the per-channel absmax of dz (Engine.chan_amax)."""
+        assert not chan or dout_partial is None, "the per-channel absmax comes out of the reduction pass"
         x, raws, out = rec["x"], rec["raws"], rec["out"]
         n = len(b.convs)
         g, g_part, g_amax, dz = dout, dout_partial, dout_amax, None
@@ -600,106 +598,53 @@ class Engine:
             inp = x if i == 0 else raws[i - 1]
             in_aff = None if i == 0 else (b.bns[i - 1].t4[2], b.bns[i - 1].t4[3])
             hw = (inp.shape[1], inp.shape[2])
-            act = out if last else None
-            f16 = amx is not None and ops.split_for(c.k, True) == 3     # data / weight gradients with fp16 two-term operands
-            # what this conv's data gradient must also do in its epilogue
-            add_dz, bnb = False, None
-            if i > 0:
-                if c.stride == 1 and self.fuse_bn_reduce:
-                    bnb = (raws[i - 1], None, b.bns[i - 1].t4)        # statistics of bn_{i-1}'s backward
-            elif b.ds is None:
-                add_dz = True                                           # identity shortcut: dx = dgrad + dz
-                if c.stride == 1 and self.fuse_bn_reduce and prev is not None:
-                    bnb = (prev[0], x, prev[1])                         # statistics for the previous block's last BN
-                    if rec.get("xmask") is not None:
-                        bnb = bnb + (rec["xmask"],)                     # sign bits of x instead of x itself
-            res_amax, draw_amax = take(), take()
-            # f16x3: the gradient wrt the raw conv output (draw) travels as an f16 PAIR tensor - written once in the two-term
-            # form under a rigorous bound known before it is computed, staged by plain copy in its data and weight gradients
-            pairs = f16 and self.pair_draw
+            # data / weight gradients with fp16 two-term operands.  Then the gradient wrt the raw conv output (draw) travels as an
+            # f16 PAIR tensor - written once in the two-term form under a rigorous bound known before it is computed, staged by
+            # plain copy in its data and weight gradients - and amx16 hands out the slot of that bound
+            f16 = amx is not None and ops.split_for(c.k, True) == 3
+            amx16 = amx if f16 else None
             raw_amax = rec["raw_amax"][i] if f16 else None
-            se_last = last and b.se is not None     # (never the fused IN_BNBWD form: it assumes dz = g [out > 0])
-            if not se_last and self.fuse_bn_apply and c.stride == 1 and (self.fuse_apply_min_c <= c.cout <= self.fuse_apply_max_c
-                                                                         or (c.k == 1 and self.fuse_apply_1x1)):
-                ca = None
-                if g_part is None:
-                    ca = amx.take_n(c.cout) if (chan and last and f16) else None
-                    g_part = ops.bn_bwd_partial(g, raw, act, bn.t4, MASK_ACT if last else MASK_RAW, chan_amax=ca)
-                est = take() if f16 else None
-                coef = ops.bn_bwd_coef(g_part, raw.numel() // raw.shape[-1], bn.h.weight.data, bn.t4, bn.h.weight.grad,
-                                       bn.h.bias.grad, acc, amax_in=g_amax, raw_amax=raw_amax, est_out=est, chan_amax=ca)
-                draw = torch.empty_like(raw)
-                # the shortcut gradient dz = dout*[out > 0]: with an identity shortcut and sign masks it is never stored - the
-                # first conv's data-gradient epilogue re-forms it from dout and the mask bits
-                lazy_dz = b.ds is None and rec.get("mask") is not None and n > 1
-                dzb = torch.empty_like(raw) if (last and not lazy_dz) else None
-                inb = (raw, act, bn.t4, coef)
-                if last and rec.get("mask") is not None:
-                    inb = inb + (rec["mask"],)                          # sign bits of the block output instead of it
-                if add_dz and lazy_dz:
-                    res = ops.conv_dgrad(g, c.wpk_t, c.cin, c.k, 1, hw, add=dout, add_mask=rec["mask"], bn_bwd=bnb,
-                                         in_bnbwd=inb, side=(draw, dzb), in_amax=est, out_amax=res_amax, side_amax=draw_amax,
-                                         side_presplit=pairs)
-                else:
-                    res = ops.conv_dgrad(g, c.wpk_t, c.cin, c.k, 1, hw, add=dz if add_dz else None, bn_bwd=bnb,
-                                         in_bnbwd=inb, side=(draw, dzb), in_amax=est, out_amax=res_amax, side_amax=draw_amax,
-                                         side_presplit=pairs)
-                if last:
-                    dz = dzb
-                draw_slot = est if pairs else draw_amax
-                self._count(draw, draw_slot, pairs=pairs)
-                if self.bound_log is not None and est is not None:
-                    self.bound_log.append((c.cout, c.k, est, draw_amax))
+            # which form bn_i's backward takes.  An SE block's last BatchNorm is never fused: IN_BNBWD assumes dz = g [out > 0]
+            se = last and b.se is not None
+            fused = not se and c.stride == 1 and c.cout <= self.fuse_apply_max_c
+            bits = rec["mask"] if last else None    # sign words of the block output; an inner mask is recomputed from raw_i
+            # the shortcut gradient dz = dout*[out > 0] is stored for the downsample branch only.  With an identity shortcut it
+            # is never stored: the first conv's data-gradient epilogue re-forms it from dout and the mask bits (dx = dgrad + dz)
+            keep_dz = last and b.ds is not None
+            add, add_mask = (dout, rec["mask"]) if (i == 0 and b.ds is None) else (None, None)
+            ca_n = c.cout if (chan and last and f16) else 0     # channels of the per-channel absmax row of dz, 0 = none
+            # what this conv's data gradient also reduces in its epilogue (stride 1 only): the backward statistics of bn_{i-1},
+            # or - identity shortcut - of the BatchNorm below the block, masked by the sign bits of x
+            bnb = None
+            if c.stride == 1 and i > 0:
+                bnb = (raws[i - 1], None, b.bns[i - 1].t4)
+            elif c.stride == 1 and b.ds is None and prev is not None:
+                bnb = (prev[0], x, prev[1], rec["xmask"])
+            res_amax, draw_amax = take(), take()
+            if fused:
+                draw, draw_slot, dz_i, inb = self._bnbwd_fused(bn, raw, g, g_part, g_amax, bits, out if last else None, keep_dz,
+                                                               acc, amx16, raw_amax, draw_amax, ca_n)
+                res = ops.conv_dgrad(g, c.wpk_t, c.cin, c.k, 1, hw, add=add, add_mask=add_mask, bn_bwd=bnb, in_bnbwd=inb,
+                                     side=(draw, dz_i), in_amax=draw_slot if f16 else None, out_amax=res_amax,
+                                     side_amax=draw_amax, side_presplit=f16)
             else:
-                lazy_dz = False
-                est = take() if pairs else None
-                pair = (g_amax, raw_amax, est) if pairs else None
-                if se_last:
-                    # SE block: e = dout [out > 0] is the shortcut gradient; the BatchNorm sees dz = g e + dq / HW.  One pass
-                    # reduces (sum e, sum e raw) per utterance, the gate kernels turn those tables into dW1, dW2, dq and the
-                    # BatchNorm-backward statistics, one pass writes draw (and e, unless the first conv re-forms it from the bits)
-                    bits = rec.get("mask")
-                    lazy_dz = b.ds is None and bits is not None and n > 1
-                    ca = amx.take_n(c.cout) if (chan and pairs) else None
-                    mode, actm = (MASK_BITS, bits) if bits is not None else (MASK_ACT, out)
-                    sums, q, u, gate = rec["se"]
-                    S = ops.se_bwd_reduce(g, raw, actm, mode, chan_amax=ca)
-                    w1, w2 = b.se.w1, b.se.w2
-                    coef, dq, _, _ = ops.se_bwd_gate(S, sums, q, u, gate, w1.data, w2.data, bn.t4, bn.h.weight.data, w1.grad,
-                                                     w2.grad, bn.h.weight.grad, bn.h.bias.grad, raw.shape[1] * raw.shape[2],
-                                                     accumulate=acc, pair=pair, chan_amax=ca)
-                    draw = ops.se_bwd_apply(g, raw, actm, mode, gate, dq[1], bn.t4, coef, e_out=None if lazy_dz else g,
-                                            amax_out=draw_amax, pair_scale=est)
-                    dz = None if lazy_dz else g                         # (dout now holds e)
-                elif last:
-                    # separate BatchNorm-backward pass (then a plain, pipelined data gradient).  With sign masks it reads the
-                    # bits instead of the block output, and with an identity shortcut dz is not stored: the first conv's
-                    # data-gradient epilogue re-forms it from dout and the bits (as in the fused form above)
-                    bits = rec.get("mask")
-                    lazy_dz = b.ds is None and bits is not None and n > 1
-                    ca = amx.take_n(c.cout) if (chan and pairs and g_part is None) else None
-                    draw = ops.bn_backward(g, raw, bits if bits is not None else out, bn.t4, bn.h.weight.data, bn.h.weight.grad,
-                                           bn.h.bias.grad, MASK_BITS if bits is not None else MASK_ACT,
-                                           dz_out=None if lazy_dz else g, accumulate=acc, partial=g_part, amax_out=draw_amax,
-                                           pair=pair, chan_amax=ca)
-                    dz = None if lazy_dz else g                         # (dout now holds dz)
+                if se:
+                    draw, draw_slot, dz_i = self._bnbwd_se(b.se, rec["se"], bn, raw, g, g_amax, bits, keep_dz, acc, amx16,
+                                                           raw_amax, draw_amax, ca_n)
                 else:
-                    draw = ops.bn_backward(g, raw, None, bn.t4, bn.h.weight.data, bn.h.weight.grad, bn.h.bias.grad, MASK_RAW,
-                                           draw_out=g, accumulate=acc, partial=g_part, amax_out=draw_amax, pair=pair)
-                draw_slot = est if pairs else draw_amax
-                self._count(draw, draw_slot, pairs=pairs)
-                if self.bound_log is not None and est is not None:
-                    self.bound_log.append((c.cout, c.k, est, draw_amax))
-                if add_dz and dz is None and rec.get("mask") is not None:
-                    res = ops.conv_dgrad(draw, c.wpk_t, c.cin, c.k, c.stride, hw, add=dout, add_mask=rec["mask"], bn_bwd=bnb,
-                                         in_amax=draw_slot if f16 else None, out_amax=res_amax, in_presplit=pairs)
-                else:
-                    res = ops.conv_dgrad(draw, c.wpk_t, c.cin, c.k, c.stride, hw, add=dz if add_dz else None, bn_bwd=bnb,
-                                         in_amax=draw_slot if f16 else None, out_amax=res_amax, in_presplit=pairs)
+                    draw, draw_slot, dz_i = self._bnbwd_pass(bn, raw, g, g_part, g_amax, bits, keep_dz, acc, amx16, raw_amax,
+                                                             draw_amax, ca_n)
+                res = ops.conv_dgrad(draw, c.wpk_t, c.cin, c.k, c.stride, hw, add=add, add_mask=add_mask, bn_bwd=bnb,
+                                     in_amax=draw_slot if f16 else None, out_amax=res_amax, in_presplit=f16)
+            if last:
+                dz = dz_i
+            self._count(draw, draw_slot, pairs=f16)
+            if self.bound_log is not None and f16:
+                self.bound_log.append((c.cout, c.k, draw_slot, draw_amax))
             g, g_part = res if bnb is not None else (res, None)
             g_amax = res_amax
             self._wgrad(inp, draw, c.h.weight.grad, c.k, c.stride, in_affine=in_aff, accumulate=acc,
-                        dy_amax=draw_slot if f16 else None, x_amax=rec["in_amax"][i] if f16 else None, dy_presplit=pairs)
+                        dy_amax=draw_slot if f16 else None, x_amax=rec["in_amax"][i] if f16 else None, dy_presplit=f16)
         dx, part, dx_amax = g, g_part, g_amax
         if b.ds is not None:
             cd, bnd = b.ds
@@ -715,6 +660,55 @@ class Engine:
                            in_amax=drawd_amax, out_amax=dx_amax)
             part = None
         return dx, part, dx_amax
+
+    # The three forms of one BatchNorm backward inside _block_bwd.  g / g_part / g_amax: the gradient wrt the BatchNorm's (+ReLU)
+    # output, its partial sums when the producing epilogue made them, its absmax slot.  bits: sign words of the block output (the
+    # last BatchNorm) or None (an inner one).  keep_dz: also store dz.  amx16: the slot table in the f16x3 mode, else None.
+    # ca_n: channels of the per-channel absmax row to take, or 0.  -> (draw, the slot that scales draw for its consumers, dz).
+    def _bnbwd_fused(self, bn, raw, g, g_part, g_amax, bits, act, keep_dz, acc, amx16, raw_amax, draw_amax, ca_n):
+        """Fused into the data gradient of the same convolution: reduce (unless g_part came from an epilogue; the last BatchNorm
+        from the block output `act`) and finalize here; the data gradient applies it while staging and writes draw and dz as
+        side outputs.  -> (draw, draw_slot, dz, in_bnbwd operand of that data gradient); draw and dz are still empty."""
+        ca = amx16.take_n(ca_n) if ca_n else None
+        if g_part is None:
+            g_part = ops.bn_bwd_partial(g, raw, act, bn.t4, MASK_RAW if bits is None else MASK_ACT, chan_amax=ca)
+        est = amx16.take() if amx16 else None
+        coef = ops.bn_bwd_coef(g_part, raw.numel() // raw.shape[-1], bn.h.weight.data, bn.t4, bn.h.weight.grad,
+                               bn.h.bias.grad, acc, amax_in=g_amax, raw_amax=raw_amax, est_out=est, chan_amax=ca)
+        draw = torch.empty_like(raw)
+        dz = torch.empty_like(raw) if keep_dz else None
+        inb = (raw, act, bn.t4, coef) if bits is None else (raw, act, bn.t4, coef, bits)
+        return draw, (est if amx16 else draw_amax), dz, inb
+
+    def _bnbwd_pass(self, bn, raw, g, g_part, g_amax, bits, keep_dz, acc, amx16, raw_amax, draw_amax, ca_n):
+        """Stand-alone BatchNorm-backward pass (then a plain, pipelined data gradient).  An inner BatchNorm overwrites g with draw;
+        the last one reads the bits instead of the block output and leaves dout alone, or (keep_dz) turns it into dz."""
+        est = amx16.take() if amx16 else None
+        pair = (g_amax, raw_amax, est) if amx16 else None
+        ca = amx16.take_n(ca_n) if ca_n else None
+        dz = g if keep_dz else None
+        draw = ops.bn_backward(g, raw, bits, bn.t4, bn.h.weight.data, bn.h.weight.grad, bn.h.bias.grad,
+                               MASK_RAW if bits is None else MASK_BITS, draw_out=g if bits is None else None, dz_out=dz,
+                               accumulate=acc, partial=g_part, amax_out=draw_amax, pair=pair, chan_amax=ca)
+        return draw, (est if amx16 else draw_amax), dz
+
+    def _bnbwd_se(self, se, se_rec, bn, raw, g, g_amax, bits, keep_dz, acc, amx16, raw_amax, draw_amax, ca_n):
+        """Last BatchNorm of an SE block (se: the gate's parameters, se_rec: what its forward saved): e = dout [out > 0] is the
+        shortcut gradient; the BatchNorm sees dz = g e + dq / HW.  One pass reduces (sum e, sum e raw) per utterance, the gate
+        kernels turn those tables into dW1, dW2, dq and the BatchNorm-backward statistics, one pass writes draw (and, keep_dz,
+        e over dout)."""
+        est = amx16.take() if amx16 else None
+        pair = (g_amax, raw_amax, est) if amx16 else None
+        ca = amx16.take_n(ca_n) if ca_n else None
+        sums, q, u, gate = se_rec
+        S = ops.se_bwd_reduce(g, raw, bits, MASK_BITS, chan_amax=ca)
+        w1, w2 = se.w1, se.w2
+        coef, dq, _, _ = ops.se_bwd_gate(S, sums, q, u, gate, w1.data, w2.data, bn.t4, bn.h.weight.data, w1.grad, w2.grad,
+                                         bn.h.weight.grad, bn.h.bias.grad, raw.shape[1] * raw.shape[2], accumulate=acc,
+                                         pair=pair, chan_amax=ca)
+        e = g if keep_dz else None
+        draw = ops.se_bwd_apply(g, raw, bits, MASK_BITS, gate, dq[1], bn.t4, coef, e_out=e, amax_out=draw_amax, pair_scale=est)
+        return draw, (est if amx16 else draw_amax), e
 
     # ---- fused training step (forward + CE + backward, no autograd graph) --------------------------------------
     def loss_and_grad(self, x, y, on_stage_done=None):
