@@ -362,6 +362,36 @@ int spk_stats_pool_bwd(const float* x, const float* gout, float* dx, int B, int 
 int spk_stats_pool_row_form(int on);
 int spk_stats_pool_row_cap(void);
 
+/* ---- half-precision extraction (precision="f16"; csrc/half.hip) -------------------------------------
+ * Eval mode only.  Activations are NHWC fp16 tensors; a multiply-accumulate is ONE fp16 product on v_mfma_f32_16x16x32_f16 with
+ * fp32 accumulation; the epilogue is fp32 and rounds once to fp16 (nearest even, subnormals kept).  A stored value outside
+ * fp16's range is stored as +-inf and counted: every entry below ADDS the number of not-finite values it stored for image b to
+ * ovf[b] (DEVICE int array [B], zeroed by the caller before the first launch of a forward).  Nothing is clamped.
+ * wlen (may be NULL): DEVICE int array [B]; outputs of image b at width (time) x >= wlen[b] are stored as +0. */
+/* bytes of a packed weight = 2 Cout Cin KH KW: 1 KB fragment images [KH*KW][Cin/32][Cout/16][lane 64][8 halfs], lane l element j =
+ * w[16 m + (l & 15)][32 s + 8 (l >> 4) + j][tap] rounded to fp16.  Cin, Cout in {32, 64, 128, 256}, 1x1 or 3x3; rc < 0 otherwise */
+int spk_h16_packed_bytes(int Cout, int Cin, int KH, int KW);
+/* OIHW fp32 (Conv2d.weight, scripts/model.py:32-34,104-110) -> the packed fp16 form, rounded once to nearest even; a weight
+ * outside fp16's range becomes +-inf (not refused) */
+int spk_h16_pack_conv_weight(const float* w_oihw, void* out, int Cout, int Cin, int KH, int KW, void* stream);
+/* the output tile of spk_h16_conv_fwd: rows (which = 0) and columns (which = 1); a block runs (which = 2) consecutive tiles, their
+ * loads pipelined across tile boundaries, once a launch has (which = 3) or more (tile, output-channel tile) pairs, else one */
+int spk_h16_conv_tile(int which);
+/* stem conv1 + bn1 + ReLU in eval mode (scripts/model.py:249-251): the fp32 arithmetic of spk_stem_conv_fwd(_len) with
+ * SPK_EPI_AFFINE | SPK_EPI_RELU, frames t >= wlen[b] read as 0; the result is stored as fp16 [B][F][T][32] */
+int spk_h16_stem_fwd(const float* x, const float* w, const float* scale, const float* shift, void* out_f16, const int* wlen,
+                     int* ovf, int B, int F, int T, void* stream);
+/* conv + eval BatchNorm (+ residual) (+ ReLU) of a block (scripts/model.py:48-64,118-138): 3x3 pad 1 or 1x1 pad 0, stride 1 or 2,
+ * NHWC fp16 in [B][IH][IW][Cin] -> out [B][ceil(IH/stride)][ceil(IW/stride)][Cout] fp16:
+ *   v = acc * scale[c] + shift[c];  v += float(add[same address as out]) (add may be NULL);  relu: v = max(v, 0);  length mask;
+ *   one rounding to fp16.  The sum over (tap, Cin) is never split across blocks. */
+int spk_h16_conv_fwd(const void* in_f16, const void* wpk, const float* scale, const float* shift, const void* add_f16,
+                     void* out_f16, const int* wlen, int* ovf, int B, int IH, int IW, int Cin, int Cout, int ksize, int stride,
+                     int relu, void* stream);
+/* StatsPooling (scripts/model.py:435-457) of an fp16 map in fp32: the formulas and the two-pass order of spk_stats_pool_fwd(_len),
+ * swapped var / sqrt(mean) outputs included; wlen (may be NULL) as in spk_stats_pool_fwd_len.  out: fp32 [B][C*H*(1+mode)] */
+int spk_h16_stats_pool_fwd(const void* in_f16, float* out, const int* wlen, int B, int H, int W, int C, int mode, void* stream);
+
 /* ---- GEMM (fc1 = nn.Linear(5120,256) scripts/model.py:357; cosine F.linear :485; their gradients) ------ */
 /* C[m][n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]) (+ C[m][n]).  64x64 tiles on the fp32 matrix
  * instruction, K cut into spk_gemm_splitk(M,N,K) slices whose partial tiles go through `workspace`

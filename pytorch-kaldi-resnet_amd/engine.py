@@ -35,6 +35,7 @@ class _Conv:
         self.cin, self.cout, self.k, self.stride = holder.cin, holder.cout, holder.k, holder.stride
         self.wpk = None
         self.wpk_t = None
+        self.wpk_h = None       # fp16 fragment images of the half-precision extraction path (ops.h16_pack_conv_weight)
 
     def repack(self, need_t):
         w = self.h.weight.data
@@ -137,6 +138,8 @@ class Engine:
                 self.stage_of.append(li)
         self.head_bn = _BN(model.bn1) if hasattr(model, "bn1") else None
         self.pool_mode = 1 if model.pooling == "mean+std" else 0
+        self._half_dirty = True        # the fp16 weight packs of the half-precision extraction path lag the weights
+        self.half_overflow = None      # int32 [B] device tensor of the last half predict: stored values that left fp16's range
         self.dirty = True
         self._packed_for_bwd = False
         self._pack_tables = {}
@@ -175,6 +178,17 @@ class Engine:
         self.bound_log = None          # diagnostics: when a list, (Cout, k, bound slot, true-absmax slot) of every BatchNorm-backward scale
 
     # ---- helpers ---------------------------------------------------------------------------------------
+    @property
+    def dirty(self):
+        """the weights changed since the fp32 packs were built (SGD step, load_state_dict, loadParameters, .cuda())"""
+        return self._dirty
+
+    @dirty.setter
+    def dirty(self, v):
+        self._dirty = v
+        if v:
+            self._half_dirty = True    # cleared only by _repack_half: the two pack sets are rebuilt independently
+
     @property
     def fuse_apply_max_c(self):
         if self._fuse_apply_max_c is not None:
@@ -295,6 +309,47 @@ class Engine:
         pooled = ops.stats_pool_fwd(feat, self.pool_mode, wlen=None if wl is None else wl[3])
         return ops.linear_fwd(pooled, self.m.fc1.weight.data, self.m.fc1.bias.data)
 
+    # ---- half-precision extraction (precision="f16") ---------------------------------------------
+    def _repack_half(self):
+        if self.m.arch == "se_resnet34":
+            raise NotImplementedError("precision='f16' does not support arch se_resnet34 yet (squeeze-and-excitation blocks in half "
+                                      "precision are a follow-up): use precision='f32'")
+        if not self._half_dirty:
+            return
+        for c in self._all_convs():
+            c.wpk_h = ops.h16_pack_conv_weight(c.h.weight.data, c.wpk_h)
+        self._half_dirty = False
+
+    def trunk_eval_half(self, x, wl=None):
+        """trunk_eval on fp16 activations with one fp16 product per multiply-accumulate: the stem in fp32 arithmetic stored as
+        fp16, every convolution with its eval BatchNorm (fp32 scale / shift rows), residual, ReLU and length mask in an fp32
+        epilogue rounded once.  The masking rule is trunk_eval's.  Resets and fills self.half_overflow."""
+        self._repack_half()
+        ovf = self.half_overflow = torch.zeros(x.shape[0], device=x.device, dtype=torch.int32)
+        e = self.stem_bn.eval_coeffs()
+        a = ops.h16_stem_fwd(x, self.stem_conv.h.weight.data, e[0], e[1], ovf, wlen=None if wl is None else wl[0])
+        stage = 0
+        for b in self.blocks:
+            evs = [bn.eval_coeffs() for bn in b.bns]
+            if b.ds is not None:
+                cd, ed = b.ds[0], b.ds[1].eval_coeffs()
+                res = ops.h16_conv_fwd(a, cd.wpk_h, cd.cout, 1, cd.stride, ed[0], ed[1], ovf, relu=False)
+            else:
+                res = a
+            h, n = a, len(b.convs)
+            for i, (c, ev) in enumerate(zip(b.convs, evs)):
+                if c.stride == 2:
+                    stage += 1
+                h = ops.h16_conv_fwd(h, c.wpk_h, c.cout, c.k, c.stride, ev[0], ev[1], ovf, add=res if i == n - 1 else None,
+                                     relu=True, wlen=None if wl is None else wl[stage])
+            a = h
+        return a
+
+    def embed_eval_half(self, x, wl=None):
+        feat = self.trunk_eval_half(x, wl)
+        pooled = ops.h16_stats_pool_fwd(feat, self.pool_mode, wlen=None if wl is None else wl[3])
+        return ops.linear_fwd(pooled, self.m.fc1.weight.data, self.m.fc1.bias.data)
+
     @staticmethod
     def stage_widths(lengths, B, T, device):
         """Validated per-utterance lengths -> int32 [4][B] on `device`: the valid widths of the stem and layer 1 (L), then of the
@@ -321,13 +376,24 @@ class Engine:
             w.append((w[-1] + 1) // 2)
         return torch.stack(w).to(torch.int32).to(device)
 
-    def predict(self, x, lengths=None):
+    def predict(self, x, lengths=None, precision="f32"):
         """scripts/model.py:402-409.  Uses BN batch statistics when the module is in train mode, exactly like
         the reference would; decode.py always calls it under model.eval().
         lengths (eval mode only): per-utterance frame counts of a padded batch x [B, F, T] - row b is the embedding of
-        x[b, :, :lengths[b]] alone, whatever the padding holds (length-masked stem, convolutions and pooling)."""
+        x[b, :, :lengths[b]] alone, whatever the padding holds (length-masked stem, convolutions and pooling).
+        precision: "f32" (the project's fp32 contract) or, eval mode only, "f16": fp16 activations and one fp16 product per
+        multiply-accumulate (embed_eval_half).  A row whose activations left fp16's range has self.half_overflow[b] > 0 and
+        its embedding is not to be used: predict such rows again with precision="f32"."""
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16', got %r" % (precision,))
         x = self._check_input(x)
         with torch.no_grad():
+            if precision == "f16":
+                if self.m.training:
+                    raise RuntimeError("predict(precision='f16') needs eval mode: the half-precision path applies the running "
+                                       "BatchNorm statistics (call model.eval() first)")
+                wl = None if lengths is None else self.stage_widths(lengths, x.shape[0], x.shape[2], x.device)
+                return self.embed_eval_half(x, wl)
             if lengths is not None:
                 if self.m.training:
                     raise RuntimeError("predict(lengths=...) needs eval mode: with BatchNorm batch statistics a padded batch has "

@@ -75,6 +75,12 @@ _SIGS = {
     "spk_stats_pool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "spk_stats_pool_row_form": [_I],
     "spk_stats_pool_row_cap": [],
+    "spk_h16_packed_bytes": [_I, _I, _I, _I],
+    "spk_h16_pack_conv_weight": [_P, _P, _I, _I, _I, _I, _P],
+    "spk_h16_conv_tile": [_I],
+    "spk_h16_stem_fwd": [_P] * 7 + [_I] * 3 + [_P],
+    "spk_h16_conv_fwd": [_P] * 8 + [_I] * 8 + [_P],
+    "spk_h16_stats_pool_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "spk_gemm_f32": [_P] * 4 + [_I] * 3 + [_L] * 5 + [_F, _I, _P, _P],
     "spk_gemm_splitk": [_I, _I, _I],
     "spk_colsum": [_P, _P, _I, _I, _I, _P],
@@ -179,7 +185,7 @@ def exported_symbols():
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL). Requires a contiguous fp32/int64/int32 CUDA(HIP) tensor."""
+    """Device pointer of a tensor (None -> NULL). Requires a contiguous fp32/fp16/int64/int32 CUDA(HIP) tensor."""
     if t is None:
         return None
     assert t.is_cuda, "libspkhip takes device tensors only"

@@ -234,12 +234,15 @@ class NeuralSpeakerModel(nn.Module):
         """Logits [B, spk_num] (scripts/model.py:374-400). Differentiable: loss.backward() fills .grad."""
         return self.engine().forward_logits(x, y)
 
-    def predict(self, x, lengths=None):
+    def predict(self, x, lengths=None, precision="f32"):
         """Embeddings [B, 256] = fc1 output (scripts/model.py:402-409).
         lengths: optional per-utterance frame counts [B] (list or integer tensor, any device, 1 <= L[b] <= T) of a padded batch
         x [B, F, T], eval mode only: row b is then the embedding of x[b:b+1, :, :lengths[b]] predicted alone - the frames past
-        lengths[b] are ignored whatever they hold.  None: the plain batched predict."""
-        return self.engine().predict(x, lengths)
+        lengths[b] are ignored whatever they hold.  None: the plain batched predict.
+        precision: "f32" (default: the fp32 path, unchanged) or "f16" (eval mode, not se_resnet34): fp16 activations and one fp16
+        product per multiply-accumulate.  After an "f16" call engine().half_overflow [B] int32 counts, per row, the stored
+        activations that left fp16's range; a row with a non-zero count must be predicted again with precision="f32"."""
+        return self.engine().predict(x, lengths, precision)
 
     def loadParameters(self, loaded_state):
         """scripts/model.py:415-432: name match, strip 'module.', skip on shape mismatch, same messages."""

@@ -947,6 +947,88 @@ def stats_pool_bwd(x, gout, mode, amax_out=None):
     return dx
 
 
+# ---- half-precision extraction (csrc/half.hip): fp16 NHWC activations, one fp16 product per MAC ------------
+def h16_conv_tile():
+    """(rows, columns) of the output tile of one block of spk_h16_conv_fwd"""
+    return hip.lib().spk_h16_conv_tile(0), hip.lib().spk_h16_conv_tile(1)
+
+
+def h16_conv_tiles_per_block():
+    """(tiles per block, the number of (tile, output-channel tile) pairs of a launch from which on a block runs that many)"""
+    return hip.lib().spk_h16_conv_tile(2), hip.lib().spk_h16_conv_tile(3)
+
+
+def h16_packed_bytes(Cout, Cin, KH, KW):
+    n = hip.lib().spk_h16_packed_bytes(Cout, Cin, KH, KW)
+    if n < 0:
+        hip.check(n, "spk_h16_packed_bytes")
+    return n
+
+
+def h16_pack_conv_weight(w, out=None):
+    """OIHW fp32 -> the fp16 fragment images spk_h16_conv_fwd reads (a flat float16 tensor), rounded once to nearest even"""
+    Cout, Cin, KH, KW = w.shape
+    n = h16_packed_bytes(Cout, Cin, KH, KW) // 2
+    if out is None or out.numel() != n:
+        out = torch.empty(n, device=w.device, dtype=torch.float16)
+    call("spk_h16_pack_conv_weight", ptr(w.contiguous()), ptr(out), Cout, Cin, KH, KW, stream())
+    return out
+
+
+def _check_h16(t, name):
+    if t.dtype != torch.float16:
+        raise TypeError("%s must be a float16 tensor, got %s" % (name, t.dtype))
+
+
+def _check_ovf(ovf, B):
+    if ovf.dtype != torch.int32 or ovf.numel() != B:
+        raise ValueError("ovf must be an int32 tensor [B=%d], got %s %s" % (B, ovf.dtype, tuple(ovf.shape)))
+
+
+def h16_stem_fwd(x, w, scale, shift, ovf, wlen=None):
+    """x [B][F][T] fp32 -> relu(bn(conv(x))) as fp16 [B][F][T][32]; adds the not-finite stores of row b to ovf[b]"""
+    B, F, T = x.shape
+    _check_ovf(ovf, B)
+    if wlen is not None:
+        _check_wlen(wlen, B)
+    out = torch.empty(B, F, T, 32, device=x.device, dtype=torch.float16)
+    call("spk_h16_stem_fwd", ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(out), ptr(wlen), ptr(ovf), B, F, T, stream(),
+         label="h16_stem", flops=2.0 * 9 * 32 * B * F * T, nbytes=4.0 * x.numel() + 2.0 * out.numel())
+    return out
+
+
+def h16_conv_fwd(x, wpk, Cout, ksize, stride, scale, shift, ovf, add=None, relu=True, wlen=None):
+    """x [B][IH][IW][Cin] fp16 -> [B][ceil(IH/stride)][ceil(IW/stride)][Cout] fp16 (3x3 pad 1 or 1x1):
+    round16(mask(relu(acc * scale + shift + add))); adds the not-finite stores of row b to ovf[b]"""
+    _check_h16(x, "x")
+    B, IH, IW, Cin = x.shape
+    _check_ovf(ovf, B)
+    OH, OW = (IH + stride - 1) // stride, (IW + stride - 1) // stride
+    out = torch.empty(B, OH, OW, Cout, device=x.device, dtype=torch.float16)
+    if add is not None:
+        _check_h16(add, "add")
+        assert add.shape == out.shape, "the residual has the shape of the output"
+    if wlen is not None:
+        _check_wlen(wlen, B)
+    call("spk_h16_conv_fwd", ptr(x), ptr(wpk), ptr(scale), ptr(shift), ptr(add), ptr(out), ptr(wlen), ptr(ovf), B, IH, IW, Cin,
+         Cout, ksize, stride, 1 if relu else 0, stream(), label="h16_conv%dx%d_s%d_%dto%d" % (ksize, ksize, stride, Cin, Cout),
+         flops=2.0 * B * OH * OW * Cout * Cin * ksize * ksize,
+         nbytes=2.0 * (x.numel() + out.numel() * (2 if add is not None else 1) + Cout * Cin * ksize * ksize))
+    return out
+
+
+def h16_stats_pool_fwd(x, mode, wlen=None):
+    """x [B][H][W][C] fp16 -> fp32 [B][C*H*(1+mode)]: stats_pool_fwd's arithmetic in fp32 on the fp16 map"""
+    _check_h16(x, "x")
+    B, H, W, C = x.shape
+    if wlen is not None:
+        _check_wlen(wlen, B)
+    out = torch.empty(B, C * H * (2 if mode else 1), device=x.device, dtype=torch.float32)
+    call("spk_h16_stats_pool_fwd", ptr(x), ptr(out), ptr(wlen), B, H, W, C, mode, stream(), label="h16_stats_pool",
+         flops=4.0 * x.numel(), nbytes=2.0 * x.numel() + 4.0 * out.numel())
+    return out
+
+
 def _ptr_rows(t):
     """Device pointer of a 2-D tensor whose rows are contiguous but may be pitched (a column slice of a wider tensor): the
     callee takes stride(0) as its leading dimension."""

@@ -57,6 +57,10 @@ parser.add_argument("--mfcc-config", help="with --wav-scp: Kaldi compute-mfcc-fe
 parser.add_argument("--vad-config", help="with --wav-scp: Kaldi compute-vad config (conf/vad.conf): keep voiced frames only")
 parser.add_argument("--cmn-window", type=int, default=0,
                     help="with --wav-scp: apply-cmvn-sliding --norm-vars=false --center=true window (0: none; the recipe uses 300)")
+parser.add_argument("--half", action="store_true",
+                    help="extract with predict(precision='f16'): fp16 activations, one fp16 product per multiply-accumulate.  "
+                         "Utterances whose activations leave fp16's range are detected on the GPU and extracted again in fp32 "
+                         "(resnet18/34/50/101; not se_resnet34)")
 parser.add_argument("--out-format", default="text", choices=["text", "fv"],
                     help="text = the reference's 'utt [ v0 ... ]' lines (str(np.float32), ~0.2 ms/utt of Python formatting); "
                          "fv = binary Kaldi float-vector ark, read by the same scoring scripts")
@@ -64,6 +68,8 @@ parser.add_argument("--out-format", default="text", choices=["text", "fv"],
 
 def main():
     args = parser.parse_args()
+    if args.half and args.arch == "se_resnet34":
+        parser.error("--half does not support --arch se_resnet34 (squeeze-and-excitation blocks run in fp32 only)")
     if args.wav_scp and args.decode_scp:
         parser.error("--wav-scp and --decode-scp are mutually exclusive")
     if (args.fbank_config or args.vad_config or args.cmn_window or args.allow_downsample or args.allow_upsample) and not args.wav_scp:
@@ -164,13 +170,44 @@ def _write(f, utts, pred, fmt):
             kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=utts[i])
 
 
+class Predictor:
+    """predict() of one batch -> numpy embeddings.  --half: the half-precision predict; the per-utterance overflow counts come back
+    with the embeddings in the same device-to-host copy, and the rows whose activations left fp16's range are predicted again
+    in fp32 (x[idx], lengths[idx]) - their embeddings replace the half ones."""
+
+    def __init__(self, model, half):
+        self.model, self.half = model, half
+        self.redone = self.total = 0
+
+    def __call__(self, x, lengths=None):
+        if not self.half:
+            return self.model.predict(x, lengths=lengths).cpu().numpy()
+        emb = self.model.predict(x, lengths=lengths, precision="f16")
+        ovf = self.model.engine().half_overflow
+        both = torch.cat([emb, (ovf > 0).to(emb.dtype)[:, None]], dim=1).cpu().numpy()
+        pred = np.ascontiguousarray(both[:, :-1])
+        idx = np.nonzero(both[:, -1])[0]
+        self.total += pred.shape[0]
+        if idx.size:
+            self.redone += idx.size
+            sub = x[torch.from_numpy(idx).to(x.device)].contiguous()
+            pred[idx] = self.model.predict(sub, lengths=None if lengths is None else np.asarray(lengths)[idx]).cpu().numpy()
+        return pred
+
+    def report(self):
+        if self.half:
+            print("=> {} of {} utterances left the fp16 range and were extracted in fp32".format(self.redone, self.total))
+
+
 def sequence_generator(loader, model, out_path, args):
     model.eval()
     name = str(args.gpu) if args.distributed else "alone"
+    predict = Predictor(model, args.half)
     with open(os.path.join(out_path, name), "w" if args.out_format == "text" else "wb") as f, torch.no_grad():
         for audios, utts in loader:
-            pred = model.predict(audios.cuda(args.gpu, non_blocking=True)).cpu().numpy()
+            pred = predict(audios.cuda(args.gpu, non_blocking=True))
             _write(f, utts, pred, args.out_format)
+    predict.report()
 
 
 def native_generator(model, args):
@@ -244,6 +281,7 @@ def native_generator(model, args):
             for i in range(pred.shape[0]):
                 kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=keys[i])
 
+    predict = Predictor(model, args.half)
     with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
             ThreadPoolExecutor(1) as wr:
         nxt = rd.submit(load, 0) if mine else None
@@ -257,7 +295,7 @@ def native_generator(model, args):
                 x = features.decompress(buf[0].cuda(args.gpu, non_blocking=True), buf[1].cuda(args.gpu, non_blocking=True), lengths)
             else:
                 x = buf.cuda(args.gpu, non_blocking=True)
-            pred = model.predict(x, lengths=lengths).cpu().numpy()
+            pred = predict(x, lengths)
             if pending is not None:
                 pending.result()
             pending = wr.submit(emit, f, [utts[k] for k in b], pred)
@@ -266,6 +304,7 @@ def native_generator(model, args):
             pending.result()
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + predict + write)".format(done, dt, done / max(dt, 1e-9)))
+    predict.report()
 
 
 def wav_generator(model, args):
@@ -302,6 +341,7 @@ def wav_generator(model, args):
             for i in range(pred.shape[0]):
                 kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=ks[i])
 
+    predict = Predictor(model, args.half)
     with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
             ThreadPoolExecutor(1) as wr:
         nxt = rd.submit(load, 0) if mine else None
@@ -320,7 +360,7 @@ def wav_generator(model, args):
                 continue
             if keep.size < len(b):
                 feats = feats[torch.from_numpy(keep).to(feats.device)].contiguous()
-            pred = model.predict(feats, lengths=lengths[keep]).cpu().numpy()
+            pred = predict(feats, lengths[keep])
             if pending is not None:
                 pending.result()
             pending = wr.submit(emit, f, [keys[b[r]] for r in keep], pred)
@@ -330,6 +370,7 @@ def wav_generator(model, args):
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + front end + predict + write)".format(
             done, dt, done / max(dt, 1e-9)))
+    predict.report()
 
 
 if __name__ == "__main__":
