@@ -634,6 +634,22 @@ int spk_plda_llr(const double* en /*[n_en][D]*/, const double* te /*[n_te][D]*/,
                  const int* count /*[n_en]*/, const int* tab_count /*[U]*/, const double* tab_log /*[U][2]*/, int U, float* out,
                  int T, int D, int n_en, int n_te, void* stream);
 
+/* ---- windowed extraction (csrc/window.hip) ---------------------------------------------------------------
+ * A plan of N windows over a padded batch src [B][F][T] (fp32): window i is the frames [start[i], start[i] + len[i]) of row[i].
+ * out [N][F][Wcap]: out[i][f][j] = src[row[i]][f][start[i] + j] for j < len[i] and +0 for len[i] <= j < Wcap - the slices bit for
+ * bit.  row, start, len: the plan on the HOST, checked before anything is launched - row outside [0, B), start < 0, len < 1,
+ * start + len > T and len > Wcap are refused (< 0, out untouched); plan_dev: the same three arrays on the device, int [3][N] (row,
+ * start, len), which the kernel reads.  16-byte stores when Wcap % 4 == 0 and out is 16-byte aligned, 16-byte loads where a
+ * window's start allows them, 4-byte accesses otherwise; N * F < 2^31. */
+int spk_window_gather(const float* src, int B, int F, int T, const int* row /*host [N]*/, const int* start /*host [N]*/,
+                      const int* len /*host [N]*/, const int* plan_dev /*device [3][N]*/, float* out, int N, int Wcap, void* stream);
+/* out[u][d] = (sum_r weight[r] emb[r][d]) * (1.0f / sum_r weight[r]) over the rows r = seg_off[u] .. seg_off[u + 1] - 1 of
+ * emb [N][D], in that order: acc = fmaf(weight[r], emb[r][d], acc) and tot += weight[r] in fp32, the reciprocal correctly rounded.
+ * seg_off: host int [U + 1], checked before the launch (0 = seg_off[0] < ... < seg_off[U] = N: an empty segment is refused);
+ * seg_off_dev: the same on the device.  One lane per (u, d), no atomics. */
+int spk_window_mean(const float* emb /*[N][D]*/, int N, int D, const int* seg_off /*host [U+1]*/, const int* seg_off_dev,
+                    const float* weight /*[N]*/, float* out /*[U][D]*/, int U, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

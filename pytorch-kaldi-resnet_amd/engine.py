@@ -140,6 +140,7 @@ class Engine:
         self.pool_mode = 1 if model.pooling == "mean+std" else 0
         self._half_dirty = True        # the fp16 weight packs of the half-precision extraction path lag the weights
         self.half_overflow = None      # int32 [B] device tensor of the last half predict: stored values that left fp16's range
+        self.windows_skipped = None    # numpy int64: the utterances the last predict_windows found shorter than min_window
         self.dirty = True
         self._packed_for_bwd = False
         self._pack_tables = {}
@@ -403,6 +404,73 @@ class Engine:
                 emb, _ = self._embed_train(x, save=False)
                 return emb
             return self.embed_eval(x)
+
+    def predict_windows(self, x, lengths, window, period, min_window=None, average=False, precision="f32", batch_size=None):
+        """Windowed extraction, eval mode only.  x [B, F, T]: a padded batch, lengths: per-utterance frame
+        counts (0 <= L[b] <= T; None: T frames each).  The windows of ingest.plan_windows(lengths, window, period, min_window)
+        (min_window None: 1) are gathered into padded batches of at most batch_size rows (default B; ingest.window_batches,
+        spk_window_gather) and each runs through predict(xw, lengths=lw, precision=precision): a row is the embedding of its
+        window run alone.
+        -> (emb [N, D], utt [N], start [N], length [N]) in plan order (the last three numpy int64), or with average=True
+        (emb [U', D], utt [U']): per utterance that has a window, the mean of its window embeddings weighted by window length
+        (spk_window_mean).  self.windows_skipped: the utterances shorter than min_window.  After a precision="f16" call
+        self.half_overflow holds the count of every WINDOW, in plan order (also with average=True)."""
+        import numpy as np
+        from . import ingest
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16', got %r" % (precision,))
+        if self.m.training:
+            raise RuntimeError("predict_windows(...) needs eval mode: with BatchNorm batch statistics a batch of windows has no "
+                               "per-window meaning (call model.eval() first)")
+        x = self._check_input(x)
+        B, _, T = x.shape
+        if lengths is None:
+            L = np.full(B, T, dtype=np.int64)
+        else:
+            if isinstance(lengths, torch.Tensor):
+                if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+                    raise TypeError("lengths must be integers, got a %s tensor" % lengths.dtype)
+                lengths = lengths.detach().cpu().numpy()
+            L = np.asarray(lengths)
+            if L.dtype.kind not in "iu":
+                raise TypeError("lengths must be integers")
+            L = L.astype(np.int64)
+            if L.shape != (B,):
+                raise ValueError("lengths has shape %s for a batch of %d utterances" % (L.shape, B))
+            if B and (int(L.min()) < 0 or int(L.max()) > T):
+                raise ValueError("lengths must lie in [0, T=%d], got min %d max %d" % (T, int(L.min()), int(L.max())))
+        plan = ingest.plan_windows(L, window, period, 1 if min_window is None else min_window)
+        self.windows_skipped = plan.skipped
+        N = plan.utt.size
+        D = self.m.fc1.weight.shape[0]
+        half = precision == "f16"
+        if half:
+            self._repack_half()           # the refusals of the half path, also when there is no window to run
+        if N == 0:
+            self.half_overflow = torch.zeros(0, device=x.device, dtype=torch.int32) if half else self.half_overflow
+            emb = torch.empty(0, D, device=x.device, dtype=torch.float32)
+            return (emb, plan.utt) if average else (emb, plan.utt, plan.start, plan.length)
+        batches = ingest.window_batches(plan.length, B if batch_size is None else int(batch_size))
+        embs, ovfs = [], []
+        with torch.no_grad():
+            for idx, wcap in batches:
+                xw = ops.window_gather(x, plan.utt[idx], plan.start[idx], plan.length[idx], wcap)
+                embs.append(self.predict(xw, lengths=plan.length[idx].tolist(), precision=precision))
+                if half:
+                    ovfs.append(self.half_overflow)
+            # back to plan order with the gather itself: row i of the result is row inv[i] of the concatenation, whole
+            order = np.concatenate([idx for idx, _ in batches])
+            inv = np.empty(N, dtype=np.int64)
+            inv[order] = np.arange(N)
+            zeros = np.zeros(N, dtype=np.int64)
+            emb = ops.window_gather(torch.cat(embs).view(N, 1, D), inv, zeros, np.full(N, D, dtype=np.int64), D).view(N, D)
+            if half:       # the counts travel as their bit patterns: the gather only moves words
+                cnt = torch.cat(ovfs).view(torch.float32).view(N, 1, 1)
+                self.half_overflow = ops.window_gather(cnt, inv, zeros, np.ones(N, dtype=np.int64), 1).view(N).view(torch.int32)
+            if not average:
+                return emb, plan.utt, plan.start, plan.length
+            utts, first = np.unique(plan.utt, return_index=True)        # plan.utt ascends: the windows of an utterance are adjacent
+            return ops.window_mean(emb, np.append(first, N), plan.length.astype(np.float32)), utts
 
     # ---- heads ----------------------------------------------------------------------------------------------
     def _head_fwd(self, emb, y, train, save):

@@ -123,6 +123,8 @@ _SIGS = {
     "spk_affine_lennorm": [_P, _I, _L, _P, _P, _P, _I, _P, _I, _L, _I, _I, _P],
     "spk_plda_posterior_rows": [_P] * 5 + [_I, _I, _P],
     "spk_plda_llr": [_P] * 8 + [_I, _P, _I, _I, _I, _I, _P],
+    "spk_window_gather": [_P, _I, _I, _I, _IP, _IP, _IP, _P, _P, _I, _I, _P],
+    "spk_window_mean": [_P, _I, _I, _IP, _P, _P, _P, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 

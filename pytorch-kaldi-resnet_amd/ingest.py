@@ -237,6 +237,43 @@ def pad_batches(lengths, batch_size, max_pad_ratio=0.1, quantum=8):
     return batches
 
 
+# ---- windowed extraction ----
+WindowPlan = collections.namedtuple("WindowPlan", "utt start length skipped")
+WindowPlan.__doc__ = """plan_windows' result: flat int64 arrays, one entry per window in utterance order and then window order - the
+utterance, the first frame and the frame count of the window - and `skipped`, the utterances shorter than min_window (ascending)"""
+
+
+def plan_windows(lengths, window, period, min_window):
+    """The window rule (numpy only).  An utterance of n frames with n < min_window yields no window and is listed in `skipped`;
+    otherwise window k = 0, 1, ... covers the frames [k period, min(k period + window, n)), the last one being the first k with
+    k period + window >= n (later ones would be subsets of it), emitted only when it has at least min_window frames or is k = 0.
+    period == window is Kaldi's chunking (nnet3-xvector-compute --chunk-size window --min-chunk-size min_window)."""
+    W, P, M = int(window), int(period), int(min_window)
+    if W < 1 or P < 1 or not 1 <= M <= W:
+        raise ValueError("plan_windows: window >= 1, period >= 1 and 1 <= min_window <= window, got window=%d period=%d min_window=%d"
+                         % (W, P, M))
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if n.size and n.min() < 0:
+        raise ValueError("plan_windows: a length is negative")
+    keep = n >= M
+    klast = np.where(keep, np.maximum(0, -(-(n - W) // P)), 0)          # the first k with k P + W >= n
+    emit_last = (klast == 0) | (n - klast * P >= M)
+    count = np.where(keep, klast + emit_last, 0)
+    utt = np.repeat(np.arange(n.size, dtype=np.int64), count)
+    first = np.cumsum(count) - count
+    k = np.arange(int(count.sum()), dtype=np.int64) - np.repeat(first, count)
+    start = k * P
+    length = np.minimum(start + W, n[utt]) - start
+    return WindowPlan(utt, start, length, np.nonzero(~keep)[0].astype(np.int64))
+
+
+def window_batches(length, batch_size, max_pad_ratio=0.1, quantum=8):
+    """The rows of a window plan grouped into padded batches: pad_batches over the window lengths - a list of (plan rows, Wcap) with
+    at most batch_size rows each, Wcap the batch's longest window rounded up to `quantum`, at most max_pad_ratio padded frames.
+    Every plan row lands in exactly one batch; concatenating the batches' rows gives the permutation that restores plan order."""
+    return pad_batches(length, batch_size, max_pad_ratio, quantum)
+
+
 # ---- the draws of an epoch: one seeded index function for NativeTrainLoader (archives) and WavTrainLoader (audio) ----
 def read_utt2spkid(utt2spkid_file):
     utt2spk = {}

@@ -1304,3 +1304,57 @@ def plda_llr(en, te, ia, ib, psi, count, tab_count, tab_log):
     call("spk_plda_llr", ptr(en), ptr(te), ptr(ia), ptr(ib), ptr(psi), ptr(count), ptr(tab_count), ptr(tab_log), U, ptr(out), T, D,
          en.shape[0], te.shape[0], stream())
     return out
+
+
+# ---- windowed extraction (csrc/window.hip) ------------------------------------------------------------------
+def _plan_i32(*cols):
+    """host plan columns -> one contiguous int32 numpy array [len(cols)][N]; anything that is not an integer is refused"""
+    import numpy as np
+    out = []
+    for c in cols:
+        a = np.asarray(c)
+        if a.dtype.kind not in "iu" or a.ndim != 1:
+            raise TypeError("a window plan column must be a one-dimensional integer array")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("a window plan value does not fit 32 bits")
+        out.append(a.astype(np.int32))
+    return np.ascontiguousarray(np.stack(out))
+
+
+def window_gather(src, row, start, length, Wcap, out=None):
+    """src [B][F][T] float32 (device), the plan row / start / length: host integer arrays [N] -> out [N][F][Wcap]: window i is
+    src[row[i], :, start[i]:start[i] + length[i]], zero past its length - bit for bit (spk_window_gather).  The plan is checked on
+    the host before the launch; a bad plan raises and leaves `out` untouched."""
+    B, F, T = src.shape
+    plan = _plan_i32(row, start, length)
+    N = plan.shape[1]
+    assert src.dtype == torch.float32
+    if out is None:
+        out = torch.empty(N, F, int(Wcap), device=src.device, dtype=torch.float32)
+    assert tuple(out.shape) == (N, F, int(Wcap)) and out.dtype == torch.float32
+    if N == 0:
+        return out
+    pd = torch.from_numpy(plan).to(src.device)
+    ip = ctypes.POINTER(ctypes.c_int)
+    call("spk_window_gather", ptr(src), B, F, T, plan[0].ctypes.data_as(ip), plan[1].ctypes.data_as(ip), plan[2].ctypes.data_as(ip),
+         ptr(pd), ptr(out), N, int(Wcap), stream(), nbytes=4.0 * N * F * (float(plan[2].mean()) + int(Wcap)))
+    return out
+
+
+def window_mean(emb, seg_off, weight):
+    """emb [N][D] float32 (device), seg_off: host integer array [U + 1] (0 = seg_off[0] < ... < seg_off[U] = N), weight [N]: host
+    numbers or a float32 device tensor -> float32 [U][D], out[u] = sum_r weight[r] emb[r] / sum_r weight[r] over the rows of
+    segment u in order, in fp32 (spk_window_mean).  An empty segment raises."""
+    N, D = emb.shape
+    so = _plan_i32(seg_off)[0]
+    U = so.size - 1
+    assert emb.dtype == torch.float32
+    if not isinstance(weight, torch.Tensor):
+        import numpy as np
+        weight = torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float32)).to(emb.device)
+    assert weight.dtype == torch.float32 and weight.numel() == N
+    out = torch.empty(max(U, 0), D, device=emb.device, dtype=torch.float32)
+    sd = torch.from_numpy(so).to(emb.device)
+    call("spk_window_mean", ptr(emb), N, D, so.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(sd), ptr(weight), ptr(out), U,
+         stream(), nbytes=4.0 * (N * D + U * D))
+    return out

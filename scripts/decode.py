@@ -61,6 +61,23 @@ parser.add_argument("--half", action="store_true",
                     help="extract with predict(precision='f16'): fp16 activations, one fp16 product per multiply-accumulate.  "
                          "Utterances whose activations leave fp16's range are detected on the GPU and extracted again in fp32 "
                          "(resnet18/34/50/101; not se_resnet34)")
+parser.add_argument("--window", type=int, default=None,
+                    help="windowed extraction (with --native-reader --pad-batches, or with --wav-scp): a window of W frames every "
+                         "--period frames, each embedded alone; the last, shorter window of an utterance is kept when it has at "
+                         "least --min-window frames.  One vector per window under the key <utt>-<start:08d>-<end:08d> (frame "
+                         "indices, end exclusive) and a file segments.<name> next to the embeddings with lines '<key> <utt> "
+                         "<start s> <end s>'.  With --wav-scp the indices count the frames the model sees, that is after the VAD's "
+                         "frame selection")
+parser.add_argument("--period", type=int, default=None, help="with --window: frames between window starts (default: --window)")
+parser.add_argument("--min-window", type=int, default=None,
+                    help="with --window: shortest last window that is kept, and shortest utterance that is extracted at all "
+                         "(default: --window with --average-windows, else 1)")
+parser.add_argument("--average-windows", action="store_true",
+                    help="with --window: one vector per utterance under its own key, the mean of its window embeddings weighted "
+                         "by window length (with --period = --window: nnet3-xvector-compute --chunk-size W --min-chunk-size M); "
+                         "utterances shorter than --min-window are listed on stderr and counted")
+parser.add_argument("--frame-shift", type=float, default=0.01,
+                    help="with --window: seconds per frame, used only for the times in segments.<name> (default 0.01)")
 parser.add_argument("--out-format", default="text", choices=["text", "fv"],
                     help="text = the reference's 'utt [ v0 ... ]' lines (str(np.float32), ~0.2 ms/utt of Python formatting); "
                          "fv = binary Kaldi float-vector ark, read by the same scoring scripts")
@@ -87,6 +104,22 @@ def main():
             parser.error("--mfcc-config: %s" % e)
         if num_ceps != args.input_dim:
             parser.error("--input-dim %d differs from the num-ceps %d of --mfcc-config %s" % (args.input_dim, num_ceps, args.mfcc_config))
+    if args.window is None:
+        if args.period is not None or args.min_window is not None or args.average_windows:
+            parser.error("--period / --min-window / --average-windows need --window")
+    else:
+        if not (args.wav_scp or (args.native_reader and args.pad_batches)):
+            parser.error("--window needs --native-reader --pad-batches or --wav-scp")
+        if args.chunk_size >= 0:
+            parser.error("--window and --chunk-size >= 0 are mutually exclusive (--chunk-size crops, --window covers the utterance)")
+        if args.period is None:
+            args.period = args.window
+        if args.min_window is None:
+            args.min_window = args.window if args.average_windows else 1
+        if args.window < 1 or args.period < 1:
+            parser.error("--window and --period must be >= 1, got --window %d --period %d" % (args.window, args.period))
+        if not 1 <= args.min_window <= args.window:
+            parser.error("--min-window must lie in [1, --window %d], got %d" % (args.window, args.min_window))
     if args.pad_batches and not args.native_reader:
         parser.error("--pad-batches needs --native-reader")
     if args.pad_batches and args.chunk_size >= 0:
@@ -199,6 +232,77 @@ class Predictor:
             print("=> {} of {} utterances left the fp16 range and were extracted in fp32".format(self.redone, self.total))
 
 
+class WindowPredictor:
+    """--window: predict_windows() of one padded batch -> (numpy embeddings, their keys, their segments lines or None).  Without
+    --average-windows a row per window, keyed <utt>-<start:08d>-<end:08d>; with it a row per utterance, the length-weighted mean
+    of its windows (spk_window_mean).  --half: the windows whose activations left fp16's range (engine().half_overflow, one count
+    per window) are gathered and predicted again in fp32, before any averaging.  Utterances shorter than --min-window are named
+    on stderr and counted."""
+
+    def __init__(self, model, args):
+        self.model, self.a = model, args
+        self.redone = self.total = self.skipped = self.utts = 0
+
+    def __call__(self, x, lengths, names):
+        from pytorch_kaldi_resnet_amd import ingest, ops
+        a, m = self.a, self.model
+        x = x.contiguous()
+        lengths = np.asarray(lengths, dtype=np.int64)
+        kw = dict(window=a.window, period=a.period, min_window=a.min_window, batch_size=a.batch_size)
+        if a.average_windows and not a.half:
+            emb, utt = m.predict_windows(x, lengths, average=True, **kw)
+        else:
+            emb, utt, start, length = m.predict_windows(x, lengths, precision="f16" if a.half else "f32", **kw)
+            if a.half and utt.size:
+                idx = np.nonzero(m.engine().half_overflow.cpu().numpy())[0]
+                self.total += utt.size
+                self.redone += idx.size
+                for sub, wcap in (ingest.window_batches(length[idx], a.batch_size) if idx.size else []):
+                    rows = idx[sub]
+                    xw = ops.window_gather(x, utt[rows], start[rows], length[rows], wcap)
+                    emb[torch.from_numpy(rows).to(emb.device)] = m.predict(xw, lengths=length[rows].tolist())
+            if a.average_windows and utt.size:
+                uu, first = np.unique(utt, return_index=True)
+                emb, utt = ops.window_mean(emb, np.append(first, utt.size), length.astype(np.float32)), uu
+        skipped = m.engine().windows_skipped
+        for b in skipped:
+            sys.stderr.write("=> skipping {}: {} frames, shorter than --min-window {}\n".format(names[b], int(lengths[b]), a.min_window))
+        self.skipped += len(skipped)
+        self.utts += len(names)
+        pred = emb.cpu().numpy()
+        if a.average_windows:
+            return pred, [names[b] for b in utt], None
+        keys = ["%s-%08d-%08d" % (names[b], s, s + l) for b, s, l in zip(utt, start, length)]
+        seg = ["%s %s %.3f %.3f\n" % (k, names[b], s * a.frame_shift, (s + l) * a.frame_shift)
+               for k, b, s, l in zip(keys, utt, start, length)]
+        return pred, keys, seg
+
+    def report(self):
+        if self.a.half:
+            print("=> {} of {} windows left the fp16 range and were extracted in fp32".format(self.redone, self.total))
+        print("=> {} of {} utterances shorter than --min-window were skipped".format(self.skipped, self.utts))
+
+
+def _emit(f, seg, keys, pred, seglines, args):
+    """one batch of vectors (text: formatted natively; fv: binary Kaldi vectors) and, with --window, its segments lines"""
+    from pytorch_kaldi_resnet_amd import ingest, kaldi_io
+    if pred.shape[0] == 0:
+        return
+    if args.out_format == "text":
+        f.write(ingest.format_text_vectors(keys, pred, max(1, args.workers)))
+    else:
+        for i in range(pred.shape[0]):
+            kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=keys[i])
+    if seg is not None and seglines:
+        seg.write("".join(seglines))
+
+
+def _segments_file(args, name):
+    if args.window is None or args.average_windows:
+        return None
+    return open(os.path.join(args.out_path, "segments." + name), "w")
+
+
 def sequence_generator(loader, model, out_path, args):
     model.eval()
     name = str(args.gpu) if args.distributed else "alone"
@@ -274,14 +378,8 @@ def native_generator(model, args):
             table.read_crop(b, [0] * len(b), T, buf, max(1, args.workers))
         return buf
 
-    def emit(f, keys, pred):
-        if args.out_format == "text":
-            f.write(ingest.format_text_vectors(keys, pred, max(1, args.workers)))
-        else:
-            for i in range(pred.shape[0]):
-                kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=keys[i])
-
-    predict = Predictor(model, args.half)
+    predict = Predictor(model, args.half) if args.window is None else WindowPredictor(model, args)
+    seg = _segments_file(args, name)
     with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
             ThreadPoolExecutor(1) as wr:
         nxt = rd.submit(load, 0) if mine else None
@@ -295,13 +393,19 @@ def native_generator(model, args):
                 x = features.decompress(buf[0].cuda(args.gpu, non_blocking=True), buf[1].cuda(args.gpu, non_blocking=True), lengths)
             else:
                 x = buf.cuda(args.gpu, non_blocking=True)
-            pred = predict(x, lengths)
+            keys, seglines = [utts[k] for k in b], None
+            if args.window is None:
+                pred = predict(x, lengths)
+            else:
+                pred, keys, seglines = predict(x, lengths, keys)
             if pending is not None:
                 pending.result()
-            pending = wr.submit(emit, f, [utts[k] for k in b], pred)
+            pending = wr.submit(_emit, f, seg, keys, pred, seglines, args)
             done += len(b)
         if pending is not None:
             pending.result()
+        if seg is not None:
+            seg.close()
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + predict + write)".format(done, dt, done / max(dt, 1e-9)))
     predict.report()
@@ -334,14 +438,8 @@ def wav_generator(model, args):
         table.read_padded(b, nmax, buf, max(1, args.workers))
         return buf
 
-    def emit(f, ks, pred):
-        if args.out_format == "text":
-            f.write(ingest.format_text_vectors(ks, pred, max(1, args.workers)))
-        else:
-            for i in range(pred.shape[0]):
-                kaldi_io.write_vec_flt(f, np.ascontiguousarray(pred[i]), key=ks[i])
-
-    predict = Predictor(model, args.half)
+    predict = Predictor(model, args.half) if args.window is None else WindowPredictor(model, args)
+    seg = _segments_file(args, name)
     with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
             ThreadPoolExecutor(1) as wr:
         nxt = rd.submit(load, 0) if mine else None
@@ -360,13 +458,19 @@ def wav_generator(model, args):
                 continue
             if keep.size < len(b):
                 feats = feats[torch.from_numpy(keep).to(feats.device)].contiguous()
-            pred = predict(feats, lengths[keep])
+            ks, seglines = [keys[b[r]] for r in keep], None
+            if args.window is None:
+                pred = predict(feats, lengths[keep])
+            else:          # the windows count the frames the model sees: after the VAD's frame selection
+                pred, ks, seglines = predict(feats, lengths[keep], ks)
             if pending is not None:
                 pending.result()
-            pending = wr.submit(emit, f, [keys[b[r]] for r in keep], pred)
+            pending = wr.submit(_emit, f, seg, ks, pred, seglines, args)
             done += keep.size
         if pending is not None:
             pending.result()
+        if seg is not None:
+            seg.close()
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + front end + predict + write)".format(
             done, dt, done / max(dt, 1e-9)))
