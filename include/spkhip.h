@@ -650,6 +650,44 @@ int spk_window_gather(const float* src, int B, int F, int T, const int* row /*ho
 int spk_window_mean(const float* emb /*[N][D]*/, int N, int D, const int* seg_off /*host [U+1]*/, const int* seg_off_dev,
                     const float* weight /*[N]*/, float* out /*[U][D]*/, int U, void* stream);
 
+/* ---- diarization back end (csrc/diar.hip) -----------------------------------------------------------------
+ * A batch of R recordings: recording r owns the rows rec_off[r] .. rec_off[r + 1] - 1 (n_r of them) of every [Ntot] table, an
+ * n_r x n_r matrix at element offset mat_off[r] = sum over r' < r of n_r'^2, and T_r (T_r + 1) / 2 tiles (T_r = ceil(n_r / 16)) from
+ * tile_off[r] on.  rec_off is a HOST int64 array [R + 1], checked before anything is launched: it must start at 0, be strictly
+ * increasing (no empty recording) and end at Ntot, and the sum of n_r^2 must stay below 2^31; otherwise the call returns < 0 and
+ * writes nothing.  The kernels read the tables from tab_dev: the device copy of what spk_diar_tables wrote. */
+/* host only: tab [3][R + 1] = rec_off, mat_off, tile_off (the last entries: Ntot, sum n^2, all tiles) */
+int spk_diar_tables(const long long* rec_off /*host [R+1]*/, int R, long long Ntot, long long* tab /*host [3][R+1]*/);
+/* q[i] = scale * sum_d k[d] U[i][d]^2 in fp64, one wave per row: lane l adds d = l, l + 64, ... in order and the 64 partial sums
+ * meet in a butterfly.  The PLDA setting of spk_score_dense: k_d = psi_d^2 / ((psi_d + 1)(2 psi_d + 1)), scale = -0.5. */
+int spk_score_dense_q(const double* U /*[N][D]*/, const double* k /*[D]*/, double scale, double* q /*[N]*/, long long N, int D,
+                      void* stream);
+/* out[mat_off[r] + i n_r + j] = (float)(q[a] + q[b] + K + sum_d g[d] U[a][d] U[b][d]), a = rec_off[r] + i, b = rec_off[r] + j, for
+ * every pair of rows of every recording: fp64 on v_mfma_f64_16x16x4_f64, one rounding to float.  16 x 16 tiles of the upper triangle,
+ * every value stored at (i, j) and (j, i): out is symmetric bit for bit, and nothing outside the R matrices is written.
+ * 1 <= D <= 512 (padded with zeros in registers), any n_r >= 1.  PLDA with both sides counted once (U: the projected,
+ * length-normalised rows Plda::TransformIvector gives): g_d = psi_d / (2 psi_d + 1), q as above,
+ * K = 0.5 sum_d (log(psi_d + 1) - log(1 + psi_d / (psi_d + 1))): Plda::LogLikelihoodRatio(u_i, 1, u_j) as spk_plda_llr states it.
+ * Cosine: q = 0, K = 0, g = 1, U the unit rows. */
+int spk_score_dense(const double* U /*[Ntot][D]*/, const long long* rec_off /*host [R+1]*/, const long long* tab_dev /*[3][R+1]*/,
+                    const double* q /*[Ntot]*/, const double* g /*[D]*/, double K, float* out, long long Ntot, int D, int R,
+                    void* stream);
+/* threads of the workgroup that clusters one recording, and the largest n_r spk_ahc_batch takes (8192) */
+int spk_ahc_threads(void);
+int spk_ahc_max_n(void);
+/* Average-linkage agglomerative clustering of every recording of the batch, one workgroup each (no workgroup waits on another).
+ * S: the float matrices as spk_score_dense lays them out; only the upper triangles are read.  cost(i, j) = -(double)S[i][j]; C holds
+ * summed pairwise costs, m the cluster sizes.  While more than max(min(min_clusters[r], n_r), 1) clusters are active: over the active
+ * pairs i < j take the smallest c = C[i][j] / ((double)m_i (double)m_j), compared with c < best from best = +inf (a NaN or +inf never
+ * wins), ties to the smallest i, then the smallest j; stop if there is none, or if c <= -threshold[r] does not hold
+ * (threshold[r] = -inf: no threshold); else record (i, j, c), C[i][k] += C[j][k] for every other active k, m_i += m_j, j leaves.
+ * labels[rec_off[r] + w]: 1, 2, ... numbering the final clusters by their lowest member.  merges [Ntot][2] and merge_cost [Ntot]:
+ * recording r uses the slots from rec_off[r], n_merges[r] of them.  ws: ws_elems >= sum n_r^2 doubles (the kernel builds its table
+ * there).  Refused on the host (< 0, nothing written): a bad rec_off, n_r > spk_ahc_max_n(), a workspace that is too small. */
+int spk_ahc_batch(const float* S, const long long* rec_off /*host [R+1]*/, const long long* tab_dev /*[3][R+1]*/,
+                  const int* min_clusters /*[R]*/, const double* threshold /*[R]*/, double* ws, long long ws_elems, int* labels /*[Ntot]*/,
+                  int* merges /*[Ntot][2]*/, double* merge_cost /*[Ntot]*/, int* n_merges /*[R]*/, long long Ntot, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,339 @@
+"""Diarization back end: the consumer of the sliding-window embeddings decode.py --window writes.  Per
+recording an all-pairs score matrix (Kaldi's ivector-plda-scoring-dense without its per-recording PCA, or cosine), average-linkage
+agglomerative clustering with a threshold or a known speaker count (agglomerative-cluster) and RTTM output (make_rttm.py).  No Kaldi
+binary is involved: the contract is the rule as section 6n states it, pinned by the independent restatement in tests/diar_ref.py.
+
+Two back ends.  `host` is numpy in fp64.  `hip` keeps the embeddings, the scores and the clustering on the GPU (csrc/diar.hip through
+ops.py, the projections through csrc/plda.hip).  A batch of recordings is one [Ntot][D] table with rec_off [R + 1]: recording r owns
+the rows rec_off[r] .. rec_off[r + 1] - 1, and its n x n score matrix lies at mat_off[r] = sum of the earlier n^2 in one flat array."""
+import numpy as np
+
+from . import plda as _plda
+
+
+def _rec_off(rec_off, Ntot):
+    ro = np.asarray(rec_off)
+    if ro.dtype.kind not in "iu" or ro.ndim != 1 or ro.size < 2:
+        raise ValueError("rec_off must be a one-dimensional integer array of at least two entries")
+    ro = ro.astype(np.int64)
+    if ro[0] != 0 or ro[-1] != Ntot or (np.diff(ro) < 1).any():
+        raise ValueError("rec_off must start at 0, increase strictly (no empty recording) and end at %d" % Ntot)
+    n = np.diff(ro)
+    mat_off = np.concatenate([[0], np.cumsum(n * n)]).astype(np.int64)
+    if mat_off[-1] >= 1 << 31:
+        raise ValueError("the score matrices of one batch must hold fewer than 2^31 entries, got %d" % mat_off[-1])
+    return ro, mat_off
+
+
+def plda_dense_terms(psi):
+    """(g [D], k [D], K) of the dense form of Plda::LogLikelihoodRatio(u_i, 1, u_j):
+    llr = q_i + q_j + K + sum_d g_d u_id u_jd with q_i = -0.5 sum_d k_d u_id^2"""
+    psi = np.asarray(psi, dtype=np.float64)
+    g = psi / (2.0 * psi + 1.0)
+    k = psi * psi / ((psi + 1.0) * (2.0 * psi + 1.0))
+    K = 0.5 * float((np.log(psi + 1.0) - np.log(1.0 + psi / (psi + 1.0))).sum())
+    return g, k, K
+
+
+def _center(emb, mean):
+    """x0 = fl32(x - m) as plda._center takes it: values and mean as float32; mean None: the fp64 mean of the rows themselves"""
+    x = np.asarray(emb).astype(np.float32).astype(np.float64)
+    m = x.mean(axis=0) if mean is None else np.asarray(mean).astype(np.float32).astype(np.float64)
+    if x.ndim != 2 or x.shape[1] != m.shape[0]:
+        raise ValueError("the mean has %d dimensions, the embeddings %s" % (m.shape[0], x.shape[1:]))
+    return (x - m).astype(np.float32)
+
+
+def dense_inputs(emb, kind, mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True,
+                 simple_length_normalization=False, backend="host"):
+    """-> (U [Ntot][D'] fp64, q [Ntot] fp64, g [D'] fp64, K): the operands of the dense score, numpy on `host`, device tensors on
+    `hip`.  cosine: rows of norm sqrt(D) (ivector-normalize-length's scaling, spk_affine_lennorm) with g = 1 / D - the cosine of the
+    centred embeddings; q = 0 and K = 0.  plda: the rows Plda::TransformIvector gives for one utterance per side."""
+    x0 = _center(emb, mean)
+    N = x0.shape[0]
+    if kind == "cosine":
+        z = x0 if transform is None else _plda.project(x0, transform, backend)
+        D = z.shape[1]
+        if backend == "hip":
+            import torch
+            from . import ops
+            U = ops.affine_lennorm(z if torch.is_tensor(z) else _plda._up(z), None, None, None, True, torch.float64)
+            return U, torch.zeros(N, device=U.device, dtype=torch.float64), _plda._up(np.full(D, 1.0 / D)), 0.0
+        assert backend == "host", backend
+        y = z.astype(np.float64)
+        ss = (y * y).sum(axis=1)
+        U = y * np.where(ss > 0, np.sqrt(D / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
+        return U, np.zeros(N), np.full(D, 1.0 / D), 0.0
+    if kind != "plda":
+        raise ValueError("kind must be cosine or plda, got %r" % (kind,))
+    if plda is None or transform is None:
+        raise ValueError("plda scoring needs the transform and the Plda object")
+    model = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))
+    g, k, K = plda_dense_terms(model[2])
+    counts = np.ones(N, dtype=np.int64)
+    z = _plda.project(x0, transform, backend)
+    if backend == "hip":
+        from . import ops
+        U = _plda._side_hip(z, model, counts, normalize_length, simple_length_normalization)
+        return U, ops.score_dense_q(U, _plda._up(k), -0.5), _plda._up(g), K
+    assert backend == "host", backend
+    U = _plda._side_host(z, model, counts, normalize_length, simple_length_normalization)
+    return U, -0.5 * (k[None, :] * U * U).sum(axis=1), g, K
+
+
+def score_dense(emb, rec_off, kind="cosine", mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True,
+                simple_length_normalization=False, backend="host", return_device=False):
+    """emb [Ntot][D] (the rows of all recordings, recording after recording), rec_off [R + 1] -> (scores float32 [sum n^2], mat_off
+    int64 [R + 1]): recording r's matrix S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) at scores[mat_off[r]:], symmetric
+    bit for bit.  `hip` with return_device: the scores stay on the GPU (what cluster(..., backend="hip") takes)."""
+    emb = np.asarray(emb)
+    ro, mat_off = _rec_off(rec_off, emb.shape[0])
+    U, q, g, K = dense_inputs(emb, kind, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
+    if backend == "hip":
+        from . import ops
+        out, mo = ops.score_dense(U, ro, q, g, K)
+        assert (mo == mat_off).all()
+        return (out if return_device else out.cpu().numpy()), mat_off
+    out = np.empty(int(mat_off[-1]), dtype=np.float32)
+    for r in range(ro.size - 1):
+        u, qq = U[ro[r]:ro[r + 1]], q[ro[r]:ro[r + 1]]
+        s = np.triu(((u * g[None, :]) @ u.T + qq[:, None]) + qq[None, :] + K)
+        s = s + np.triu(s, 1).T                                     # the upper triangle, mirrored
+        out[mat_off[r]:mat_off[r + 1]] = s.astype(np.float32).ravel()
+    return out, mat_off
+
+
+# ---- clustering -------------------------------------------------------------------------------------------------------------------
+def _ahc_host(S, min_clusters, threshold):
+    """One recording by the rule of section 6n, with the cached row minima the kernel keeps (csrc/diar.hip): the minimum of row a over
+    the active b > a, refreshed only where a merge can have changed it.  -> (labels, merges, costs)"""
+    n = S.shape[0]
+    C = np.triu(-S.astype(np.float64), 1)
+    C = C + C.T
+    m = np.ones(n)
+    active = np.ones(n, dtype=bool)
+    root = np.arange(n)
+    val = np.full(n, np.inf)
+    col = np.full(n, -1, dtype=np.int64)
+
+    def scan(a):
+        b = np.arange(a + 1, n)
+        b = b[active[b]]
+        val[a], col[a] = np.inf, -1
+        if b.size:
+            c = C[a, b] / (m[a] * m[b])
+            c = np.where(c == c, c, np.inf)                        # a NaN never wins
+            k = int(np.argmin(c))                                  # the first of equal costs
+            if c[k] < np.inf:
+                val[a], col[a] = c[k], b[k]
+
+    for a in range(n - 1):
+        scan(a)
+    target = max(min(int(min_clusters), n), 1)
+    merges, costs = [], []
+    nactive = n
+    with np.errstate(all="ignore"):
+        while nactive > target:
+            cand = np.where(active & (col >= 0), val, np.inf)
+            i = int(np.argmin(cand))
+            if not cand[i] < np.inf:
+                break
+            c, j = cand[i], int(col[i])
+            if not c <= -threshold:
+                break
+            merges.append((i, j))
+            costs.append(c)
+            k = active.copy()
+            k[[i, j]] = False
+            C[i, k] = C[i, k] + C[j, k]
+            C[k, i] = C[i, k]
+            m[i] += m[j]
+            active[j] = False
+            root[root == j] = i
+            for a in np.nonzero(active[:j])[0]:
+                if a == i or col[a] == i or col[a] == j:
+                    scan(a)
+                elif a < i:
+                    ci = C[a, i] / (m[a] * m[i])
+                    if ci < val[a] or (ci == val[a] and i < col[a]) or (col[a] < 0 and ci < np.inf):
+                        val[a], col[a] = ci, i
+            nactive -= 1
+    rank = np.cumsum(active)
+    return rank[root].astype(np.int32), merges, costs
+
+
+def _per_recording(v, R, dtype, default, name):
+    if v is None:
+        return np.full(R, default, dtype=dtype)
+    a = np.asarray(v, dtype=dtype)
+    if a.ndim == 0:
+        return np.full(R, a, dtype=dtype)
+    if a.shape != (R,):
+        raise ValueError("%s must be one value or one per recording (%d), got %s" % (name, R, a.shape))
+    return a
+
+
+def cluster(scores, rec_off, threshold=None, num_speakers=None, backend="host", ws_budget_bytes=1 << 31):
+    """scores: the flat float32 matrices of score_dense (numpy, or on `hip` a device tensor), rec_off [R + 1].  threshold: stop when
+    the next merge's cost c does not satisfy c <= -threshold, i.e. when the average score of the best pair falls below it (one value
+    or one per recording; None or -inf: none).  num_speakers: clusters to stop at (one value or one per recording; values above n
+    clamp to n; None: 1).  -> (labels int32 [Ntot] from 1, numbered by lowest member window; merges int32 [Ntot][2] and merge_cost
+    float64 [Ntot], recording r in the slots from rec_off[r]; n_merges int32 [R]) as numpy arrays.  The merge list of a correct
+    implementation is unique: both back ends give the same bits."""
+    ro = np.asarray(rec_off)
+    ro, mat_off = _rec_off(ro, int(ro[-1]) if ro.ndim == 1 and ro.size else 0)
+    R, Ntot = ro.size - 1, int(ro[-1])
+    minc = _per_recording(num_speakers, R, np.int64, 1, "num_speakers")
+    if (minc < 1).any():
+        raise ValueError("num_speakers must be at least 1")
+    thr = _per_recording(threshold, R, np.float64, -np.inf, "threshold")
+    if np.isnan(thr).any():
+        raise ValueError("a threshold is NaN")
+    minc = np.minimum(minc, np.diff(ro))                            # (fits int32)
+    if backend == "hip":
+        import torch
+        from . import ops
+        sd = scores if torch.is_tensor(scores) else torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).cuda()
+        lab, mer, cost, nm = ops.ahc_batch(sd, ro, minc.astype(np.int32), thr, ws_budget_bytes)
+        return lab.cpu().numpy(), mer.cpu().numpy(), cost.cpu().numpy(), nm.cpu().numpy()
+    assert backend == "host", backend
+    s = np.asarray(scores.cpu().numpy() if hasattr(scores, "cpu") else scores, dtype=np.float32)
+    if s.size < mat_off[-1]:
+        raise ValueError("the scores hold %d values, rec_off asks for %d" % (s.size, mat_off[-1]))
+    labels = np.empty(Ntot, dtype=np.int32)
+    merges = np.zeros((Ntot, 2), dtype=np.int32)
+    cost = np.zeros(Ntot, dtype=np.float64)
+    nm = np.empty(R, dtype=np.int32)
+    for r in range(R):
+        n = int(ro[r + 1] - ro[r])
+        lab, mer, cs = _ahc_host(s[mat_off[r]:mat_off[r + 1]].reshape(n, n), minc[r], thr[r])
+        labels[ro[r]:ro[r + 1]] = lab
+        nm[r] = len(mer)
+        if mer:
+            merges[ro[r]:ro[r] + len(mer)] = mer
+            cost[ro[r]:ro[r] + len(mer)] = cs
+    return labels, merges, cost, nm
+
+
+# ---- RTTM -------------------------------------------------------------------------------------------------------------------------
+def read_segments(path):
+    """'<key> <recording> <start s> <end s>' lines (decode.py --window's segments.<name>) -> [(key, recording, start, end)]"""
+    out = []
+    for ln, line in enumerate(open(path), 1):
+        f = line.split()
+        if not f:
+            continue
+        if len(f) != 4:
+            raise ValueError("%s:%d: expected '<key> <recording> <start> <end>', got %r" % (path, ln, line.strip()))
+        out.append((f[0], f[1], float(f[2]), float(f[3])))
+    return out
+
+
+def make_rttm(segments, labels, channel=0):
+    """segments: (key, recording, start, end) per window; labels: key -> label, or one label per window in the same order.  Per
+    recording (in order of first appearance) the windows sorted by (start, end); every adjacent pair with different labels that
+    overlaps is cut at the midpoint of the overlap; consecutive windows of one label that touch or overlap are merged; empty pieces
+    are dropped.  Only adjacent pairs are cut: with a period below half the window deeper overlaps stay.  -> the RTTM lines."""
+    if not isinstance(labels, dict):
+        labels = list(labels)
+        if len(labels) != len(segments):
+            raise ValueError("%d labels for %d windows" % (len(labels), len(segments)))
+        labels = {s[0]: l for s, l in zip(segments, labels)}
+    recs = {}
+    for key, reco, start, end in segments:
+        recs.setdefault(reco, []).append([float(start), float(end), int(labels[key])])
+    lines = []
+    for reco, w in recs.items():
+        w.sort(key=lambda p: (p[0], p[1]))
+        for cur, nxt in zip(w[:-1], w[1:]):
+            if cur[2] != nxt[2] and nxt[0] < cur[1]:
+                mid = 0.5 * (nxt[0] + cur[1])
+                cur[1] = nxt[0] = mid
+        pieces = []
+        for p in w:
+            if pieces and pieces[-1][2] == p[2] and p[0] <= pieces[-1][1]:
+                pieces[-1][1] = max(pieces[-1][1], p[1])
+            else:
+                pieces.append(list(p))
+        for start, end, lab in pieces:
+            if end > start:
+                lines.append("SPEAKER %s %s %.3f %.3f <NA> <NA> %d <NA> <NA>" % (reco, channel, start, end - start, lab))
+    return lines
+
+
+# ---- one call -----------------------------------------------------------------------------------------------------------------------
+def group_windows(emb_keys, segments, recordings=None):
+    """The batch layout of a segments list against the embedding keys: (recordings in order of first appearance, the windows of
+    each in file order as indices into `segments`, rec_off).  Raises ValueError naming what is wrong: a key of one file that the other
+    lacks, a key listed twice, a recording (of `recordings`, when given) with no window."""
+    seg_keys = [s[0] for s in segments]
+    have, want = set(emb_keys), set(seg_keys)
+    if len(want) != len(seg_keys):
+        seen, dup = set(), []
+        for k in seg_keys:
+            if k in seen:
+                dup.append(k)
+            seen.add(k)
+        raise ValueError("segments lists a window twice: " + " ".join(dup[:5]))
+    if want - have:
+        raise ValueError("windows of the segments file without an embedding: " + " ".join(sorted(want - have)[:5]))
+    if have - want:
+        raise ValueError("embeddings without a line in the segments file: " + " ".join(sorted(have - want)[:5]))
+    order, rows = [], {}
+    for i, s in enumerate(segments):
+        if s[1] not in rows:
+            order.append(s[1])
+            rows[s[1]] = []
+        rows[s[1]].append(i)
+    if recordings is not None:
+        empty = [r for r in recordings if r not in rows]
+        if empty:
+            raise ValueError("recordings with no window: " + " ".join(empty[:5]))
+    if not order:
+        raise ValueError("recordings with no window: the segments file is empty")
+    rec_off = np.concatenate([[0], np.cumsum([len(rows[r]) for r in order])]).astype(np.int64)
+    return order, [rows[r] for r in order], rec_off
+
+
+def read_reco2num_spk(path):
+    out = {}
+    for line in open(path):
+        f = line.split()
+        if not f:
+            continue
+        if len(f) != 2 or int(f[1]) < 1:
+            raise ValueError("%s: expected '<recording> <speakers >= 1>', got %r" % (path, line.strip()))
+        out[f[0]] = int(f[1])
+    return out
+
+
+def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=None, recordings=None, backend="host", channel=0,
+            return_scores=False, **score_args):
+    """embeddings: key -> vector (scoring.read_embeddings), segments: read_segments' list; exactly one of threshold and
+    reco2num_spk (recording -> speakers).  -> dict(recordings, rec_off, mat_off, keys (batch order), labels, scores (numpy with
+    return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges)"""
+    if (threshold is None) == (reco2num_spk is None):
+        raise ValueError("give exactly one of threshold and reco2num_spk")
+    emb_keys = embeddings.keys_list if hasattr(embeddings, "keys_list") else list(embeddings)
+    order, rows, rec_off = group_windows(emb_keys, segments, recordings)
+    num = None
+    if reco2num_spk is not None:
+        absent = [r for r in reco2num_spk if r not in set(order)]
+        if absent:
+            raise ValueError("recordings of reco2num-spk that are absent from the segments file: " + " ".join(absent[:5]))
+        missing = [r for r in order if r not in reco2num_spk]
+        if missing:
+            raise ValueError("recordings without a speaker count in reco2num-spk: " + " ".join(missing[:5]))
+        num = np.array([reco2num_spk[r] for r in order], dtype=np.int64)
+    flat = [i for rr in rows for i in rr]
+    keys = [segments[i][0] for i in flat]
+    if hasattr(embeddings, "mat") and hasattr(embeddings, "index"):
+        emb = embeddings.mat[[embeddings.index[k] for k in keys]]
+    else:
+        emb = np.stack([np.asarray(embeddings[k], dtype=np.float64) for k in keys])
+    scores, mat_off = score_dense(emb, rec_off, kind, backend=backend, return_device=(backend == "hip"), **score_args)
+    labels, merges, cost, nm = cluster(scores, rec_off, threshold, num, backend)
+    segs = [segments[i] for i in flat]
+    return {"recordings": order, "rec_off": rec_off, "mat_off": mat_off, "keys": keys, "labels": labels,
+            "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),
+            "merges": merges, "merge_cost": cost, "n_merges": nm}

@@ -125,6 +125,12 @@ _SIGS = {
     "spk_plda_llr": [_P] * 8 + [_I, _P, _I, _I, _I, _I, _P],
     "spk_window_gather": [_P, _I, _I, _I, _IP, _IP, _IP, _P, _P, _I, _I, _P],
     "spk_window_mean": [_P, _I, _I, _IP, _P, _P, _P, _I, _P],
+    "spk_diar_tables": [_P, _I, _L, _P],                # host only: rec_off (host int64) -> rec_off / mat_off / tile_off
+    "spk_score_dense_q": [_P, _P, _D, _P, _L, _I, _P],
+    "spk_score_dense": [_P, _P, _P, _P, _P, _D, _P, _L, _I, _I, _P],
+    "spk_ahc_threads": [],
+    "spk_ahc_max_n": [],
+    "spk_ahc_batch": [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 

@@ -1358,3 +1358,95 @@ def window_mean(emb, seg_off, weight):
     call("spk_window_mean", ptr(emb), N, D, so.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(sd), ptr(weight), ptr(out), U,
          stream(), nbytes=4.0 * (N * D + U * D))
     return out
+
+
+# ---- diarization back end (csrc/diar.hip) ---------------------------------------------------------------------
+def diar_tables(rec_off, Ntot):
+    """host rec_off [R + 1] -> (rec_off as contiguous int64, tab int64 [3][R + 1] = rec_off, mat_off, tile_off), both on the host.
+    A rec_off that does not start at 0, is not strictly increasing or does not end at Ntot raises (spk_diar_tables)."""
+    import numpy as np
+    ro = np.asarray(rec_off)
+    if ro.dtype.kind not in "iu" or ro.ndim != 1 or ro.size < 2:
+        raise TypeError("rec_off must be a one-dimensional integer array of at least two entries")
+    ro = np.ascontiguousarray(ro, dtype=np.int64)
+    tab = np.zeros((3, ro.size), dtype=np.int64)
+    hip.call("spk_diar_tables", ro.ctypes.data, ro.size - 1, int(Ntot), tab.ctypes.data)
+    return ro, tab
+
+
+def score_dense_q(U, k, scale):
+    """U [N][D], k [D] float64 -> q [N] float64, q_i = scale sum_d k_d U_id^2 (spk_score_dense_q)"""
+    N, D = U.shape
+    assert U.dtype == torch.float64 and k.dtype == torch.float64 and k.numel() == D
+    q = torch.empty(N, device=U.device, dtype=torch.float64)
+    call("spk_score_dense_q", ptr(U), ptr(k), float(scale), ptr(q), N, D, stream(), nbytes=8.0 * N * D)
+    return q
+
+
+def score_dense(U, rec_off, q, g, K, out=None):
+    """U [Ntot][D], q [Ntot], g [D] float64 (device), rec_off: host integers [R + 1] -> (out float32 [sum n^2], mat_off int64 [R + 1]
+    on the host): recording r's n x n matrix S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) at out[mat_off[r]:], symmetric
+    bit for bit (spk_score_dense).  `out`: a float32 device tensor of at least mat_off[R] elements to write into; a bad rec_off
+    raises and leaves it untouched."""
+    Ntot, D = U.shape
+    ro, tab = diar_tables(rec_off, Ntot)
+    R = ro.size - 1
+    assert U.dtype == torch.float64 and q.dtype == torch.float64 and g.dtype == torch.float64
+    assert q.numel() == Ntot and g.numel() == D
+    total = int(tab[1, R])
+    if out is None:
+        out = torch.empty(total, device=U.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() >= total
+    td = torch.from_numpy(tab).to(U.device)
+    call("spk_score_dense", ptr(U), ro.ctypes.data, ptr(td), ptr(q), ptr(g), float(K), ptr(out), Ntot, D, R, stream(),
+         flops=1.0 * total * D, nbytes=4.0 * total + 8.0 * Ntot * D)
+    return out, tab[1].copy()
+
+
+def ahc_threads():
+    """threads of the workgroup that clusters one recording"""
+    return hip.lib().spk_ahc_threads()
+
+
+def ahc_max_n():
+    """the largest recording (windows) spk_ahc_batch takes"""
+    return hip.lib().spk_ahc_max_n()
+
+
+def ahc_batch(scores, rec_off, min_clusters, threshold, ws_budget_bytes=1 << 31):
+    """scores: float32 device tensor, the matrices of score_dense laid end to end; rec_off: host integers [R + 1]; min_clusters [R]
+    integers; threshold [R] floats, -inf = none -> (labels int32 [Ntot], merges int32 [Ntot][2], merge_cost float64 [Ntot],
+    n_merges int32 [R]) on the device (spk_ahc_batch; the rule: include/spkhip.h).  The batch is split into launches of consecutive
+    recordings whose fp64 tables fit ws_budget_bytes (one recording always goes)."""
+    import numpy as np
+    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
+    Ntot = int(ro[-1])
+    ro, tab = diar_tables(ro, Ntot)
+    R = ro.size - 1
+    n = np.diff(ro)
+    if int(n.max()) > ahc_max_n():
+        raise ValueError("ahc_batch: a recording has %d windows, the cap is %d" % (int(n.max()), ahc_max_n()))
+    assert scores.dtype == torch.float32 and scores.numel() >= int(tab[1, R])
+    dev = scores.device
+    mc = torch.from_numpy(np.ascontiguousarray(min_clusters, dtype=np.int32)).to(dev)
+    th = torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float64)).to(dev)
+    assert mc.numel() == R and th.numel() == R
+    labels = torch.empty(Ntot, device=dev, dtype=torch.int32)
+    merges = torch.zeros(Ntot, 2, device=dev, dtype=torch.int32)
+    cost = torch.zeros(Ntot, device=dev, dtype=torch.float64)
+    nm = torch.empty(R, device=dev, dtype=torch.int32)
+    lo = 0
+    while lo < R:
+        hi = lo + 1
+        while hi < R and 8 * int(tab[1, hi + 1] - tab[1, lo]) <= ws_budget_bytes:
+            hi += 1
+        sub, stab = diar_tables(ro[lo:hi + 1] - ro[lo], int(ro[hi] - ro[lo]))
+        need = int(stab[1, hi - lo])
+        ws = torch.empty(need, device=dev, dtype=torch.float64)
+        td = torch.from_numpy(stab).to(dev)
+        r0, r1, m0 = int(ro[lo]), int(ro[hi]), int(tab[1, lo])
+        call("spk_ahc_batch", scores[m0:].data_ptr(), sub.ctypes.data, ptr(td), mc[lo:hi].data_ptr(), th[lo:hi].data_ptr(), ptr(ws),
+             need, labels[r0:r1].data_ptr(), merges[r0:r1].data_ptr(), cost[r0:r1].data_ptr(), nm[lo:hi].data_ptr(), r1 - r0,
+             hi - lo, stream(), nbytes=12.0 * need)
+        lo = hi
+    return labels, merges, cost, nm

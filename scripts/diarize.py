@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Diarization from sliding-window embeddings: what Kaldi's callhome_diarization recipe runs behind extract_xvectors.sh -
+ivector-plda-scoring-dense (or cosine), agglomerative-cluster and make_rttm.py - on what `decode.py --window W --period P` wrote
+(DESIGN.md section 6n).  Writes <out-dir>/labels ('<window-key> <label>' lines), <out-dir>/rttm and, with --write-scores, one text
+matrix per recording in <out-dir>/scores.<recording>."""
+import argparse
+import os
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _bool(v):
+    if v.lower() in ("true", "1", "yes"):
+        return True
+    if v.lower() in ("false", "0", "no"):
+        return False
+    raise argparse.ArgumentTypeError("true or false, got %r" % v)
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--embeddings", required=True, help="the vectors decode.py --window wrote (text or binary), one per window")
+    ap.add_argument("--segments", required=True, help="segments.<name> of the same run: '<key> <recording> <start s> <end s>'")
+    ap.add_argument("--backend-score", choices=["cosine", "plda"], default="cosine")
+    ap.add_argument("--mean", default=None, help="global mean to subtract (default: the mean of --embeddings)")
+    ap.add_argument("--transform", default=None, help="LDA transform (required with plda, optional with cosine)")
+    ap.add_argument("--plda", default=None)
+    ap.add_argument("--smoothing", type=float, default=0.0)
+    ap.add_argument("--normalize-length", type=_bool, default=True)
+    ap.add_argument("--simple-length-normalization", type=_bool, default=False)
+    ap.add_argument("--threshold", type=float, default=None,
+                    help="stop merging when the average score of the best pair of clusters falls below this")
+    ap.add_argument("--reco2num-spk", default=None, help="'<recording> <speakers>' lines: cluster every recording down to its count")
+    ap.add_argument("--recordings", default=None, help="optional list of the recordings expected: one with no window is an error")
+    ap.add_argument("--backend", choices=["host", "hip"], default="host", help="hip: scores and clustering on the GPU")
+    ap.add_argument("--out-dir", required=True)
+    ap.add_argument("--rttm-channel", type=int, default=0)
+    ap.add_argument("--write-scores", action="store_true")
+    a = ap.parse_args(argv)
+    if (a.threshold is None) == (a.reco2num_spk is None):
+        ap.error("give exactly one of --threshold and --reco2num-spk")
+    if a.backend_score == "plda" and (a.plda is None or a.transform is None):
+        ap.error("--backend-score plda needs --plda and --transform")
+    if a.backend_score == "cosine" and a.plda is not None:
+        ap.error("--plda is only used with --backend-score plda")
+    return ap, a
+
+
+if __name__ == "__main__":
+    ap, a = parse()
+    import numpy as np
+    import pytorch_kaldi_resnet_amd  # noqa: F401
+    from pytorch_kaldi_resnet_amd import diarize, kaldi_io, plda, scoring
+    try:
+        segments = diarize.read_segments(a.segments)
+        emb = scoring.read_embeddings(a.embeddings)
+        extra = {}
+        if a.backend_score == "plda":
+            extra = dict(plda=plda.read_plda(a.plda), smoothing=a.smoothing, normalize_length=a.normalize_length,
+                         simple_length_normalization=a.simple_length_normalization)
+        res = diarize.diarize(emb, segments, a.backend_score, threshold=a.threshold,
+                              reco2num_spk=diarize.read_reco2num_spk(a.reco2num_spk) if a.reco2num_spk else None,
+                              recordings=[l.split()[0] for l in open(a.recordings) if l.strip()] if a.recordings else None,
+                              backend=a.backend, channel=a.rttm_channel, return_scores=a.write_scores,
+                              mean=kaldi_io.read_vec_flt(a.mean) if a.mean else None,
+                              transform=plda.read_transform(a.transform) if a.transform else None, **extra)
+    except ValueError as e:
+        ap.error(str(e))
+    os.makedirs(a.out_dir, exist_ok=True)
+    with open(os.path.join(a.out_dir, "labels"), "w") as f:
+        for k, l in zip(res["keys"], res["labels"]):
+            f.write("%s %d\n" % (k, l))
+    with open(os.path.join(a.out_dir, "rttm"), "w") as f:
+        f.write("".join(l + "\n" for l in res["rttm"]))
+    if a.write_scores:
+        ro, mo = res["rec_off"], res["mat_off"]
+        for r, reco in enumerate(res["recordings"]):
+            n = int(ro[r + 1] - ro[r])
+            np.savetxt(os.path.join(a.out_dir, "scores." + reco), res["scores"][mo[r]:mo[r + 1]].reshape(n, n), fmt="%.9g")
+    print("diarized {} recordings ({} windows, {} segments) into {}".format(len(res["recordings"]), len(res["keys"]),
+                                                                           len(res["rttm"]), a.out_dir))
