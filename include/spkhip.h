@@ -688,6 +688,31 @@ int spk_ahc_batch(const float* S, const long long* rec_off /*host [R+1]*/, const
                   const int* min_clusters /*[R]*/, const double* threshold /*[R]*/, double* ws, long long ws_elems, int* labels /*[Ntot]*/,
                   int* merges /*[Ntot][2]*/, double* merge_cost /*[Ntot]*/, int* n_merges /*[R]*/, long long Ntot, int R, void* stream);
 
+/* ---- VBx resegmentation (csrc/diar.hip) ---------------------------------------------------------------------
+ * A variational-Bayes HMM over the window rows of every recording of a batch (the layout above), one workgroup per recording (no
+ * workgroup waits on another), fp64 throughout.  X [Ntot][D]: rows in the space where the within-class covariance is I; Phi [D] >= 0:
+ * the between-class variances.  One Smax per launch: gamma [Ntot][Smax] (in: initial responsibilities, out: the last ones), pi
+ * [R][Smax] (in and out), n_states[r] in [1, Smax]: columns at or beyond n_states[r] are not read and are written as 0.  The rule
+ * (rho = X sqrt(Phi), G_t = -0.5 (sum_d X_td^2 + D log 2 pi); per iteration N_s, invL_sd = 1 / (1 + Fa/Fb N_s Phi_d), alpha_sd,
+ * logp_ts, forward-backward under tr_ij = loopP [i == j] + (1 - loopP) pi_j, ELBO_it = tll + 0.5 Fb sum_sd (log invL_sd - invL_sd -
+ * alpha_sd^2 + 1), the pi update, and the stop after iteration it > 0 with ELBO_it - ELBO_{it-1} < epsilon; epsilon = -inf: never)
+ * is stated in full in DESIGN.md section 6o.  elbo [R][max_iters]: recording r writes its first n_iters[r] slots and leaves the rest.
+ * A state whose prior is below 2^-900 is taken to have prior 0: its gamma is 0.  Every sum has a fixed order and there are no
+ * atomics: the same bits on every run and wherever a recording sits in a batch.
+ * rec_off and n_states are given twice: HOST arrays, checked before anything is launched, and their device copies, which the kernel
+ * reads.  Refused on the host (< 0, nothing written): a bad rec_off (the checks of spk_diar_tables), D outside [1, 512], Smax outside
+ * [1, spk_vbx_max_states()], an n_states[r] outside [1, Smax], a recording longer than spk_ahc_max_n(), ws_elems below
+ * spk_vbx_ws_elems(), Fa or Fb not positive and finite, loopP outside (0, 1), max_iters < 1, epsilon NaN or +inf. */
+int spk_vbx_threads(void);     /* threads of the workgroup that runs one recording */
+int spk_vbx_max_states(void);  /* 64: one lane per state */
+/* host only: the doubles spk_vbx_batch needs, Ntot (3 + 2 Smax) + R Smax D; < 0 for a shape spk_vbx_batch refuses */
+long long spk_vbx_ws_elems(const long long* rec_off /*host [R+1]*/, int R, int Smax, int D);
+int spk_vbx_batch(const double* X /*[Ntot][D]*/, const double* Phi /*[D]*/, const long long* rec_off /*host [R+1]*/,
+                  const long long* rec_off_dev /*[R+1]*/, const int* n_states /*host [R]*/, const int* n_states_dev /*[R]*/,
+                  double* gamma /*[Ntot][Smax]*/, double* pi /*[R][Smax]*/, double Fa, double Fb, double loopP, int max_iters,
+                  double epsilon, double* ws, long long ws_elems, double* elbo /*[R][max_iters]*/, int* n_iters /*[R]*/, long long Ntot,
+                  int D, int R, int Smax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// Diarization back end on the device: what Kaldi's callhome_diarization recipe runs behind the sliding-window
+// Diarization back end on the device (DESIGN.md sections 6n and 6o): what Kaldi's callhome_diarization recipe runs behind the sliding-window
 // extraction - ivector-plda-scoring-dense (without its per-recording PCA) and agglomerative-cluster.
 //   spk_diar_tables   - host only: checks rec_off and derives the three offset tables both kernels read
 //   spk_score_dense_q - q_i = scale * sum_d k_d U_id^2 per row (one wave per row, fp64, a fixed lane order)
@@ -7,6 +7,8 @@
 //                       triangle, mirrored, so S == S^T bit for bit
 //   spk_ahc_batch     - average-linkage agglomerative clustering, one workgroup per recording running its whole merge loop with
 //                       __syncthreads() alone: nothing waits on another workgroup
+//   spk_vbx_batch     - VBx resegmentation (section 6o): a variational-Bayes HMM over the window rows, one workgroup per recording
+//                       running every iteration, its forward-backward pass in scaled form on one wave
 // Fragment map of the fp64 matrix instruction: see csrc/plda.hip.  No floating-point atomics anywhere: the same bits on every run.
 #pragma clang fp contract(off)
 #include "spk_common.h"
@@ -349,5 +351,284 @@ extern "C" int spk_ahc_batch(const float* S, const long long* rec_off, const lon
     hipLaunchKernelGGL(ahc_kernel, dim3((unsigned)R), dim3(AHC_THREADS), 0, (hipStream_t)stream, S, tab_dev, min_clusters, threshold, ws,
                        labels, merges, merge_cost, n_merges, R);
     SPK_LAUNCH_CHECK("spk_ahc_batch");
+    return 0;
+}
+
+// ---- VBx resegmentation --------------------------------------------------------------------------------------
+// A variational-Bayes HMM over the window rows of one recording: states are speakers, tr_ij = loopP [i == j] + (1 - loopP) pi_j.  One
+// workgroup per recording runs every iteration with __syncthreads() alone; every loop is bounded by max_iters, T, S or D.
+// Workspace of recording r, from ws + rec_off[r] (3 + 2 Smax) + r Smax D:  G [T], M [T], C [T], P [T][S], A [T][S], alpha [S][D].
+// The forward-backward pass is the scaled form of the contract's O(S) recursion: with M_t = max over the live states of logp_ts and
+// p_ts = exp(logp_ts - M_t) (formed by the whole workgroup, so the chain holds no exp and no log),
+//   u_ts = p_ts (loopP a_{t-1,s} + (1 - loopP) pi_s)   (u_0s = p_0s pi_s),   c_t = sum_s u_ts,   a_ts = u_ts / c_t
+//   x_ts = p_ts b_ts / c_t,   b_{t-1,s} = loopP x_ts + (1 - loopP) sum_j pi_j x_tj   (b_{T-1} = 1)
+// so that a_ts = e^{lfw_ts} / sum_i e^{lfw_ti}, gamma_ts = a_ts b_ts, tll = sum_t (M_t + log c_t) and step 7's summand is pi_s x_ts.
+// A state is live while pi_s >= 2^-900; below that its prior is taken as 0 (p = 0, gamma = 0: what the contract gives for pi_s = 0).
+// With live priors b stays below 1 + loopP / ((1 - loopP) pi_s) <= 2^954, so nothing overflows and 0 * inf cannot arise.
+#define VBX_THREADS 256
+#define VBX_WAVES (VBX_THREADS / 64)
+#define VBX_MAX_S 64            // one lane per state
+#define VBX_PF 8                // chain steps whose operands are loaded ahead
+#define VBX_PI_FLOOR 0x1p-900
+#define VBX_LOG_2PI 1.8378770664093454836
+
+// v of the lane that the DPP control names (a move inside a row of 16 lanes: no LDS crossbar, a few cycles)
+template <int CTRL>
+static __device__ __forceinline__ double vbx_dpp(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// the sum over the lanes 0 .. W - 1 (W a power of two), the same bits in each of them; lanes at or past S hold 0.  Partners at
+// distance 1 and 2 by quad permutes, the other half of 8 and of 16 lanes by the two row mirrors, 32 and 64 lanes through the
+// crossbar; both partners of a pair add the same two numbers, so every lane ends with the same bits.
+static __device__ __forceinline__ double vbx_sum(double v, int W) {
+    if (W >= 2) v += vbx_dpp<0xB1>(v);                              // quad_perm [1, 0, 3, 2]
+    if (W >= 4) v += vbx_dpp<0x4E>(v);                              // quad_perm [2, 3, 0, 1]
+    if (W >= 8) v += vbx_dpp<0x141>(v);                             // row_half_mirror
+    if (W >= 16) v += vbx_dpp<0x140>(v);                            // row_mirror
+    if (W >= 32) v += __shfl_xor(v, 16, 64);
+    if (W >= 64) v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(VBX_THREADS) void vbx_kernel(const double* __restrict__ X, const double* __restrict__ Phi,
+                                                          const long long* __restrict__ rec_off, const int* __restrict__ n_states,
+                                                          double* __restrict__ gamma, double* __restrict__ pi, double Fa, double Fb,
+                                                          double loopP, int max_iters, double epsilon, double* __restrict__ ws,
+                                                          double* __restrict__ elbo, int* __restrict__ n_iters, int D, int Smax) {
+    __shared__ double sq[DIAR_MAX_D], phi[DIAR_MAX_D];
+    __shared__ double npart[VBX_WAVES][VBX_MAX_S];
+    __shared__ double cS[VBX_MAX_S], eS[VBX_MAX_S], piS[VBX_MAX_S];
+    __shared__ double red[VBX_WAVES];
+
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = rec_off[r];
+    const int T = (int)(rec_off[r + 1] - row0), S = n_states[r];
+    int W = 1;
+    while (W < S) W <<= 1;
+    const double* Xr = X + (size_t)row0 * D;
+    double* gam = gamma + (size_t)row0 * Smax;
+    double* G = ws + (size_t)row0 * (3 + 2 * Smax) + (size_t)r * Smax * D;
+    double* M = G + T;
+    double* C = M + T;
+    double* P = C + T;
+    double* A = P + (size_t)T * S;
+    double* AL = A + (size_t)T * S;
+    const double FaFb = Fa / Fb, omlp = 1.0 - loopP;
+
+    for (int d = tid; d < D; d += VBX_THREADS) {
+        phi[d] = Phi[d];
+        sq[d] = sqrt(Phi[d]);
+    }
+    if (tid < VBX_MAX_S) {
+        const double p0 = tid < S ? pi[(size_t)r * Smax + tid] : 0.0;
+        piS[tid] = p0 >= VBX_PI_FLOOR ? p0 : 0.0;
+    }
+    for (int t = wave; t < T; t += VBX_WAVES) {
+        double s = 0.0;
+        for (int d = lane; d < D; d += 64) s += Xr[(size_t)t * D + d] * Xr[(size_t)t * D + d];
+        s = vbx_sum(s, 64);
+        if (lane == 0) G[t] = -0.5 * (s + (double)D * VBX_LOG_2PI);
+    }
+    __syncthreads();
+
+    double prev = 0.0;
+    int done = 0;
+    for (int it = 0; it < max_iters; ++it) {
+        // 1: N_s, wave w over the windows t = w, w + 4, ...; the four partial sums meet in a fixed order where they are used
+        {
+            double a = 0.0;
+            if (lane < S)
+#pragma unroll 8
+                for (int t = wave; t < T; t += VBX_WAVES) a += gam[(size_t)t * Smax + lane];
+            npart[wave][lane] = a;
+        }
+        __syncthreads();
+        // 2, 3: alpha_sd, one (s, d) per thread, the sum over t in order
+        for (int idx = tid; idx < S * D; idx += VBX_THREADS) {
+            const int s = idx / D, d = idx - s * D;
+            double acc = 0.0;
+#pragma unroll 8
+            for (int t = 0; t < T; ++t) acc += gam[(size_t)t * Smax + s] * (Xr[(size_t)t * D + d] * sq[d]);
+            const double Ns = ((npart[0][s] + npart[1][s]) + npart[2][s]) + npart[3][s];
+            const double invL = 1.0 / (1.0 + FaFb * Ns * phi[d]);
+            AL[idx] = FaFb * invL * acc;
+        }
+        __syncthreads();
+        // the two sums over d of every state: one wave per state, lane l takes d = l, l + 64, ...
+        for (int s = wave; s < S; s += VBX_WAVES) {
+            const double Ns = ((npart[0][s] + npart[1][s]) + npart[2][s]) + npart[3][s];
+            double c = 0.0, e = 0.0;
+            for (int d = lane; d < D; d += 64) {
+                const double invL = 1.0 / (1.0 + FaFb * Ns * phi[d]), a = AL[s * D + d];
+                c += (invL + a * a) * phi[d];
+                e += ((log(invL) - invL) - a * a) + 1.0;
+            }
+            c = vbx_sum(c, 64);
+            e = vbx_sum(e, 64);
+            if (lane == 0) {
+                cS[s] = -0.5 * c;
+                eS[s] = e;
+            }
+        }
+        __syncthreads();
+        // 4: logp_ts, one (t, s) per thread
+        for (int idx = tid; idx < T * S; idx += VBX_THREADS) {
+            const int t = idx / S, s = idx - t * S;
+            double dot = 0.0;
+#pragma unroll 8
+            for (int d = 0; d < D; ++d) dot += (Xr[(size_t)t * D + d] * sq[d]) * AL[s * D + d];
+            P[idx] = Fa * ((dot + cS[s]) + G[t]);
+        }
+        __syncthreads();
+        // M_t and p_ts, one window per thread
+        for (int t = tid; t < T; t += VBX_THREADS) {
+            double m = -__builtin_inf();
+            for (int s = 0; s < S; ++s)
+                if (piS[s] > 0.0) m = fmax(m, P[(size_t)t * S + s]);
+            M[t] = m;
+            for (int s = 0; s < S; ++s) P[(size_t)t * S + s] = piS[s] > 0.0 ? exp(P[(size_t)t * S + s] - m) : 0.0;
+        }
+        __syncthreads();
+        // 5, 7: the two chains on one wave, lane s holding state s; the operands of VBX_PF steps are loaded a block ahead
+        if (wave == 0) {
+            const bool live = lane < S;
+            const double pis = piS[lane], q = omlp * pis;
+            double ahat = 0.0, buf[VBX_PF];
+#pragma unroll
+            for (int k = 0; k < VBX_PF; ++k) buf[k] = (live && k < T) ? P[(size_t)k * S + lane] : 0.0;
+            for (int t0 = 0; t0 < T; t0 += VBX_PF) {
+                double cur[VBX_PF];
+#pragma unroll
+                for (int k = 0; k < VBX_PF; ++k) {
+                    cur[k] = buf[k];
+                    const int tn = t0 + VBX_PF + k;
+                    buf[k] = (live && tn < T) ? P[(size_t)tn * S + lane] : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < VBX_PF; ++k) {
+                    const int t = t0 + k;
+                    if (t < T) {                                     // wave-uniform
+                        const double u = t == 0 ? cur[k] * pis : cur[k] * (loopP * ahat + q);
+                        const double c = vbx_sum(u, W);
+                        ahat = live ? u / c : 0.0;
+                        if (live) A[(size_t)t * S + lane] = ahat;
+                        if (lane == 0) C[t] = c;
+                    }
+                }
+            }
+            double bhat = 1.0, acc = 0.0, g = ahat;                 // gamma_{T-1} = a_{T-1}
+            if (live) gam[(size_t)(T - 1) * Smax + lane] = g;
+            // step j = 0, 1, ... handles t = T - 1 - j >= 1: it needs p_t, c_t and a_{t-1}
+            double bp[VBX_PF], bc[VBX_PF], ba[VBX_PF];
+#pragma unroll
+            for (int k = 0; k < VBX_PF; ++k) {
+                const int t = T - 1 - k;
+                const bool v = t >= 1;
+                bp[k] = (live && v) ? P[(size_t)t * S + lane] : 0.0;
+                bc[k] = v ? C[t] : 1.0;
+                ba[k] = (live && v) ? A[(size_t)(t - 1) * S + lane] : 0.0;
+            }
+            for (int j0 = 0; j0 < T - 1; j0 += VBX_PF) {
+                double cp[VBX_PF], cc[VBX_PF], ca[VBX_PF];
+#pragma unroll
+                for (int k = 0; k < VBX_PF; ++k) {
+                    cp[k] = bp[k];
+                    cc[k] = bc[k];
+                    ca[k] = ba[k];
+                    const int t = T - 1 - (j0 + VBX_PF + k);
+                    const bool v = t >= 1;
+                    bp[k] = (live && v) ? P[(size_t)t * S + lane] : 0.0;
+                    bc[k] = v ? C[t] : 1.0;
+                    ba[k] = (live && v) ? A[(size_t)(t - 1) * S + lane] : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < VBX_PF; ++k) {
+                    const int t = T - 1 - (j0 + k);
+                    if (t >= 1) {                                    // wave-uniform
+                        const double x = (cp[k] * bhat) / cc[k], y = pis * x;
+                        acc += y;
+                        bhat = loopP * x + omlp * vbx_sum(y, W);
+                        g = ca[k] * bhat;
+                        if (live) gam[(size_t)(t - 1) * Smax + lane] = g;
+                    }
+                }
+            }
+            double pn = live ? g + omlp * acc : 0.0;                // g = gamma_0 here (T = 1: acc = 0)
+            pn = pn / vbx_sum(pn, W);
+            piS[lane] = (live && pn >= VBX_PI_FLOOR) ? pn : 0.0;
+        }
+        __syncthreads();
+        // 6, 8: tll = sum_t (M_t + log c_t) and the ELBO, the same bits in every thread
+        {
+            double s = 0.0;
+            for (int t = tid; t < T; t += VBX_THREADS) s += M[t] + log(C[t]);
+            s = vbx_sum(s, 64);
+            if (lane == 0) red[wave] = s;
+        }
+        __syncthreads();
+        double e = 0.0;
+        for (int s = 0; s < S; ++s) e += eS[s];
+        const double el = (((red[0] + red[1]) + red[2]) + red[3]) + 0.5 * Fb * e;
+        if (tid == 0) elbo[(size_t)r * max_iters + it] = el;
+        done = it + 1;
+        if (it > 0 && el - prev < epsilon) break;                   // block-uniform
+        prev = el;
+    }
+    // (the last barrier of the loop stands between the last writes of piS and gamma and these reads)
+    for (int s = tid; s < Smax; s += VBX_THREADS) pi[(size_t)r * Smax + s] = s < S ? piS[s] : 0.0;
+    if (S < Smax)
+        for (int idx = tid; idx < T * (Smax - S); idx += VBX_THREADS) {
+            const int t = idx / (Smax - S);
+            gam[(size_t)t * Smax + S + (idx - t * (Smax - S))] = 0.0;
+        }
+    if (tid == 0) n_iters[r] = done;
+}
+
+extern "C" int spk_vbx_threads(void) { return VBX_THREADS; }
+extern "C" int spk_vbx_max_states(void) { return VBX_MAX_S; }
+
+// what both host entry points check: rec_off (as spk_diar_tables does), D, Smax and the length of every recording
+static int vbx_shape(const char* who, const long long* rec_off, int R, long long Ntot, int Smax, int D) {
+    const int rc = diar_tables(who, rec_off, R, Ntot, nullptr);
+    if (rc) return rc;
+    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "%s: D=%d must lie in [1, %d]", who, D, DIAR_MAX_D);
+    SPK_REQUIRE(Smax >= 1 && Smax <= VBX_MAX_S, "%s: Smax=%d must lie in [1, %d]", who, Smax, VBX_MAX_S);
+    for (int r = 0; r < R; ++r)
+        SPK_REQUIRE(rec_off[r + 1] - rec_off[r] <= AHC_MAX_N, "%s: recording %d has %lld windows, the cap is %d", who, r,
+                    rec_off[r + 1] - rec_off[r], AHC_MAX_N);
+    return 0;
+}
+
+extern "C" long long spk_vbx_ws_elems(const long long* rec_off, int R, int Smax, int D) {
+    SPK_REQUIRE(rec_off && R >= 1, "spk_vbx_ws_elems: bad arguments (R=%d)", R);
+    const int rc = vbx_shape("spk_vbx_ws_elems", rec_off, R, rec_off[R], Smax, D);
+    if (rc) return rc;
+    return rec_off[R] * (3 + 2 * (long long)Smax) + (long long)R * Smax * D;
+}
+
+extern "C" int spk_vbx_batch(const double* X, const double* Phi, const long long* rec_off, const long long* rec_off_dev,
+                             const int* n_states, const int* n_states_dev, double* gamma, double* pi, double Fa, double Fb,
+                             double loopP, int max_iters, double epsilon, double* ws, long long ws_elems, double* elbo, int* n_iters,
+                             long long Ntot, int D, int R, int Smax, void* stream) {
+    const int rc = vbx_shape("spk_vbx_batch", rec_off, R, Ntot, Smax, D);
+    if (rc) return rc;
+    SPK_REQUIRE(n_states, "spk_vbx_batch: n_states is missing");
+    for (int r = 0; r < R; ++r)
+        SPK_REQUIRE(n_states[r] >= 1 && n_states[r] <= Smax, "spk_vbx_batch: n_states[%d]=%d must lie in [1, Smax=%d]", r, n_states[r],
+                    Smax);
+    SPK_REQUIRE(Fa > 0.0 && Fa < __builtin_inf() && Fb > 0.0 && Fb < __builtin_inf(), "spk_vbx_batch: Fa=%g and Fb=%g must be positive and finite",
+                Fa, Fb);
+    SPK_REQUIRE(loopP > 0.0 && loopP < 1.0, "spk_vbx_batch: loopP=%g must lie strictly between 0 and 1", loopP);
+    SPK_REQUIRE(max_iters >= 1, "spk_vbx_batch: max_iters=%d must be at least 1", max_iters);
+    SPK_REQUIRE(epsilon < __builtin_inf(), "spk_vbx_batch: epsilon=%g must be a number below +inf (-inf: never stop early)", epsilon);
+    const long long need = Ntot * (3 + 2 * (long long)Smax) + (long long)R * Smax * D;
+    SPK_REQUIRE(ws_elems >= need, "spk_vbx_batch: the workspace holds %lld doubles, the batch needs %lld", ws_elems, need);
+    SPK_REQUIRE(X && Phi && rec_off_dev && n_states_dev && gamma && pi && ws && elbo && n_iters, "spk_vbx_batch: null device pointer");
+    hipLaunchKernelGGL(vbx_kernel, dim3((unsigned)R), dim3(VBX_THREADS), 0, (hipStream_t)stream, X, Phi, rec_off_dev, n_states_dev, gamma,
+                       pi, Fa, Fb, loopP, max_iters, epsilon, ws, elbo, n_iters, D, Smax);
+    SPK_LAUNCH_CHECK("spk_vbx_batch");
     return 0;
 }

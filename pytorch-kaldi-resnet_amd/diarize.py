@@ -89,18 +89,23 @@ def score_dense(emb, rec_off, kind="cosine", mean=None, transform=None, plda=Non
     emb = np.asarray(emb)
     ro, mat_off = _rec_off(rec_off, emb.shape[0])
     U, q, g, K = dense_inputs(emb, kind, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
+    return _score_rows(U, q, g, K, ro, mat_off, backend, return_device), mat_off
+
+
+def _score_rows(U, q, g, K, ro, mat_off, backend, return_device):
+    """the dense scores of rows that dense_inputs made (on `hip`: device tensors in, and with return_device a device tensor out)"""
     if backend == "hip":
         from . import ops
         out, mo = ops.score_dense(U, ro, q, g, K)
         assert (mo == mat_off).all()
-        return (out if return_device else out.cpu().numpy()), mat_off
+        return out if return_device else out.cpu().numpy()
     out = np.empty(int(mat_off[-1]), dtype=np.float32)
     for r in range(ro.size - 1):
         u, qq = U[ro[r]:ro[r + 1]], q[ro[r]:ro[r + 1]]
         s = np.triu(((u * g[None, :]) @ u.T + qq[:, None]) + qq[None, :] + K)
         s = s + np.triu(s, 1).T                                     # the upper triangle, mirrored
         out[mat_off[r]:mat_off[r + 1]] = s.astype(np.float32).ravel()
-    return out, mat_off
+    return out
 
 
 # ---- clustering -------------------------------------------------------------------------------------------------------------------
@@ -215,6 +220,176 @@ def cluster(scores, rec_off, threshold=None, num_speakers=None, backend="host", 
     return labels, merges, cost, nm
 
 
+# ---- VBx resegmentation ------------------------------------------------------------------------------------
+VBX_DEFAULTS = dict(Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=40, epsilon=1e-6, init_smoothing=7.0)
+VBX_PI_FLOOR = 2.0 ** -900      # a state whose prior is below this is taken to have prior 0 (csrc/diar.hip)
+
+
+def vbx_inputs(emb, mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True, simple_length_normalization=False,
+               backend="host"):
+    """-> (X [Ntot][D'] fp64, Phi [D'] fp64): the rows of dense_inputs(kind="plda") - Plda::TransformIvector for one utterance per
+    side, the space where the within-class covariance is I - and the between-class variances psi of the smoothed model.  numpy on
+    `host`, device tensors on `hip`."""
+    U = dense_inputs(emb, "plda", mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)[0]
+    psi = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))[2]
+    return U, (_plda._up(psi) if backend == "hip" else psi)
+
+
+def vbx_init(init_labels, rec_off, init_smoothing=7.0):
+    """first-pass labels [Ntot] -> (gamma [Ntot][Smax], pi [R][Smax], n_states [R]): per recording S = its number of distinct labels
+    (state s: the s-th smallest), gamma_ts = softmax_s(init_smoothing [label_t == s]) over its S states, pi_s = 1 / S; the columns
+    at or beyond S are 0"""
+    lab = np.asarray(init_labels)
+    ro, _ = _rec_off(rec_off, lab.shape[0])
+    R = ro.size - 1
+    idx = [np.unique(lab[ro[r]:ro[r + 1]], return_inverse=True)[1] for r in range(R)]
+    ns = np.array([int(i.max()) + 1 for i in idx], dtype=np.int32)
+    Smax = int(ns.max())
+    gamma = np.zeros((lab.shape[0], Smax))
+    pi = np.zeros((R, Smax))
+    for r in range(R):
+        S = int(ns[r])
+        z = float(init_smoothing) * (idx[r][:, None] == np.arange(S)[None, :])
+        e = np.exp(z - z.max(axis=1, keepdims=True))
+        gamma[ro[r]:ro[r + 1], :S] = e / e.sum(axis=1, keepdims=True)
+        pi[r, :S] = 1.0 / S
+    return gamma, pi, ns
+
+
+def vbx_labels(gamma, rec_off, n_states):
+    """the window label: argmax_s gamma_ts over the recording's states, ties to the lowest s, renumbered 1, 2, ... by lowest member
+    window (section 6n's rule) -> int32 [Ntot]"""
+    ro = np.asarray(rec_off, dtype=np.int64)
+    out = np.empty(gamma.shape[0], dtype=np.int32)
+    for r in range(ro.size - 1):
+        a = np.argmax(gamma[ro[r]:ro[r + 1], :int(n_states[r])], axis=1)
+        _, first, inv = np.unique(a, return_index=True, return_inverse=True)
+        out[ro[r]:ro[r + 1]] = (np.argsort(np.argsort(first)) + 1)[inv]
+    return out
+
+
+def _vbx_host(X, Phi, gamma, pi, Fa, Fb, loopP, max_iters, epsilon):
+    """One recording by the rule of section 6o in numpy fp64, with the forward-backward pass in the scaled form the kernel uses
+    (csrc/diar.hip): a_t = e^{lfw_t} / sum_i e^{lfw_ti}, gamma_t = a_t b_t.  -> (gamma, pi, elbo list)"""
+    T, D = X.shape
+    rho = X * np.sqrt(Phi)[None, :]
+    G = -0.5 * ((X * X).sum(axis=1) + D * np.log(2 * np.pi))
+    FaFb = Fa / Fb
+    pi = np.where(pi >= VBX_PI_FLOOR, pi, 0.0)
+    elbo = []
+    with np.errstate(all="ignore"):
+        for it in range(max_iters):
+            N = gamma.sum(axis=0)
+            invL = 1.0 / (1.0 + FaFb * N[:, None] * Phi[None, :])
+            alpha = FaFb * invL * (gamma.T @ rho)
+            logp = Fa * (rho @ alpha.T - 0.5 * ((invL + alpha ** 2) @ Phi)[None, :] + G[:, None])
+            live = pi > 0
+            M = np.where(live[None, :], logp, -np.inf).max(axis=1)
+            p = np.where(live[None, :], np.exp(logp - M[:, None]), 0.0)
+            a = np.empty_like(p)
+            c = np.empty(T)
+            u = p[0] * pi
+            c[0] = u.sum()
+            a[0] = u / c[0]
+            for t in range(1, T):
+                u = p[t] * (loopP * a[t - 1] + (1.0 - loopP) * pi)
+                c[t] = u.sum()
+                a[t] = u / c[t]
+            gamma = np.empty_like(p)
+            gamma[T - 1] = a[T - 1]
+            b = np.ones(p.shape[1])
+            acc = np.zeros(p.shape[1])
+            for t in range(T - 1, 0, -1):
+                x = p[t] * b / c[t]
+                y = pi * x
+                acc += y
+                b = loopP * x + (1.0 - loopP) * y.sum()
+                gamma[t - 1] = a[t - 1] * b
+            elbo.append(float((M + np.log(c)).sum() + 0.5 * Fb * (np.log(invL) - invL - alpha ** 2 + 1.0).sum()))
+            pi = gamma[0] + (1.0 - loopP) * acc
+            pi = pi / pi.sum()
+            pi = np.where(pi >= VBX_PI_FLOOR, pi, 0.0)
+            if it > 0 and elbo[-1] - elbo[-2] < epsilon:
+                break
+    return gamma, pi, elbo
+
+
+def vbx(X, Phi, rec_off, init_labels=None, gamma=None, pi=None, n_states=None, Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=40,
+        epsilon=1e-6, init_smoothing=7.0, backend="host", ws_budget_bytes=1 << 31):
+    """VBx (section 6o) over the rows X [Ntot][D] (vbx_inputs) of the recordings rec_off [R + 1], Phi [D] >= 0.  The start is either
+    init_labels [Ntot] (first-pass labels: vbx_init) or gamma [Ntot][Smax] with optional pi [R][Smax] (default 1 / n_states) and
+    n_states [R] (default Smax).  epsilon = -inf always runs max_iters iterations.  On `hip` X and Phi may be device tensors.
+    -> dict(labels int32 [Ntot] (vbx_labels), gamma [Ntot][Smax], pi [R][Smax], elbo [R][max_iters] (NaN past n_iters), n_iters
+    int32 [R], n_states int32 [R]) as numpy arrays."""
+    if not (Fa > 0 and np.isfinite(Fa) and Fb > 0 and np.isfinite(Fb)):
+        raise ValueError("Fa and Fb must be positive and finite, got %r and %r" % (Fa, Fb))
+    if not 0.0 < loop_prob < 1.0:
+        raise ValueError("loop_prob must lie strictly between 0 and 1, got %r" % (loop_prob,))
+    if int(max_iters) != max_iters or max_iters < 1:
+        raise ValueError("max_iters must be an integer of at least 1, got %r" % (max_iters,))
+    if not epsilon < np.inf:
+        raise ValueError("epsilon must be a number below +inf, got %r" % (epsilon,))
+    Ntot, D = X.shape
+    ro, _ = _rec_off(rec_off, Ntot)
+    R = ro.size - 1
+    if (init_labels is None) == (gamma is None):
+        raise ValueError("give exactly one of init_labels and gamma")
+    if init_labels is not None:
+        if pi is not None or n_states is not None:
+            raise ValueError("pi and n_states go with gamma, not with init_labels")
+        if np.shape(init_labels) != (Ntot,):
+            raise ValueError("init_labels must hold one label per window (%d), got %s" % (Ntot, np.shape(init_labels)))
+        gamma, pi, ns = vbx_init(init_labels, ro, init_smoothing)
+    else:
+        gamma = np.array(gamma, dtype=np.float64)
+        if gamma.ndim != 2 or gamma.shape[0] != Ntot or gamma.shape[1] < 1:
+            raise ValueError("gamma must be [Ntot = %d][Smax], got %s" % (Ntot, gamma.shape))
+        ns = _per_recording(n_states, R, np.int32, gamma.shape[1], "n_states")
+        if (ns < 1).any() or (ns > gamma.shape[1]).any():
+            raise ValueError("n_states must lie in [1, Smax = %d]" % gamma.shape[1])
+        if pi is None:
+            pi = (np.arange(gamma.shape[1])[None, :] < ns[:, None]) / ns[:, None].astype(np.float64)
+        pi = np.array(pi, dtype=np.float64)
+        if pi.shape != (R, gamma.shape[1]):
+            raise ValueError("pi must be [R = %d][Smax = %d], got %s" % (R, gamma.shape[1], pi.shape))
+    Smax = gamma.shape[1]
+    phi_host = np.asarray(Phi.cpu().numpy() if hasattr(Phi, "cpu") else Phi, dtype=np.float64)
+    if phi_host.shape != (D,) or not (phi_host >= 0).all():
+        raise ValueError("Phi must hold %d values >= 0" % D)
+    elbo = np.full((R, int(max_iters)), np.nan)
+    if backend == "hip":
+        import torch
+        from . import ops
+        if Smax > ops.vbx_max_states():
+            raise ValueError("the hip back end takes at most %d states per recording, got %d" % (ops.vbx_max_states(), Smax))
+        if int(np.diff(ro).max()) > ops.ahc_max_n():
+            raise ValueError("vbx: a recording has %d windows, the cap is %d" % (int(np.diff(ro).max()), ops.ahc_max_n()))
+        Xd = X if torch.is_tensor(X) else _plda._up(np.asarray(X, dtype=np.float64))
+        Pd = Phi if torch.is_tensor(Phi) else _plda._up(phi_host)
+        gd, pd = _plda._up(gamma), _plda._up(pi)
+        ed, nd = ops.vbx_batch(Xd.contiguous(), Pd, ro, ns, gd, pd, Fa, Fb, loop_prob, int(max_iters), epsilon,
+                               ws_budget_bytes=ws_budget_bytes)
+        gamma, pi, elbo, nit = gd.cpu().numpy(), pd.cpu().numpy(), ed.cpu().numpy(), nd.cpu().numpy()
+    else:
+        assert backend == "host", backend
+        Xh = np.asarray(X.cpu().numpy() if hasattr(X, "cpu") else X, dtype=np.float64)
+        nit = np.empty(R, dtype=np.int32)
+        for r in range(R):
+            S = int(ns[r])
+            g, p, el = _vbx_host(Xh[ro[r]:ro[r + 1]], phi_host, gamma[ro[r]:ro[r + 1], :S], pi[r, :S], float(Fa), float(Fb),
+                                 float(loop_prob), int(max_iters), float(epsilon))
+            gamma[ro[r]:ro[r + 1]] = 0.0
+            gamma[ro[r]:ro[r + 1], :S] = g
+            pi[r] = 0.0
+            pi[r, :S] = p
+            elbo[r, :len(el)] = el
+            nit[r] = len(el)
+    return {"labels": vbx_labels(gamma, ro, ns), "gamma": gamma, "pi": pi, "elbo": elbo, "n_iters": nit, "n_states": ns}
+
+
+_vbx = vbx      # (diarize() has a parameter of that name)
+
+
 # ---- RTTM -------------------------------------------------------------------------------------------------------------------------
 def read_segments(path):
     """'<key> <recording> <start s> <end s>' lines (decode.py --window's segments.<name>) -> [(key, recording, start, end)]"""
@@ -308,12 +483,21 @@ def read_reco2num_spk(path):
 
 
 def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=None, recordings=None, backend="host", channel=0,
-            return_scores=False, **score_args):
+            return_scores=False, vbx=None, **score_args):
     """embeddings: key -> vector (scoring.read_embeddings), segments: read_segments' list; exactly one of threshold and
     reco2num_spk (recording -> speakers).  -> dict(recordings, rec_off, mat_off, keys (batch order), labels, scores (numpy with
-    return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges)"""
+    return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges).
+    vbx: None, or a dict with any of Fa, Fb, loop_prob, max_iters, epsilon, init_smoothing (VBX_DEFAULTS): the clustering's labels
+    then seed VBx (section 6o; kind must be plda), `labels` and `rttm` hold its result and the dict gains ahc_labels, vbx_elbo,
+    vbx_n_iters and vbx_pi; on `hip` the rows stay on the device between scoring and VBx."""
     if (threshold is None) == (reco2num_spk is None):
         raise ValueError("give exactly one of threshold and reco2num_spk")
+    if vbx is not None:
+        if kind != "plda":
+            raise ValueError("vbx needs kind='plda' (its rows and variances are the PLDA's), got %r" % (kind,))
+        unknown = sorted(set(vbx) - set(VBX_DEFAULTS))
+        if unknown:
+            raise ValueError("unknown vbx parameters: " + " ".join(unknown))
     emb_keys = embeddings.keys_list if hasattr(embeddings, "keys_list") else list(embeddings)
     order, rows, rec_off = group_windows(emb_keys, segments, recordings)
     num = None
@@ -331,9 +515,22 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
         emb = embeddings.mat[[embeddings.index[k] for k in keys]]
     else:
         emb = np.stack([np.asarray(embeddings[k], dtype=np.float64) for k in keys])
-    scores, mat_off = score_dense(emb, rec_off, kind, backend=backend, return_device=(backend == "hip"), **score_args)
+    if vbx is None:
+        scores, mat_off = score_dense(emb, rec_off, kind, backend=backend, return_device=(backend == "hip"), **score_args)
+    else:
+        ro, mat_off = _rec_off(rec_off, emb.shape[0])
+        U, q, g, K = dense_inputs(emb, kind, backend=backend, **score_args)
+        scores = _score_rows(U, q, g, K, ro, mat_off, backend, backend == "hip")
     labels, merges, cost, nm = cluster(scores, rec_off, threshold, num, backend)
     segs = [segments[i] for i in flat]
-    return {"recordings": order, "rec_off": rec_off, "mat_off": mat_off, "keys": keys, "labels": labels,
-            "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),
-            "merges": merges, "merge_cost": cost, "n_merges": nm}
+    extra = {}
+    if vbx is not None:
+        psi = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in score_args["plda"]), float(score_args.get("smoothing", 0.0)))[2]
+        res = _vbx(U, psi, rec_off, init_labels=labels, backend=backend, **vbx)
+        extra = {"ahc_labels": labels, "vbx_elbo": res["elbo"], "vbx_n_iters": res["n_iters"], "vbx_pi": res["pi"]}
+        labels = res["labels"]
+    out = {"recordings": order, "rec_off": rec_off, "mat_off": mat_off, "keys": keys, "labels": labels,
+           "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),
+           "merges": merges, "merge_cost": cost, "n_merges": nm}
+    out.update(extra)
+    return out

@@ -131,6 +131,10 @@ _SIGS = {
     "spk_ahc_threads": [],
     "spk_ahc_max_n": [],
     "spk_ahc_batch": [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _I, _P],
+    "spk_vbx_threads": [],
+    "spk_vbx_max_states": [],
+    "spk_vbx_ws_elems": [_P, _I, _I, _I],               # host only; returns long long (restype set in lib())
+    "spk_vbx_batch": [_P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I, _D, _P, _L, _P, _P, _L, _I, _I, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
@@ -176,6 +180,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
+        l.spk_vbx_ws_elems.restype = ctypes.c_longlong
         if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
             l.spk_stats_pool_row_form(0)
         _lib = l

@@ -1450,3 +1450,67 @@ def ahc_batch(scores, rec_off, min_clusters, threshold, ws_budget_bytes=1 << 31)
              hi - lo, stream(), nbytes=12.0 * need)
         lo = hi
     return labels, merges, cost, nm
+
+
+# ---- VBx resegmentation (csrc/diar.hip) -----------------------------------------------------------------------
+def vbx_threads():
+    """threads of the workgroup that runs the VB-HMM of one recording"""
+    return hip.lib().spk_vbx_threads()
+
+
+def vbx_max_states():
+    """the largest Smax spk_vbx_batch takes (one lane per state)"""
+    return hip.lib().spk_vbx_max_states()
+
+
+def vbx_ws_elems(rec_off, Smax, D):
+    """doubles of workspace spk_vbx_batch needs for the batch; a shape it refuses raises"""
+    import numpy as np
+    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
+    n = hip.lib().spk_vbx_ws_elems(ro.ctypes.data, ro.size - 1, int(Smax), int(D))
+    if n < 0:
+        hip.check(int(n), "spk_vbx_ws_elems")
+    return int(n)
+
+
+def vbx_batch(X, Phi, rec_off, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=40, epsilon=1e-6, elbo=None,
+              n_iters=None, ws_budget_bytes=1 << 31):
+    """X [Ntot][D], Phi [D], gamma [Ntot][Smax], pi [R][Smax]: float64 device tensors; rec_off [R + 1] and n_states [R]: host
+    integers.  Runs the VB-HMM of every recording (spk_vbx_batch; the rule: DESIGN.md section 6o) and updates gamma and pi in place.
+    -> (elbo float64 [R][max_iters], n_iters int32 [R]) on the device; recording r fills elbo[r][:n_iters[r]] and leaves the other
+    slots as they were (NaN in a tensor made here).  The batch is split into launches of consecutive recordings whose workspace fits
+    ws_budget_bytes (one recording always goes); a recording's result does not depend on the split."""
+    import numpy as np
+    Ntot, D = X.shape
+    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
+    ro, _ = diar_tables(ro, Ntot)
+    R = ro.size - 1
+    ns = np.ascontiguousarray(np.asarray(n_states), dtype=np.int32)
+    Smax = gamma.shape[1]
+    assert X.dtype == torch.float64 and Phi.dtype == torch.float64 and gamma.dtype == torch.float64 and pi.dtype == torch.float64
+    assert Phi.numel() == D and gamma.shape == (Ntot, Smax) and pi.shape == (R, Smax) and ns.shape == (R,)
+    assert X.is_contiguous() and gamma.is_contiguous() and pi.is_contiguous()      # (row slices of them go to the launches)
+    dev = X.device
+    if elbo is None:
+        elbo = torch.full((R, max(int(max_iters), 1)), float("nan"), device=dev, dtype=torch.float64)
+    if n_iters is None:
+        n_iters = torch.zeros(R, device=dev, dtype=torch.int32)
+    assert elbo.dtype == torch.float64 and elbo.shape == (R, max(int(max_iters), 1)) and elbo.is_contiguous()
+    assert n_iters.dtype == torch.int32 and n_iters.numel() == R and n_iters.is_contiguous()
+    per_row, per_rec = 8 * (3 + 2 * Smax), 8 * Smax * D
+    nsd = torch.from_numpy(ns).to(dev)
+    lo = 0
+    while lo < R:
+        hi = lo + 1
+        while hi < R and per_row * int(ro[hi + 1] - ro[lo]) + per_rec * (hi + 1 - lo) <= ws_budget_bytes:
+            hi += 1
+        sub = np.ascontiguousarray(ro[lo:hi + 1] - ro[lo])
+        need = vbx_ws_elems(sub, Smax, D)
+        ws = torch.empty(need, device=dev, dtype=torch.float64)
+        sd = torch.from_numpy(sub).to(dev)
+        r0, r1 = int(ro[lo]), int(ro[hi])
+        call("spk_vbx_batch", X[r0:r1].data_ptr(), ptr(Phi), sub.ctypes.data, ptr(sd), ns[lo:hi].ctypes.data, nsd[lo:hi].data_ptr(),
+             gamma[r0:r1].data_ptr(), pi[lo:hi].data_ptr(), float(Fa), float(Fb), float(loop_prob), int(max_iters), float(epsilon),
+             ptr(ws), need, elbo[lo:hi].data_ptr(), n_iters[lo:hi].data_ptr(), r1 - r0, D, hi - lo, Smax, stream(), nbytes=8.0 * need)
+        lo = hi
+    return elbo, n_iters

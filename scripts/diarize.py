@@ -2,7 +2,8 @@
 """Diarization from sliding-window embeddings: what Kaldi's callhome_diarization recipe runs behind extract_xvectors.sh -
 ivector-plda-scoring-dense (or cosine), agglomerative-cluster and make_rttm.py - on what `decode.py --window W --period P` wrote
 (DESIGN.md section 6n).  Writes <out-dir>/labels ('<window-key> <label>' lines), <out-dir>/rttm and, with --write-scores, one text
-matrix per recording in <out-dir>/scores.<recording>."""
+matrix per recording in <out-dir>/scores.<recording>.  With --vbx the clustering is the first pass of VBx resegmentation (section
+6o): labels and rttm then hold the VBx result and <out-dir>/labels.ahc the first pass."""
 import argparse
 import os
 import sys
@@ -36,6 +37,13 @@ def parse(argv=None):
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--rttm-channel", type=int, default=0)
     ap.add_argument("--write-scores", action="store_true")
+    ap.add_argument("--vbx", action="store_true", help="resegment with VBx, seeded by the clustering (needs --backend-score plda)")
+    ap.add_argument("--vbx-fa", type=float, default=0.3)
+    ap.add_argument("--vbx-fb", type=float, default=17.0)
+    ap.add_argument("--vbx-loop-prob", type=float, default=0.99)
+    ap.add_argument("--vbx-max-iters", type=int, default=40)
+    ap.add_argument("--vbx-epsilon", type=float, default=1e-6)
+    ap.add_argument("--vbx-init-smoothing", type=float, default=7.0)
     a = ap.parse_args(argv)
     if (a.threshold is None) == (a.reco2num_spk is None):
         ap.error("give exactly one of --threshold and --reco2num-spk")
@@ -43,6 +51,8 @@ def parse(argv=None):
         ap.error("--backend-score plda needs --plda and --transform")
     if a.backend_score == "cosine" and a.plda is not None:
         ap.error("--plda is only used with --backend-score plda")
+    if a.vbx and a.backend_score != "plda":
+        ap.error("--vbx needs --backend-score plda")
     return ap, a
 
 
@@ -62,6 +72,8 @@ if __name__ == "__main__":
                               reco2num_spk=diarize.read_reco2num_spk(a.reco2num_spk) if a.reco2num_spk else None,
                               recordings=[l.split()[0] for l in open(a.recordings) if l.strip()] if a.recordings else None,
                               backend=a.backend, channel=a.rttm_channel, return_scores=a.write_scores,
+                              vbx=dict(Fa=a.vbx_fa, Fb=a.vbx_fb, loop_prob=a.vbx_loop_prob, max_iters=a.vbx_max_iters,
+                                       epsilon=a.vbx_epsilon, init_smoothing=a.vbx_init_smoothing) if a.vbx else None,
                               mean=kaldi_io.read_vec_flt(a.mean) if a.mean else None,
                               transform=plda.read_transform(a.transform) if a.transform else None, **extra)
     except ValueError as e:
@@ -70,6 +82,10 @@ if __name__ == "__main__":
     with open(os.path.join(a.out_dir, "labels"), "w") as f:
         for k, l in zip(res["keys"], res["labels"]):
             f.write("%s %d\n" % (k, l))
+    if a.vbx:
+        with open(os.path.join(a.out_dir, "labels.ahc"), "w") as f:
+            for k, l in zip(res["keys"], res["ahc_labels"]):
+                f.write("%s %d\n" % (k, l))
     with open(os.path.join(a.out_dir, "rttm"), "w") as f:
         f.write("".join(l + "\n" for l in res["rttm"]))
     if a.write_scores:
