@@ -713,6 +713,58 @@ int spk_vbx_batch(const double* X /*[Ntot][D]*/, const double* Phi /*[D]*/, cons
                   double epsilon, double* ws, long long ws_elems, double* elbo /*[R][max_iters]*/, int* n_iters /*[R]*/, long long Ntot,
                   int D, int R, int Smax, void* stream);
 
+/* ---- per-recording PCA of the dense PLDA scores (csrc/pca.hip) ------------------------------------------------
+ * spk_syevj_batch: R symmetric matrices A [R][ld][ld] of orders orders[r] in [1, ld], ld <= spk_syevj_max_dim() (256); of each the
+ * upper triangle of the leading orders[r] x orders[r] part is read.  One workgroup per matrix runs a parallel-ordered cyclic
+ * two-sided Jacobi iteration (round-robin pairs, m / 2 rotations per round) with __syncthreads() alone, at most
+ * spk_syevj_max_sweeps() sweeps.  w [R][ld]: eigenvalues descending; vec [R][ld][ld]: row k = the unit eigenvector of w[k]; both 0 at
+ * and beyond orders[r].  sweeps [R]: sweeps run, the last, rotation-free one included; info [R]: 0 converged, 1 the bound was
+ * reached (a NaN in the matrix ends so, with NaN results).  The orders are given twice: a HOST array, checked, and its device copy.
+ * ws: spk_syevj_ws_elems(R, ld) doubles (padded orders up to 98 iterate in LDS, up to 140 the matrix does and the eigenvector table
+ * lies in ws, larger ones iterate in ws; the bits do not depend on it).
+ * Refused on the host (< 0, nothing written): R or ld out of range, an order outside [1, ld], a small workspace, a null pointer. */
+int spk_syevj_max_dim(void);
+int spk_syevj_max_sweeps(void);
+int spk_syevj_threads(void);
+long long spk_syevj_ws_elems(int R, int ld);
+int spk_syevj_batch(const double* A /*[R][ld][ld]*/, const int* orders /*host [R]*/, const int* orders_dev /*[R]*/, double* ws,
+                    long long ws_elems, double* w /*[R][ld]*/, double* vec /*[R][ld][ld]*/, int* sweeps /*[R]*/, int* info /*[R]*/,
+                    int R, int ld, void* stream);
+/* Steps 1-5 of section 6p for every recording of a batch (the layout of spk_score_dense: rec_off on the host, tab_dev on the device).
+ * Z [Ntot][L]: the float rows plda.project gives; W = Ti Ti^T and B = Ti diag(psi) Ti^T with Ti = T^-1 (host, once per call), T [L][L],
+ * psi [L] and mean [L]: the smoothed global model; 0 < E < 1.  Per recording: the covariance C of its rows, C = P diag(s) P^T,
+ * dim = min(k + 1, L, n - 1) with k the smallest k with (s_1 + ... + s_k) / tot > E, W_r = P_r W P_r^T = G G^T, T1 = G^-1,
+ * T1 B_r T1^T = U diag(psi_r) U^T, A_r = U^T T1 P_r, b_r = -A_r mean.  dim [R]; s [R][L] (floored at 0, descending); psi_r [R][L];
+ * A_r [R][L][L]; b_r [R][L]: rows and entries at or beyond dim[r] are 0.  A recording with n = 1 or tot <= 0 is skipped: dim = L,
+ * A_r = T, b_r = -T mean, psi_r = psi.  info [R]: 0, 1 (an eigendecomposition reached its sweep bound) or 2 (a Cholesky pivot was not
+ * positive); with info != 0 the recording's A_r, b_r and psi_r are 0.  The skip comes first: a skipped recording never factorises
+ * W_r, so it keeps info = 0 even where W is not positive definite.  L <= 256.  ws: spk_pca_plda_ws_elems() doubles (< 0 for a
+ * refused shape).  Refused on the host (< 0, nothing written): a bad rec_off, R > 65535, L outside [1, 256], E outside (0, 1) or NaN,
+ * a small workspace, a null device pointer. */
+long long spk_pca_plda_ws_elems(const long long* rec_off /*host [R+1]*/, int R, int L);
+int spk_pca_plda_batch(const float* Z /*[Ntot][L]*/, const long long* rec_off /*host [R+1]*/, const long long* tab_dev /*[3][R+1]*/,
+                       const double* W /*[L][L]*/, const double* B /*[L][L]*/, const double* T /*[L][L]*/, const double* psi /*[L]*/,
+                       const double* mean /*[L]*/, double E, double* ws, long long ws_elems, int* dim /*[R]*/, double* s /*[R][L]*/,
+                       double* psi_r /*[R][L]*/, double* A_r /*[R][L][L]*/, double* b_r /*[R][L]*/, int* info /*[R]*/, long long Ntot,
+                       int L, int R, void* stream);
+/* The score terms of every recording from its psi_r [R][L] (zero padded): g = psi / (2 psi + 1), k = psi^2 / ((psi + 1)(2 psi + 1)),
+ * qn = 1 / (psi + 1) (the length normalisation's weights), all [R][L], and K [R] = 0.5 sum_d (log(psi_d + 1) - log(1 + psi_d /
+ * (psi_d + 1))), one wave per recording, the sum in a fixed order.  psi = 0 gives g = k = 0, qn = 1 and adds exactly 0 to K.
+ * Refused on the host (< 0): R or L (1..512) out of range, a null device pointer. */
+int spk_pca_score_terms(const double* psi_r /*[R][L]*/, double* g /*[R][L]*/, double* k /*[R][L]*/, double* qn /*[R][L]*/,
+                        double* K /*[R]*/, int R, int L, void* stream);
+/* The per-recording forms of spk_affine_lennorm, spk_score_dense_q and spk_score_dense (the same kernel bodies): recording r's rows
+ * go through A [r], b [r], q [r] (NULL: ones) with Do = dim[r] in the scale, k [r], g [r] and K [r].  Rows are L wide everywhere; the
+ * zero padding beyond dim[r] contributes exactly 0. */
+int spk_affine_lennorm_rec(const float* X /*[Ntot][L]*/, const long long* rec_off /*host [R+1]*/, const long long* tab_dev,
+                           const double* A /*[R][L][L]*/, const double* b /*[R][L]*/, const double* q /*[R][L] or NULL*/,
+                           const int* dim /*[R]*/, int scale, double* Y /*[Ntot][L]*/, long long Ntot, int L, int R, void* stream);
+int spk_score_dense_q_rec(const double* U /*[Ntot][D]*/, const long long* rec_off /*host [R+1]*/, const long long* tab_dev,
+                          const double* k /*[R][D]*/, double scale, double* q /*[Ntot]*/, long long Ntot, int D, int R, void* stream);
+int spk_score_dense_rec(const double* U /*[Ntot][D]*/, const long long* rec_off /*host [R+1]*/, const long long* tab_dev,
+                        const double* q /*[Ntot]*/, const double* g /*[R][D]*/, const double* K /*[R]*/, float* out, long long Ntot,
+                        int D, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // Diarization back end on the device (DESIGN.md sections 6n and 6o): what Kaldi's callhome_diarization recipe runs behind the sliding-window
-// extraction - ivector-plda-scoring-dense (without its per-recording PCA) and agglomerative-cluster.
+// extraction - ivector-plda-scoring-dense (its per-recording PCA: csrc/pca.hip, section 6p) and agglomerative-cluster.
 //   spk_diar_tables   - host only: checks rec_off and derives the three offset tables both kernels read
 //   spk_score_dense_q - q_i = scale * sum_d k_d U_id^2 per row (one wave per row, fp64, a fixed lane order)
 //   spk_score_dense   - S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) for every pair of rows of one recording, all
@@ -27,7 +27,7 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // ---- offset tables --------------------------------------------------------------------------------------------------------------
 // tab [3][R + 1]: rec_off (rows), mat_off (elements of the n x n matrices laid end to end) and tile_off (16 x 16 tiles of the upper
 // triangles).  rec_off must start at 0, be strictly increasing and end at Ntot; sum n^2 must stay below 2^31.
-static int diar_tables(const char* who, const long long* rec_off, int R, long long Ntot, long long* tab) {
+int spk_diar_check(const char* who, const long long* rec_off, int R, long long Ntot, long long* tab) {
     SPK_REQUIRE(rec_off && R >= 1 && Ntot >= 1, "%s: bad arguments (R=%d, Ntot=%lld)", who, R, Ntot);
     SPK_REQUIRE(rec_off[0] == 0 && rec_off[R] == Ntot, "%s: rec_off must run from 0 to Ntot=%lld, got %lld .. %lld", who, Ntot,
                 rec_off[0], rec_off[R]);
@@ -55,15 +55,27 @@ static int diar_tables(const char* who, const long long* rec_off, int R, long lo
 
 extern "C" int spk_diar_tables(const long long* rec_off, int R, long long Ntot, long long* tab) {
     SPK_REQUIRE(tab, "spk_diar_tables: tab is missing");
-    return diar_tables("spk_diar_tables", rec_off, R, Ntot, tab);
+    return spk_diar_check("spk_diar_tables", rec_off, R, Ntot, tab);
 }
 
 // ---- q ----------------------------------------------------------------------------------------------------------------------------
+// REC (the per-recording forms of section 6p): k [R][D], row i takes the k of its recording (rec_off = the first row of tab)
+template <bool REC>
 __global__ __launch_bounds__(256) void dense_q_kernel(const double* __restrict__ U, const double* __restrict__ k, double scale,
-                                                      double* __restrict__ q, long long N, int D) {
+                                                      double* __restrict__ q, long long N, int D, const long long* __restrict__ rec_off,
+                                                      int R) {
     const int lane = threadIdx.x & 63;
     const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= N) return;
+    if (REC) {
+        int lo = 0, hi = R;                                       // the last r with rec_off[r] <= i
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rec_off[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        k += (size_t)lo * D;
+    }
     const double* u = U + (size_t)i * D;
     double s = 0.0;
     for (int d = lane; d < D; d += 64) s += k[d] * u[d] * u[d];
@@ -74,8 +86,21 @@ __global__ __launch_bounds__(256) void dense_q_kernel(const double* __restrict__
 
 extern "C" int spk_score_dense_q(const double* U, const double* k, double scale, double* q, long long N, int D, void* stream) {
     SPK_REQUIRE(U && k && q && N >= 1 && N < (1ll << 32) && D >= 1, "spk_score_dense_q: bad arguments");
-    hipLaunchKernelGGL(dense_q_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, k, scale, q, N, D);
+    hipLaunchKernelGGL(dense_q_kernel<false>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, k, scale, q, N, D,
+                       (const long long*)nullptr, 0);
     SPK_LAUNCH_CHECK("spk_score_dense_q");
+    return 0;
+}
+
+extern "C" int spk_score_dense_q_rec(const double* U, const long long* rec_off, const long long* tab_dev, const double* k, double scale,
+                                     double* q, long long Ntot, int D, int R, void* stream) {
+    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "spk_score_dense_q_rec: D=%d must lie in [1, %d]", D, DIAR_MAX_D);
+    const int rc = spk_diar_check("spk_score_dense_q_rec", rec_off, R, Ntot, nullptr);
+    if (rc) return rc;
+    SPK_REQUIRE(U && tab_dev && k && q, "spk_score_dense_q_rec: null device pointer");
+    hipLaunchKernelGGL(dense_q_kernel<true>, dim3((unsigned)((Ntot + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, k, scale, q, Ntot,
+                       D, tab_dev, R);
+    SPK_LAUNCH_CHECK("spk_score_dense_q_rec");
     return 0;
 }
 
@@ -83,9 +108,12 @@ extern "C" int spk_score_dense_q(const double* U, const double* k, double scale,
 // One wave per tile.  The sum over d may run in any order, so step s of lane group gq takes d = d0 + 4 gq + s: a lane reads four
 // consecutive values of its row.  D is padded to a multiple of 16 with zeros in registers.  A tile on the diagonal computes
 // (g u_i) u_j and (g u_j) u_i, whose roundings differ: only its entries with i <= j are kept, and every entry is stored twice.
+// REC: g [R][D] and Kr [R], the terms of the tile's recording.
+template <bool REC>
 __global__ __launch_bounds__(256) void score_dense_kernel(const double* __restrict__ U, const long long* __restrict__ tab,
                                                           const double* __restrict__ q, const double* __restrict__ g, double K,
-                                                          float* __restrict__ out, int D, int R, long long ntiles) {
+                                                          const double* __restrict__ Kr, float* __restrict__ out, int D, int R,
+                                                          long long ntiles) {
     const int lane = threadIdx.x & 63, c = lane & 15, gq = lane >> 4;
     const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= ntiles) return;                                   // wave-uniform
@@ -99,6 +127,10 @@ __global__ __launch_bounds__(256) void score_dense_kernel(const double* __restri
         else hi = mid;
     }
     const int r = lo;
+    if (REC) {
+        g += (size_t)r * D;
+        K = Kr[r];
+    }
     const long long row0 = rec_off[r];
     const int n = (int)(rec_off[r + 1] - row0), T = (n + 15) >> 4;
     int p = (int)(tile - tile_off[r]), ti = 0;
@@ -139,13 +171,28 @@ extern "C" int spk_score_dense(const double* U, const long long* rec_off, const 
     SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "spk_score_dense: D=%d must lie in [1, %d]", D, DIAR_MAX_D);
     std::vector<long long> tab;
     if (R >= 1) tab.resize(3 * ((size_t)R + 1));
-    const int rc = diar_tables("spk_score_dense", rec_off, R, Ntot, tab.data());
+    const int rc = spk_diar_check("spk_score_dense", rec_off, R, Ntot, tab.data());
     if (rc) return rc;
     SPK_REQUIRE(U && tab_dev && q && g && out, "spk_score_dense: null device pointer");
     const long long ntiles = tab[2 * (R + 1) + R];
-    hipLaunchKernelGGL(score_dense_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q, g, K,
-                       out, D, R, ntiles);
+    hipLaunchKernelGGL(score_dense_kernel<false>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q,
+                       g, K, (const double*)nullptr, out, D, R, ntiles);
     SPK_LAUNCH_CHECK("spk_score_dense");
+    return 0;
+}
+
+extern "C" int spk_score_dense_rec(const double* U, const long long* rec_off, const long long* tab_dev, const double* q, const double* g,
+                                   const double* K, float* out, long long Ntot, int D, int R, void* stream) {
+    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "spk_score_dense_rec: D=%d must lie in [1, %d]", D, DIAR_MAX_D);
+    std::vector<long long> tab;
+    if (R >= 1) tab.resize(3 * ((size_t)R + 1));
+    const int rc = spk_diar_check("spk_score_dense_rec", rec_off, R, Ntot, tab.data());
+    if (rc) return rc;
+    SPK_REQUIRE(U && tab_dev && q && g && K && out, "spk_score_dense_rec: null device pointer");
+    const long long ntiles = tab[2 * (R + 1) + R];
+    hipLaunchKernelGGL(score_dense_kernel<true>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q, g,
+                       0.0, K, out, D, R, ntiles);
+    SPK_LAUNCH_CHECK("spk_score_dense_rec");
     return 0;
 }
 
@@ -339,7 +386,7 @@ extern "C" int spk_ahc_batch(const float* S, const long long* rec_off, const lon
                              int* n_merges, long long Ntot, int R, void* stream) {
     std::vector<long long> tab;
     if (R >= 1) tab.resize(3 * ((size_t)R + 1));
-    const int rc = diar_tables("spk_ahc_batch", rec_off, R, Ntot, tab.data());
+    const int rc = spk_diar_check("spk_ahc_batch", rec_off, R, Ntot, tab.data());
     if (rc) return rc;
     for (int r = 0; r < R; ++r)
         SPK_REQUIRE(rec_off[r + 1] - rec_off[r] <= AHC_MAX_N, "spk_ahc_batch: recording %d has %lld windows, the cap is %d", r,
@@ -592,7 +639,7 @@ extern "C" int spk_vbx_max_states(void) { return VBX_MAX_S; }
 
 // what both host entry points check: rec_off (as spk_diar_tables does), D, Smax and the length of every recording
 static int vbx_shape(const char* who, const long long* rec_off, int R, long long Ntot, int Smax, int D) {
-    const int rc = diar_tables(who, rec_off, R, Ntot, nullptr);
+    const int rc = spk_diar_check(who, rec_off, R, Ntot, nullptr);
     if (rc) return rc;
     SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "%s: D=%d must lie in [1, %d]", who, D, DIAR_MAX_D);
     SPK_REQUIRE(Smax >= 1 && Smax <= VBX_MAX_S, "%s: Smax=%d must lie in [1, %d]", who, Smax, VBX_MAX_S);

@@ -163,13 +163,27 @@ extern "C" int spk_segment_sum_f64(const void* X, int x_f64, long long ld, const
 // One block per 32 rows; its four waves share the output columns (instruction tile t of 16 columns belongs to wave t & 3), so a
 // block owns whole rows and the row sums need one exchange through LDS.  The sum over k may run in any order, so step s of lane
 // group g takes k = k0 + 4 g + s: every lane reads four consecutive values of its row of X and of A.  A == NULL: the identity.
-template <typename TI, typename TO, int NT>
+// REC (spk_affine_lennorm_rec): block (x, r) takes rows 32 x .. of recording r, whose A, b and q lie at r Do Di
+// and r Do, and whose Do in the scale is dim[r]; the arithmetic is the same.
+template <typename TI, typename TO, int NT, bool REC = false>
 __global__ __launch_bounds__(256) void affine_kernel(const TI* __restrict__ X, long long ldx, const double* __restrict__ A,
                                                      const double* __restrict__ b, const double* __restrict__ q, TO* __restrict__ Y,
-                                                     long long N, int Di, int Do, int scale) {
+                                                     long long N, int Di, int Do, int scale, const long long* __restrict__ rec_off = nullptr,
+                                                     const int* __restrict__ dim = nullptr) {
     __shared__ double part[4][32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long long row0 = (long long)blockIdx.x * 32;
+    long long row0 = (long long)blockIdx.x * 32;
+    int Ds = Do;
+    if (REC) {
+        const int r = blockIdx.y;
+        row0 += rec_off[r];
+        N = rec_off[r + 1];
+        if (row0 >= N) return;                                 // block-uniform
+        A += (size_t)r * Do * Di;
+        b += (size_t)r * Do;
+        if (q) q += (size_t)r * Do;
+        Ds = dim[r];
+    }
     f64x4 acc[2][NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -240,7 +254,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const TI* __restrict__ X, l
             for (int r = 0; r < 4; ++r) {
                 const int rr = 16 * m + g + 4 * r;
                 const double tot = ((part[0][rr] + part[1][rr]) + part[2][rr]) + part[3][rr];
-                const double f = tot > 0.0 ? sqrt((double)Do / tot) : 1.0;
+                const double f = tot > 0.0 ? sqrt((double)Ds / tot) : 1.0;
 #pragma unroll
                 for (int n = 0; n < NT; ++n) acc[m][n][r] *= f;
             }
@@ -282,6 +296,31 @@ extern "C" int spk_affine_lennorm(const void* X, int x_f64, long long ldx, const
     else if (y_f64) affine_launch<float, double>(X, ldx, A, b, q, Y, N, Di, Do, scale, st);
     else affine_launch<float, float>(X, ldx, A, b, q, Y, N, Di, Do, scale, st);
     SPK_LAUNCH_CHECK("spk_affine_lennorm");
+    return 0;
+}
+
+// The per-recording form: X [Ntot][L] float rows, A [R][L][L], b [R][L], q [R][L] or NULL, dim [R]; rows and entries of A and b at or
+// beyond dim[r] are 0, so Y [Ntot][L] is 0 there.
+extern "C" int spk_affine_lennorm_rec(const float* X, const long long* rec_off, const long long* tab_dev, const double* A,
+                                      const double* b, const double* q, const int* dim, int scale, double* Y, long long Ntot, int L,
+                                      int R, void* stream) {
+    SPK_REQUIRE(L >= 1 && L <= 256, "spk_affine_lennorm_rec: L=%d must lie in [1, 256]", L);
+    const int rc = spk_diar_check("spk_affine_lennorm_rec", rec_off, R, Ntot, nullptr);
+    if (rc) return rc;
+    SPK_REQUIRE(R <= 65535, "spk_affine_lennorm_rec: R=%d must stay below 65536", R);
+    long long nmax = 0;
+    for (int r = 0; r < R; ++r) nmax = rec_off[r + 1] - rec_off[r] > nmax ? rec_off[r + 1] - rec_off[r] : nmax;
+    SPK_REQUIRE(X && tab_dev && A && b && dim && Y, "spk_affine_lennorm_rec: null device pointer");
+    const dim3 grid((unsigned)((nmax + 31) / 32), (unsigned)R);
+    const int need = spk_ceil_div(spk_ceil_div(L, 16), 4);
+#define AFF(NT)                                                                                                                     \
+    hipLaunchKernelGGL((affine_kernel<float, double, NT, true>), grid, dim3(256), 0, (hipStream_t)stream, X, (long long)L, A, b, q, Y, \
+                       Ntot, L, L, scale, tab_dev, dim)
+    if (need <= 1) AFF(1);
+    else if (need <= 2) AFF(2);
+    else AFF(4);
+#undef AFF
+    SPK_LAUNCH_CHECK("spk_affine_lennorm_rec");
     return 0;
 }
 

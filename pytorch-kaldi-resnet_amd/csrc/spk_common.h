@@ -53,6 +53,10 @@ enum {
 
 static inline int spk_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// csrc/diar.hip: the checks of spk_diar_tables under the caller's name (rec_off runs from 0 to Ntot and increases strictly, n < 2^16,
+// sum n^2 < 2^31); tab [3][R + 1] is filled when it is not NULL.  0, or -1 with spk_last_error set.
+int spk_diar_check(const char* who, const long long* rec_off, int R, long long Ntot, long long* tab);
+
 // ---- which compile-time instance a launch takes (host).  The launchers and the C ABI (spk_conv_variant_of /
 // spk_wgrad_variant_of) call the same pure functions: (tile, flag word, pointer pattern) -> the FL / VAR template argument, or -1
 // = the generic instance that reads everything from the argument block.

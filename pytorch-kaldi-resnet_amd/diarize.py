@@ -1,7 +1,9 @@
 """Diarization back end: the consumer of the sliding-window embeddings decode.py --window writes.  Per
-recording an all-pairs score matrix (Kaldi's ivector-plda-scoring-dense without its per-recording PCA, or cosine), average-linkage
-agglomerative clustering with a threshold or a known speaker count (agglomerative-cluster) and RTTM output (make_rttm.py).  No Kaldi
-binary is involved: the contract is the rule as section 6n states it, pinned by the independent restatement in tests/diar_ref.py.
+recording an all-pairs score matrix (Kaldi's ivector-plda-scoring-dense, or cosine), average-linkage agglomerative clustering with a
+threshold or a known speaker count (agglomerative-cluster) and RTTM output (make_rttm.py).  No Kaldi binary is involved: the contract
+is the rule as section 6n states it, pinned by the independent restatement in tests/diar_ref.py.  With target_energy the PLDA scores
+take ivector-plda-scoring-dense's per-recording PCA (--target-energy; section 6p, pinned by tests/pca_ref.py): the PLDA model is
+projected onto the leading principal directions of each recording's own rows and diagonalised again before that recording is scored.
 
 Two back ends.  `host` is numpy in fp64.  `hip` keeps the embeddings, the scores and the clustering on the GPU (csrc/diar.hip through
 ops.py, the projections through csrc/plda.hip).  A batch of recordings is one [Ntot][D] table with rec_off [R + 1]: recording r owns
@@ -81,13 +83,153 @@ def dense_inputs(emb, kind, mean=None, transform=None, plda=None, smoothing=0.0,
     return U, -0.5 * (k[None, :] * U * U).sum(axis=1), g, K
 
 
+# ---- per-recording PCA ---------------------------------------------------------------------------------------
+def _check_energy(target_energy, kind):
+    if kind != "plda":
+        raise ValueError("target_energy needs kind='plda' (the PCA adapts the PLDA model), got %r" % (kind,))
+    if not 0.0 < float(target_energy) < 1.0:
+        raise ValueError("target_energy must lie strictly between 0 and 1, got %r" % (target_energy,))
+    return float(target_energy)
+
+
+def pca_dim_rule(s, n, E):
+    """s [L] descending and >= 0, n rows -> the retained dimension of section 6p, or None where the recording skips the PCA"""
+    L = len(s)
+    cum = np.cumsum(s)                                              # (in index order)
+    tot = cum[-1]
+    if n == 1 or not tot > 0:
+        return None
+    over = np.nonzero(cum / tot > E)[0]
+    k = int(over[0]) + 1 if over.size else L
+    return min(k + 1, L, n - 1)
+
+
+def _pca_rec_host(z, W, B, model, E):
+    """steps 1-5 of section 6p for the rows z [n][L] of one recording -> (dim, s [L], psi_r [L], A_r [L][L], b_r [L], info), zero
+    padded at and beyond dim"""
+    mean, T, psi = model
+    n, L = z.shape
+    x = z.astype(np.float64)
+    mu = x.sum(axis=0) / n
+    C = np.triu((x.T @ x) / n - np.outer(mu, mu))
+    C = C + np.triu(C, 1).T
+    s, P = _plda._sym_eig_desc(C)
+    s = np.maximum(s, 0.0)
+    dim = pca_dim_rule(s, n, E)
+    if dim is None:
+        return L, s, psi.copy(), T.copy(), -(T @ mean), 0
+    Pr = P[:, :dim].T
+    Wr, Br = Pr @ W @ Pr.T, Pr @ B @ Pr.T
+    A, b, pr = np.zeros((L, L)), np.zeros(L), np.zeros(L)
+    try:
+        G = np.linalg.cholesky(np.tril(Wr) + np.tril(Wr, -1).T)
+    except np.linalg.LinAlgError:
+        return dim, s, pr, A, b, 2
+    T1 = np.linalg.inv(G)
+    p, U = _plda._sym_eig_desc(T1 @ Br @ T1.T)
+    pr[:dim] = np.maximum(p, 0.0)
+    A[:dim] = U.T @ T1 @ Pr
+    b[:dim] = -(A[:dim] @ mean)
+    return dim, s, pr, A, b, 0
+
+
+def pca_inputs(emb, rec_off, target_energy, mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True,
+               simple_length_normalization=False, backend="host", ws_budget_bytes=1 << 31):
+    """The operands of the dense score with the per-recording PCA of section 6p: the embeddings centred and projected as
+    dense_inputs(kind="plda") does, then pca_rows on the smoothed model"""
+    E = _check_energy(target_energy, "plda")
+    if plda is None or transform is None:
+        raise ValueError("plda scoring needs the transform and the Plda object")
+    emb = np.asarray(emb)
+    model = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))
+    z = _plda.project(_center(emb, mean), transform, backend)
+    return pca_rows(z, rec_off, model, E, normalize_length, simple_length_normalization, backend, ws_budget_bytes)
+
+
+def pca_rows(z, rec_off, model, target_energy, normalize_length=True, simple_length_normalization=False, backend="host",
+             ws_budget_bytes=1 << 31):
+    """z [Ntot][L] float32 (numpy, or on `hip` a device tensor): the rows plda.project gives; model = (mean, T, psi), already
+    smoothed -> dict(U [Ntot][L] fp64 (zeros beyond dim[r]), q [Ntot], g [R][L], K [R], dim [R], s [R][L], psi_r [R][L], info [R]);
+    U, q, g and K are device tensors on `hip`, the rest numpy.  A recording whose factorisation failed (info != 0) raises ValueError
+    naming it."""
+    E = _check_energy(target_energy, "plda")
+    ro, _ = _rec_off(rec_off, z.shape[0])
+    R = ro.size - 1
+    model = tuple(np.asarray(v, dtype=np.float64) for v in model)
+    m, T, psi = model
+    L = len(psi)
+    if z.shape[1] != L:
+        raise ValueError("the rows have %d dimensions, the PLDA model %d" % (z.shape[1], L))
+    Ti = np.linalg.inv(T)
+    W, B = Ti @ Ti.T, (Ti * psi[None, :]) @ Ti.T
+    if backend == "hip":
+        import torch
+        from . import ops
+        if L > ops.syevj_max_dim():
+            raise ValueError("target_energy on the hip back end takes at most %d PLDA dimensions, got %d" % (ops.syevj_max_dim(), L))
+        up = _plda._up
+        z = (z if torch.is_tensor(z) else up(z, np.float32)).contiguous()
+        dim_d, s_d, psi_d, A_d, b_d, info_d = ops.pca_plda_batch(z, ro, up(W), up(B), up(T), up(psi), up(m), E, ws_budget_bytes)
+        g, k, qn, K = ops.pca_score_terms(psi_d)
+        plain = simple_length_normalization or not normalize_length
+        U = ops.affine_lennorm_rec(z, ro, A_d, b_d, None if plain else qn, dim_d, normalize_length)
+        q = ops.score_dense_q_rec(U, ro, k, -0.5)
+        # (the one synchronisation of the chain, after its kernels are queued; a recording in error has zeros in A_r, b_r and psi_r)
+        dim, info, s, psi_r = dim_d.cpu().numpy(), info_d.cpu().numpy(), s_d.cpu().numpy(), psi_d.cpu().numpy()
+    else:
+        assert backend == "host", backend
+        z = np.asarray(z, dtype=np.float32)
+        dim, info = np.empty(R, dtype=np.int32), np.empty(R, dtype=np.int32)
+        s, psi_r, A_r, b_r = np.zeros((R, L)), np.zeros((R, L)), np.zeros((R, L, L)), np.zeros((R, L))
+        for r in range(R):
+            dim[r], s[r], psi_r[r], A_r[r], b_r[r], info[r] = _pca_rec_host(z[ro[r]:ro[r + 1]], W, B, model, E)
+    bad = np.nonzero(info)[0]
+    if bad.size:
+        raise ValueError("the per-recording PCA failed for recording %d (info = %d: %s)" % (
+            bad[0], info[bad[0]], "a Cholesky pivot was not positive" if info[bad[0]] == 2 else "an eigendecomposition did not converge"))
+    if backend != "hip":
+        terms = [plda_dense_terms(psi_r[r]) for r in range(R)]
+        g, k, K = np.stack([t[0] for t in terms]), np.stack([t[1] for t in terms]), np.array([t[2] for t in terms])
+        qn = None if (simple_length_normalization or not normalize_length) else 1.0 / (psi_r + 1.0)
+        U = np.zeros((z.shape[0], L))
+        for r in range(R):
+            u = z[ro[r]:ro[r + 1]].astype(np.float64) @ A_r[r].T + b_r[r]
+            if normalize_length:
+                ss = (u * u * (1.0 if qn is None else qn[r][None, :])).sum(axis=1)
+                u = u * np.where(ss > 0, np.sqrt(dim[r] / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
+            U[ro[r]:ro[r + 1]] = u
+        q = np.concatenate([-0.5 * (k[r][None, :] * U[ro[r]:ro[r + 1]] ** 2).sum(axis=1) for r in range(R)])
+    return {"U": U, "q": q, "g": g, "K": K, "dim": dim, "s": s, "psi_r": psi_r, "info": info}
+
+
+def _score_rows_rec(p, ro, mat_off, backend, return_device):
+    """_score_rows with the terms of every recording's own model (pca_inputs' dict)"""
+    if backend == "hip":
+        from . import ops
+        out, mo = ops.score_dense_rec(p["U"], ro, p["q"], p["g"], p["K"])
+        assert (mo == mat_off).all()
+        return out if return_device else out.cpu().numpy()
+    out = np.empty(int(mat_off[-1]), dtype=np.float32)
+    for r in range(ro.size - 1):
+        u, qq = p["U"][ro[r]:ro[r + 1]], p["q"][ro[r]:ro[r + 1]]
+        s = np.triu(((u * p["g"][r][None, :]) @ u.T + qq[:, None]) + qq[None, :] + p["K"][r])
+        s = s + np.triu(s, 1).T
+        out[mat_off[r]:mat_off[r + 1]] = s.astype(np.float32).ravel()
+    return out
+
+
 def score_dense(emb, rec_off, kind="cosine", mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True,
-                simple_length_normalization=False, backend="host", return_device=False):
+                simple_length_normalization=False, backend="host", return_device=False, target_energy=None):
     """emb [Ntot][D] (the rows of all recordings, recording after recording), rec_off [R + 1] -> (scores float32 [sum n^2], mat_off
     int64 [R + 1]): recording r's matrix S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) at scores[mat_off[r]:], symmetric
-    bit for bit.  `hip` with return_device: the scores stay on the GPU (what cluster(..., backend="hip") takes)."""
+    bit for bit.  `hip` with return_device: the scores stay on the GPU (what cluster(..., backend="hip") takes).  target_energy (a
+    number in (0, 1), kind plda): every recording is scored with its own PCA-adapted model (section 6p)."""
     emb = np.asarray(emb)
     ro, mat_off = _rec_off(rec_off, emb.shape[0])
+    if target_energy is not None:
+        _check_energy(target_energy, kind)
+        p = pca_inputs(emb, ro, target_energy, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
+        return _score_rows_rec(p, ro, mat_off, backend, return_device), mat_off
     U, q, g, K = dense_inputs(emb, kind, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
     return _score_rows(U, q, g, K, ro, mat_off, backend, return_device), mat_off
 
@@ -483,15 +625,19 @@ def read_reco2num_spk(path):
 
 
 def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=None, recordings=None, backend="host", channel=0,
-            return_scores=False, vbx=None, **score_args):
+            return_scores=False, vbx=None, target_energy=None, **score_args):
     """embeddings: key -> vector (scoring.read_embeddings), segments: read_segments' list; exactly one of threshold and
     reco2num_spk (recording -> speakers).  -> dict(recordings, rec_off, mat_off, keys (batch order), labels, scores (numpy with
     return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges).
     vbx: None, or a dict with any of Fa, Fb, loop_prob, max_iters, epsilon, init_smoothing (VBX_DEFAULTS): the clustering's labels
     then seed VBx (section 6o; kind must be plda), `labels` and `rttm` hold its result and the dict gains ahc_labels, vbx_elbo,
-    vbx_n_iters and vbx_pi; on `hip` the rows stay on the device between scoring and VBx."""
+    vbx_n_iters and vbx_pi; on `hip` the rows stay on the device between scoring and VBx.  target_energy: None, or the energy in
+    (0, 1) of the per-recording PCA (section 6p; kind must be plda): the clustering then runs on the adapted scores and the dict gains
+    pca_dim (one int per recording); VBx keeps the global rows and the global psi."""
     if (threshold is None) == (reco2num_spk is None):
         raise ValueError("give exactly one of threshold and reco2num_spk")
+    if target_energy is not None:
+        _check_energy(target_energy, kind)
     if vbx is not None:
         if kind != "plda":
             raise ValueError("vbx needs kind='plda' (its rows and variances are the PLDA's), got %r" % (kind,))
@@ -515,7 +661,15 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
         emb = embeddings.mat[[embeddings.index[k] for k in keys]]
     else:
         emb = np.stack([np.asarray(embeddings[k], dtype=np.float64) for k in keys])
-    if vbx is None:
+    extra = {}
+    if target_energy is not None:
+        ro, mat_off = _rec_off(rec_off, emb.shape[0])
+        p = pca_inputs(emb, ro, target_energy, backend=backend, **score_args)
+        scores = _score_rows_rec(p, ro, mat_off, backend, backend == "hip")
+        extra["pca_dim"] = [int(d) for d in p["dim"]]
+        if vbx is not None:
+            U = dense_inputs(emb, kind, backend=backend, **score_args)[0]
+    elif vbx is None:
         scores, mat_off = score_dense(emb, rec_off, kind, backend=backend, return_device=(backend == "hip"), **score_args)
     else:
         ro, mat_off = _rec_off(rec_off, emb.shape[0])
@@ -523,11 +677,10 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
         scores = _score_rows(U, q, g, K, ro, mat_off, backend, backend == "hip")
     labels, merges, cost, nm = cluster(scores, rec_off, threshold, num, backend)
     segs = [segments[i] for i in flat]
-    extra = {}
     if vbx is not None:
         psi = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in score_args["plda"]), float(score_args.get("smoothing", 0.0)))[2]
         res = _vbx(U, psi, rec_off, init_labels=labels, backend=backend, **vbx)
-        extra = {"ahc_labels": labels, "vbx_elbo": res["elbo"], "vbx_n_iters": res["n_iters"], "vbx_pi": res["pi"]}
+        extra.update({"ahc_labels": labels, "vbx_elbo": res["elbo"], "vbx_n_iters": res["n_iters"], "vbx_pi": res["pi"]})
         labels = res["labels"]
     out = {"recordings": order, "rec_off": rec_off, "mat_off": mat_off, "keys": keys, "labels": labels,
            "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),

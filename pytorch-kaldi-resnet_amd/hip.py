@@ -135,6 +135,17 @@ _SIGS = {
     "spk_vbx_max_states": [],
     "spk_vbx_ws_elems": [_P, _I, _I, _I],               # host only; returns long long (restype set in lib())
     "spk_vbx_batch": [_P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I, _D, _P, _L, _P, _P, _L, _I, _I, _I, _P],
+    "spk_syevj_max_dim": [],
+    "spk_syevj_max_sweeps": [],
+    "spk_syevj_threads": [],
+    "spk_syevj_ws_elems": [_I, _I],                     # host only; returns long long (restype set in lib())
+    "spk_syevj_batch": [_P, _P, _P, _P, _L, _P, _P, _P, _P, _I, _I, _P],
+    "spk_pca_plda_ws_elems": [_P, _I, _I],              # host only; returns long long
+    "spk_pca_plda_batch": [_P] * 8 + [_D, _P, _L] + [_P] * 6 + [_L, _I, _I, _P],
+    "spk_pca_score_terms": [_P] * 5 + [_I, _I, _P],
+    "spk_affine_lennorm_rec": [_P] * 7 + [_I, _P, _L, _I, _I, _P],
+    "spk_score_dense_q_rec": [_P, _P, _P, _P, _D, _P, _L, _I, _I, _P],
+    "spk_score_dense_rec": [_P] * 7 + [_L, _I, _I, _P],
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
@@ -181,6 +192,8 @@ def lib():
             fn.argtypes = sig
             fn.restype = ctypes.c_int
         l.spk_vbx_ws_elems.restype = ctypes.c_longlong
+        l.spk_syevj_ws_elems.restype = ctypes.c_longlong
+        l.spk_pca_plda_ws_elems.restype = ctypes.c_longlong
         if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
             l.spk_stats_pool_row_form(0)
         _lib = l

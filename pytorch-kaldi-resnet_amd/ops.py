@@ -1514,3 +1514,142 @@ def vbx_batch(X, Phi, rec_off, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0
              ptr(ws), need, elbo[lo:hi].data_ptr(), n_iters[lo:hi].data_ptr(), r1 - r0, D, hi - lo, Smax, stream(), nbytes=8.0 * need)
         lo = hi
     return elbo, n_iters
+
+
+# ---- per-recording PCA of the dense PLDA scores (csrc/pca.hip) ------------------------------------------------
+def syevj_max_dim():
+    """the largest order spk_syevj_batch takes"""
+    return hip.lib().spk_syevj_max_dim()
+
+
+def syevj_max_sweeps():
+    """the sweep bound of the Jacobi iteration"""
+    return hip.lib().spk_syevj_max_sweeps()
+
+
+def syevj_batch(A, orders=None):
+    """A [R][ld][ld] float64 (device), symmetric (the upper triangles are read); orders: host integers [R] in [1, ld] (default ld) ->
+    (w [R][ld] descending, vec [R][ld][ld] with row k the eigenvector of w[k], sweeps int32 [R], info int32 [R]) on the device
+    (spk_syevj_batch); zeros at and beyond a matrix's order."""
+    import numpy as np
+    R, ld = A.shape[0], A.shape[1]
+    assert A.dtype == torch.float64 and A.dim() == 3 and A.shape[2] == ld and A.is_contiguous()
+    od = np.full(R, ld, dtype=np.int32) if orders is None else np.ascontiguousarray(np.asarray(orders), dtype=np.int32)
+    assert od.shape == (R,)
+    need = hip.lib().spk_syevj_ws_elems(R, ld)
+    if need < 0:
+        raise ValueError("syevj_batch: %s" % hip.lib().spk_last_error().decode())
+    dev = A.device
+    ws = torch.empty(int(need), device=dev, dtype=torch.float64)
+    w = torch.empty(R, ld, device=dev, dtype=torch.float64)
+    vec = torch.empty(R, ld, ld, device=dev, dtype=torch.float64)
+    sweeps = torch.empty(R, device=dev, dtype=torch.int32)
+    info = torch.empty(R, device=dev, dtype=torch.int32)
+    odd = torch.from_numpy(od).to(dev)
+    call("spk_syevj_batch", ptr(A), od.ctypes.data, ptr(odd), ptr(ws), int(need), ptr(w), ptr(vec), ptr(sweeps), ptr(info), R, ld,
+         stream(), nbytes=16.0 * R * ld * ld)
+    return w, vec, sweeps, info
+
+
+def pca_plda_ws_elems(rec_off, L):
+    """doubles of workspace spk_pca_plda_batch needs for the batch; a shape it refuses raises"""
+    import numpy as np
+    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
+    n = hip.lib().spk_pca_plda_ws_elems(ro.ctypes.data, ro.size - 1, int(L))
+    if n < 0:
+        hip.check(int(n), "spk_pca_plda_ws_elems")
+    return int(n)
+
+
+def pca_plda_batch(Z, rec_off, W, B, T, psi, mean, E, ws_budget_bytes=1 << 31):
+    """Z [Ntot][L] float32 (device): the rows of plda.project; rec_off: host integers [R + 1]; W, B, T [L][L], psi and mean [L]
+    float64 (device) -> (dim int32 [R], s [R][L], psi_r [R][L], A_r [R][L][L], b_r [R][L], info int32 [R]) on the device: steps 1-5
+    of section 6p (spk_pca_plda_batch).  The batch is split into launches of consecutive recordings whose workspace fits
+    ws_budget_bytes (one recording always goes); a recording's result does not depend on the split."""
+    import numpy as np
+    Ntot, L = Z.shape
+    ro, _ = diar_tables(rec_off, Ntot)
+    R = ro.size - 1
+    if L > syevj_max_dim():
+        raise ValueError("pca_plda_batch: L=%d, the hip back end takes at most %d dimensions" % (L, syevj_max_dim()))
+    assert Z.dtype == torch.float32 and Z.is_contiguous()
+    for t, n in ((W, L * L), (B, L * L), (T, L * L), (psi, L), (mean, L)):
+        assert t.dtype == torch.float64 and t.numel() == n and t.is_contiguous()
+    dev = Z.device
+    dim = torch.empty(R, device=dev, dtype=torch.int32)
+    info = torch.empty(R, device=dev, dtype=torch.int32)
+    s = torch.empty(R, L, device=dev, dtype=torch.float64)
+    psi_r = torch.empty(R, L, device=dev, dtype=torch.float64)
+    A_r = torch.empty(R, L, L, device=dev, dtype=torch.float64)
+    b_r = torch.empty(R, L, device=dev, dtype=torch.float64)
+    per = 8 * (pca_plda_ws_elems(np.array([0, 1]), L) - 1)
+    lo = 0
+    while lo < R:
+        hi = min(R, lo + max(1, int(ws_budget_bytes // per)), lo + 65535)
+        sub, stab = diar_tables(ro[lo:hi + 1] - ro[lo], int(ro[hi] - ro[lo]))
+        need = pca_plda_ws_elems(sub, L)
+        ws = torch.empty(need, device=dev, dtype=torch.float64)
+        td = torch.from_numpy(stab).to(dev)
+        r0, r1 = int(ro[lo]), int(ro[hi])
+        call("spk_pca_plda_batch", Z[r0:r1].data_ptr(), sub.ctypes.data, ptr(td), ptr(W), ptr(B), ptr(T), ptr(psi), ptr(mean), float(E),
+             ptr(ws), need, dim[lo:hi].data_ptr(), s[lo:hi].data_ptr(), psi_r[lo:hi].data_ptr(), A_r[lo:hi].data_ptr(),
+             b_r[lo:hi].data_ptr(), info[lo:hi].data_ptr(), r1 - r0, L, hi - lo, stream(), nbytes=8.0 * need)
+        lo = hi
+    return dim, s, psi_r, A_r, b_r, info
+
+
+def pca_score_terms(psi_r):
+    """psi_r [R][L] float64 (device, zero padded) -> (g [R][L], k [R][L], qn [R][L] = 1 / (psi_r + 1), K [R]) on the device: the dense
+    score's terms of every recording (diarize.plda_dense_terms) and the length normalisation's weights (spk_pca_score_terms)"""
+    R, L = psi_r.shape
+    assert psi_r.dtype == torch.float64 and psi_r.is_contiguous()
+    g, k, qn = torch.empty_like(psi_r), torch.empty_like(psi_r), torch.empty_like(psi_r)
+    K = torch.empty(R, device=psi_r.device, dtype=torch.float64)
+    call("spk_pca_score_terms", ptr(psi_r), ptr(g), ptr(k), ptr(qn), ptr(K), R, L, stream())
+    return g, k, qn, K
+
+
+def affine_lennorm_rec(Z, rec_off, A_r, b_r, q_r, dim, scale):
+    """Z [Ntot][L] float32, A_r [R][L][L], b_r [R][L], q_r [R][L] or None (ones), dim int32 [R] (device) -> U [Ntot][L] float64:
+    recording r's rows through its own map, Do = dim[r] in the scale, zeros beyond dim[r] (spk_affine_lennorm_rec)"""
+    Ntot, L = Z.shape
+    ro, tab = diar_tables(rec_off, Ntot)
+    R = ro.size - 1
+    assert Z.dtype == torch.float32 and Z.is_contiguous() and dim.dtype == torch.int32 and dim.numel() == R
+    assert A_r.dtype == torch.float64 and A_r.numel() == R * L * L and b_r.dtype == torch.float64 and b_r.numel() == R * L
+    assert q_r is None or (q_r.dtype == torch.float64 and q_r.numel() == R * L)
+    U = torch.empty(Ntot, L, device=Z.device, dtype=torch.float64)
+    td = torch.from_numpy(tab).to(Z.device)
+    call("spk_affine_lennorm_rec", ptr(Z), ro.ctypes.data, ptr(td), ptr(A_r), ptr(b_r), ptr(q_r), ptr(dim), 1 if scale else 0, ptr(U),
+         Ntot, L, R, stream(), flops=2.0 * Ntot * L * L)
+    return U
+
+
+def score_dense_q_rec(U, rec_off, k, scale):
+    """U [Ntot][D], k [R][D] float64 -> q [Ntot], q_i = scale sum_d k[r(i)][d] U_id^2 (spk_score_dense_q_rec)"""
+    Ntot, D = U.shape
+    ro, tab = diar_tables(rec_off, Ntot)
+    R = ro.size - 1
+    assert U.dtype == torch.float64 and k.dtype == torch.float64 and k.numel() == R * D and k.is_contiguous()
+    q = torch.empty(Ntot, device=U.device, dtype=torch.float64)
+    td = torch.from_numpy(tab).to(U.device)
+    call("spk_score_dense_q_rec", ptr(U), ro.ctypes.data, ptr(td), ptr(k), float(scale), ptr(q), Ntot, D, R, stream(),
+         nbytes=8.0 * Ntot * D)
+    return q
+
+
+def score_dense_rec(U, rec_off, q, g, K, out=None):
+    """score_dense with g [R][D] and K [R] (device, float64) per recording (spk_score_dense_rec)"""
+    Ntot, D = U.shape
+    ro, tab = diar_tables(rec_off, Ntot)
+    R = ro.size - 1
+    assert U.dtype == torch.float64 and q.dtype == torch.float64 and g.dtype == torch.float64 and K.dtype == torch.float64
+    assert q.numel() == Ntot and g.numel() == R * D and K.numel() == R and g.is_contiguous()
+    total = int(tab[1, R])
+    if out is None:
+        out = torch.empty(total, device=U.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() >= total
+    td = torch.from_numpy(tab).to(U.device)
+    call("spk_score_dense_rec", ptr(U), ro.ctypes.data, ptr(td), ptr(q), ptr(g), ptr(K), ptr(out), Ntot, D, R, stream(),
+         flops=1.0 * total * D, nbytes=4.0 * total + 8.0 * Ntot * D)
+    return out, tab[1].copy()

@@ -3,7 +3,8 @@
 ivector-plda-scoring-dense (or cosine), agglomerative-cluster and make_rttm.py - on what `decode.py --window W --period P` wrote
 (DESIGN.md section 6n).  Writes <out-dir>/labels ('<window-key> <label>' lines), <out-dir>/rttm and, with --write-scores, one text
 matrix per recording in <out-dir>/scores.<recording>.  With --vbx the clustering is the first pass of VBx resegmentation (section
-6o): labels and rttm then hold the VBx result and <out-dir>/labels.ahc the first pass."""
+6o): labels and rttm then hold the VBx result and <out-dir>/labels.ahc the first pass.  With --target-energy E the PLDA scores take
+ivector-plda-scoring-dense's per-recording PCA (section 6p) and <out-dir>/pca_dim lists '<recording> <dim>'; VBx is unaffected."""
 import argparse
 import os
 import sys
@@ -37,6 +38,9 @@ def parse(argv=None):
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--rttm-channel", type=int, default=0)
     ap.add_argument("--write-scores", action="store_true")
+    ap.add_argument("--target-energy", type=float, default=None,
+                    help="per-recording PCA of ivector-plda-scoring-dense: keep this share of each recording's energy, in (0, 1) "
+                         "(needs --backend-score plda; also writes <out-dir>/pca_dim)")
     ap.add_argument("--vbx", action="store_true", help="resegment with VBx, seeded by the clustering (needs --backend-score plda)")
     ap.add_argument("--vbx-fa", type=float, default=0.3)
     ap.add_argument("--vbx-fb", type=float, default=17.0)
@@ -53,6 +57,11 @@ def parse(argv=None):
         ap.error("--plda is only used with --backend-score plda")
     if a.vbx and a.backend_score != "plda":
         ap.error("--vbx needs --backend-score plda")
+    if a.target_energy is not None:
+        if a.backend_score != "plda":
+            ap.error("--target-energy needs --backend-score plda")
+        if not 0.0 < a.target_energy < 1.0:
+            ap.error("--target-energy must lie strictly between 0 and 1, got %r" % a.target_energy)
     return ap, a
 
 
@@ -74,7 +83,7 @@ if __name__ == "__main__":
                               backend=a.backend, channel=a.rttm_channel, return_scores=a.write_scores,
                               vbx=dict(Fa=a.vbx_fa, Fb=a.vbx_fb, loop_prob=a.vbx_loop_prob, max_iters=a.vbx_max_iters,
                                        epsilon=a.vbx_epsilon, init_smoothing=a.vbx_init_smoothing) if a.vbx else None,
-                              mean=kaldi_io.read_vec_flt(a.mean) if a.mean else None,
+                              target_energy=a.target_energy, mean=kaldi_io.read_vec_flt(a.mean) if a.mean else None,
                               transform=plda.read_transform(a.transform) if a.transform else None, **extra)
     except ValueError as e:
         ap.error(str(e))
@@ -86,6 +95,10 @@ if __name__ == "__main__":
         with open(os.path.join(a.out_dir, "labels.ahc"), "w") as f:
             for k, l in zip(res["keys"], res["ahc_labels"]):
                 f.write("%s %d\n" % (k, l))
+    if a.target_energy is not None:
+        with open(os.path.join(a.out_dir, "pca_dim"), "w") as f:
+            for reco, d in zip(res["recordings"], res["pca_dim"]):
+                f.write("%s %d\n" % (reco, d))
     with open(os.path.join(a.out_dir, "rttm"), "w") as f:
         f.write("".join(l + "\n" for l in res["rttm"]))
     if a.write_scores:
