@@ -166,34 +166,31 @@ __global__ __launch_bounds__(256) void score_dense_kernel(const double* __restri
     }
 }
 
-extern "C" int spk_score_dense(const double* U, const long long* rec_off, const long long* tab_dev, const double* q, const double* g,
-                               double K, float* out, long long Ntot, int D, int R, void* stream) {
-    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "spk_score_dense: D=%d must lie in [1, %d]", D, DIAR_MAX_D);
+// the host side of both entries: K is read where !REC, Kr where REC
+template <bool REC>
+static int score_dense_launch(const char* who, const double* U, const long long* rec_off, const long long* tab_dev, const double* q,
+                              const double* g, double K, const double* Kr, float* out, long long Ntot, int D, int R, void* stream) {
+    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "%s: D=%d must lie in [1, %d]", who, D, DIAR_MAX_D);
     std::vector<long long> tab;
     if (R >= 1) tab.resize(3 * ((size_t)R + 1));
-    const int rc = spk_diar_check("spk_score_dense", rec_off, R, Ntot, tab.data());
+    const int rc = spk_diar_check(who, rec_off, R, Ntot, tab.data());
     if (rc) return rc;
-    SPK_REQUIRE(U && tab_dev && q && g && out, "spk_score_dense: null device pointer");
+    SPK_REQUIRE(U && tab_dev && q && g && (!REC || Kr) && out, "%s: null device pointer", who);
     const long long ntiles = tab[2 * (R + 1) + R];
-    hipLaunchKernelGGL(score_dense_kernel<false>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q,
-                       g, K, (const double*)nullptr, out, D, R, ntiles);
-    SPK_LAUNCH_CHECK("spk_score_dense");
+    hipLaunchKernelGGL(score_dense_kernel<REC>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q, g,
+                       K, Kr, out, D, R, ntiles);
+    SPK_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int spk_score_dense(const double* U, const long long* rec_off, const long long* tab_dev, const double* q, const double* g,
+                               double K, float* out, long long Ntot, int D, int R, void* stream) {
+    return score_dense_launch<false>("spk_score_dense", U, rec_off, tab_dev, q, g, K, nullptr, out, Ntot, D, R, stream);
 }
 
 extern "C" int spk_score_dense_rec(const double* U, const long long* rec_off, const long long* tab_dev, const double* q, const double* g,
                                    const double* K, float* out, long long Ntot, int D, int R, void* stream) {
-    SPK_REQUIRE(D >= 1 && D <= DIAR_MAX_D, "spk_score_dense_rec: D=%d must lie in [1, %d]", D, DIAR_MAX_D);
-    std::vector<long long> tab;
-    if (R >= 1) tab.resize(3 * ((size_t)R + 1));
-    const int rc = spk_diar_check("spk_score_dense_rec", rec_off, R, Ntot, tab.data());
-    if (rc) return rc;
-    SPK_REQUIRE(U && tab_dev && q && g && K && out, "spk_score_dense_rec: null device pointer");
-    const long long ntiles = tab[2 * (R + 1) + R];
-    hipLaunchKernelGGL(score_dense_kernel<true>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, U, tab_dev, q, g,
-                       0.0, K, out, D, R, ntiles);
-    SPK_LAUNCH_CHECK("spk_score_dense_rec");
-    return 0;
+    return score_dense_launch<true>("spk_score_dense_rec", U, rec_off, tab_dev, q, g, 0.0, K, out, Ntot, D, R, stream);
 }
 
 // ---- clustering -------------------------------------------------------------------------------------------------------------------

@@ -7,24 +7,12 @@ projected onto the leading principal directions of each recording's own rows and
 
 Two back ends.  `host` is numpy in fp64.  `hip` keeps the embeddings, the scores and the clustering on the GPU (csrc/diar.hip through
 ops.py, the projections through csrc/plda.hip).  A batch of recordings is one [Ntot][D] table with rec_off [R + 1]: recording r owns
-the rows rec_off[r] .. rec_off[r + 1] - 1, and its n x n score matrix lies at mat_off[r] = sum of the earlier n^2 in one flat array."""
+the rows rec_off[r] .. rec_off[r + 1] - 1, and its n x n score matrix lies at mat_off[r] = sum of the earlier n^2 in one flat array.
+pca_rows, cluster, vbx and vbx_init take that layout as a RecBatch (recbatch.py) in place of rec_off; diarize() builds one per call."""
 import numpy as np
 
 from . import plda as _plda
-
-
-def _rec_off(rec_off, Ntot):
-    ro = np.asarray(rec_off)
-    if ro.dtype.kind not in "iu" or ro.ndim != 1 or ro.size < 2:
-        raise ValueError("rec_off must be a one-dimensional integer array of at least two entries")
-    ro = ro.astype(np.int64)
-    if ro[0] != 0 or ro[-1] != Ntot or (np.diff(ro) < 1).any():
-        raise ValueError("rec_off must start at 0, increase strictly (no empty recording) and end at %d" % Ntot)
-    n = np.diff(ro)
-    mat_off = np.concatenate([[0], np.cumsum(n * n)]).astype(np.int64)
-    if mat_off[-1] >= 1 << 31:
-        raise ValueError("the score matrices of one batch must hold fewer than 2^31 entries, got %d" % mat_off[-1])
-    return ro, mat_off
+from .recbatch import RecBatch
 
 
 def plda_dense_terms(psi):
@@ -51,29 +39,38 @@ def dense_inputs(emb, kind, mean=None, transform=None, plda=None, smoothing=0.0,
     """-> (U [Ntot][D'] fp64, q [Ntot] fp64, g [D'] fp64, K): the operands of the dense score, numpy on `host`, device tensors on
     `hip`.  cosine: rows of norm sqrt(D) (ivector-normalize-length's scaling, spk_affine_lennorm) with g = 1 / D - the cosine of the
     centred embeddings; q = 0 and K = 0.  plda: the rows Plda::TransformIvector gives for one utterance per side."""
+    if kind == "plda":
+        z, model = _plda_z(emb, mean, transform, plda, smoothing, backend)
+        return _plda_rows(z, model, normalize_length, simple_length_normalization, backend)
+    if kind != "cosine":
+        raise ValueError("kind must be cosine or plda, got %r" % (kind,))
     x0 = _center(emb, mean)
     N = x0.shape[0]
-    if kind == "cosine":
-        z = x0 if transform is None else _plda.project(x0, transform, backend)
-        D = z.shape[1]
-        if backend == "hip":
-            import torch
-            from . import ops
-            U = ops.affine_lennorm(z if torch.is_tensor(z) else _plda._up(z), None, None, None, True, torch.float64)
-            return U, torch.zeros(N, device=U.device, dtype=torch.float64), _plda._up(np.full(D, 1.0 / D)), 0.0
-        assert backend == "host", backend
-        y = z.astype(np.float64)
-        ss = (y * y).sum(axis=1)
-        U = y * np.where(ss > 0, np.sqrt(D / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
-        return U, np.zeros(N), np.full(D, 1.0 / D), 0.0
-    if kind != "plda":
-        raise ValueError("kind must be cosine or plda, got %r" % (kind,))
+    z = x0 if transform is None else _plda.project(x0, transform, backend)
+    D = z.shape[1]
+    if backend == "hip":
+        import torch
+        from . import ops
+        U = ops.affine_lennorm(z if torch.is_tensor(z) else _plda._up(z), None, None, None, True, torch.float64)
+        return U, torch.zeros(N, device=U.device, dtype=torch.float64), _plda._up(np.full(D, 1.0 / D)), 0.0
+    assert backend == "host", backend
+    y = z.astype(np.float64)
+    ss = (y * y).sum(axis=1)
+    U = y * np.where(ss > 0, np.sqrt(D / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
+    return U, np.zeros(N), np.full(D, 1.0 / D), 0.0
+
+
+def _plda_z(emb, mean, transform, plda, smoothing, backend):
+    """where every PLDA path starts, once per call -> (z [Ntot][L] float32: the centred, projected rows of plda.project, the smoothed model)"""
     if plda is None or transform is None:
         raise ValueError("plda scoring needs the transform and the Plda object")
-    model = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))
+    return _plda.project(_center(emb, mean), transform, backend), _plda.smooth(plda, smoothing)
+
+
+def _plda_rows(z, model, normalize_length, simple_length_normalization, backend):
+    """z and the smoothed model of _plda_z -> (U, q, g, K) of dense_inputs(kind="plda")"""
     g, k, K = plda_dense_terms(model[2])
-    counts = np.ones(N, dtype=np.int64)
-    z = _plda.project(x0, transform, backend)
+    counts = np.ones(z.shape[0], dtype=np.int64)
     if backend == "hip":
         from . import ops
         U = _plda._side_hip(z, model, counts, normalize_length, simple_length_normalization)
@@ -138,84 +135,91 @@ def pca_inputs(emb, rec_off, target_energy, mean=None, transform=None, plda=None
     """The operands of the dense score with the per-recording PCA of section 6p: the embeddings centred and projected as
     dense_inputs(kind="plda") does, then pca_rows on the smoothed model"""
     E = _check_energy(target_energy, "plda")
-    if plda is None or transform is None:
-        raise ValueError("plda scoring needs the transform and the Plda object")
-    emb = np.asarray(emb)
-    model = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))
-    z = _plda.project(_center(emb, mean), transform, backend)
+    z, model = _plda_z(emb, mean, transform, plda, smoothing, backend)
     return pca_rows(z, rec_off, model, E, normalize_length, simple_length_normalization, backend, ws_budget_bytes)
+
+
+def _pca_rows_host(z, rec, model, W, B, E, normalize_length, simple_length_normalization):
+    ro, R, L = rec.rec_off, rec.R, z.shape[1]
+    z = np.asarray(z, dtype=np.float32)
+    dim, info = np.empty(R, dtype=np.int32), np.empty(R, dtype=np.int32)
+    s, psi_r, A_r, b_r = np.zeros((R, L)), np.zeros((R, L)), np.zeros((R, L, L)), np.zeros((R, L))
+    for r in range(R):
+        dim[r], s[r], psi_r[r], A_r[r], b_r[r], info[r] = _pca_rec_host(z[ro[r]:ro[r + 1]], W, B, model, E)
+    # (a recording in error has zeros in A_r, b_r and psi_r: what follows is defined for it, and pca_rows raises)
+    g, k, K = (np.array(t) for t in zip(*(plda_dense_terms(p) for p in psi_r)))
+    qn = None if (simple_length_normalization or not normalize_length) else 1.0 / (psi_r + 1.0)
+    U = np.zeros((z.shape[0], L))
+    for r in range(R):
+        u = z[ro[r]:ro[r + 1]].astype(np.float64) @ A_r[r].T + b_r[r]
+        if normalize_length:
+            ss = (u * u * (1.0 if qn is None else qn[r][None, :])).sum(axis=1)
+            u = u * np.where(ss > 0, np.sqrt(dim[r] / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
+        U[ro[r]:ro[r + 1]] = u
+    q = np.concatenate([-0.5 * (k[r][None, :] * U[ro[r]:ro[r + 1]] ** 2).sum(axis=1) for r in range(R)])
+    return {"U": U, "q": q, "g": g, "K": K, "dim": dim, "s": s, "psi_r": psi_r, "info": info}
+
+
+def _pca_rows_hip(z, rec, model, W, B, E, normalize_length, simple_length_normalization, ws_budget_bytes):
+    import torch
+    from . import ops
+    up = _plda._up
+    z = (z if torch.is_tensor(z) else up(z, np.float32)).contiguous()
+    m, T, psi = model                                               # (more than syevj_max_dim() dimensions: pca_plda_batch raises)
+    dim, s, psi_r, A_r, b_r, info = ops.pca_plda_batch(z, rec, up(W), up(B), up(T), up(psi), up(m), E, ws_budget_bytes)
+    g, k, qn, K = ops.pca_score_terms(psi_r)
+    plain = simple_length_normalization or not normalize_length
+    U = ops.affine_lennorm_rec(z, rec, A_r, b_r, None if plain else qn, dim, normalize_length)
+    q = ops.score_dense_q(U, k, -0.5, rec)
+    # (the one synchronisation of the chain, after its kernels are queued; a recording in error has zeros in A_r, b_r and psi_r)
+    return {"U": U, "q": q, "g": g, "K": K, "dim": dim.cpu().numpy(), "s": s.cpu().numpy(), "psi_r": psi_r.cpu().numpy(),
+            "info": info.cpu().numpy()}
 
 
 def pca_rows(z, rec_off, model, target_energy, normalize_length=True, simple_length_normalization=False, backend="host",
              ws_budget_bytes=1 << 31):
-    """z [Ntot][L] float32 (numpy, or on `hip` a device tensor): the rows plda.project gives; model = (mean, T, psi), already
-    smoothed -> dict(U [Ntot][L] fp64 (zeros beyond dim[r]), q [Ntot], g [R][L], K [R], dim [R], s [R][L], psi_r [R][L], info [R]);
-    U, q, g and K are device tensors on `hip`, the rest numpy.  A recording whose factorisation failed (info != 0) raises ValueError
-    naming it."""
+    """z [Ntot][L] float32 (numpy, or on `hip` a device tensor): the rows plda.project gives; rec_off [R + 1] or a RecBatch; model =
+    (mean, T, psi), already smoothed -> dict(U [Ntot][L] fp64 (zeros beyond dim[r]), q [Ntot], g [R][L], K [R], dim [R], s [R][L],
+    psi_r [R][L], info [R]); U, q, g and K are device tensors on `hip`, the rest numpy.  A recording whose factorisation failed
+    (info != 0) raises ValueError naming it."""
     E = _check_energy(target_energy, "plda")
-    ro, _ = _rec_off(rec_off, z.shape[0])
-    R = ro.size - 1
-    model = tuple(np.asarray(v, dtype=np.float64) for v in model)
-    m, T, psi = model
-    L = len(psi)
-    if z.shape[1] != L:
-        raise ValueError("the rows have %d dimensions, the PLDA model %d" % (z.shape[1], L))
+    rec = RecBatch.of(rec_off, z.shape[0])
+    model = m, T, psi = tuple(np.asarray(v, dtype=np.float64) for v in model)
+    if z.shape[1] != len(psi):
+        raise ValueError("the rows have %d dimensions, the PLDA model %d" % (z.shape[1], len(psi)))
     Ti = np.linalg.inv(T)
     W, B = Ti @ Ti.T, (Ti * psi[None, :]) @ Ti.T
     if backend == "hip":
-        import torch
-        from . import ops
-        if L > ops.syevj_max_dim():
-            raise ValueError("target_energy on the hip back end takes at most %d PLDA dimensions, got %d" % (ops.syevj_max_dim(), L))
-        up = _plda._up
-        z = (z if torch.is_tensor(z) else up(z, np.float32)).contiguous()
-        dim_d, s_d, psi_d, A_d, b_d, info_d = ops.pca_plda_batch(z, ro, up(W), up(B), up(T), up(psi), up(m), E, ws_budget_bytes)
-        g, k, qn, K = ops.pca_score_terms(psi_d)
-        plain = simple_length_normalization or not normalize_length
-        U = ops.affine_lennorm_rec(z, ro, A_d, b_d, None if plain else qn, dim_d, normalize_length)
-        q = ops.score_dense_q_rec(U, ro, k, -0.5)
-        # (the one synchronisation of the chain, after its kernels are queued; a recording in error has zeros in A_r, b_r and psi_r)
-        dim, info, s, psi_r = dim_d.cpu().numpy(), info_d.cpu().numpy(), s_d.cpu().numpy(), psi_d.cpu().numpy()
+        p = _pca_rows_hip(z, rec, model, W, B, E, normalize_length, simple_length_normalization, ws_budget_bytes)
     else:
         assert backend == "host", backend
-        z = np.asarray(z, dtype=np.float32)
-        dim, info = np.empty(R, dtype=np.int32), np.empty(R, dtype=np.int32)
-        s, psi_r, A_r, b_r = np.zeros((R, L)), np.zeros((R, L)), np.zeros((R, L, L)), np.zeros((R, L))
-        for r in range(R):
-            dim[r], s[r], psi_r[r], A_r[r], b_r[r], info[r] = _pca_rec_host(z[ro[r]:ro[r + 1]], W, B, model, E)
+        p = _pca_rows_host(z, rec, model, W, B, E, normalize_length, simple_length_normalization)
+    info = p["info"]
     bad = np.nonzero(info)[0]
     if bad.size:
         raise ValueError("the per-recording PCA failed for recording %d (info = %d: %s)" % (
             bad[0], info[bad[0]], "a Cholesky pivot was not positive" if info[bad[0]] == 2 else "an eigendecomposition did not converge"))
-    if backend != "hip":
-        terms = [plda_dense_terms(psi_r[r]) for r in range(R)]
-        g, k, K = np.stack([t[0] for t in terms]), np.stack([t[1] for t in terms]), np.array([t[2] for t in terms])
-        qn = None if (simple_length_normalization or not normalize_length) else 1.0 / (psi_r + 1.0)
-        U = np.zeros((z.shape[0], L))
-        for r in range(R):
-            u = z[ro[r]:ro[r + 1]].astype(np.float64) @ A_r[r].T + b_r[r]
-            if normalize_length:
-                ss = (u * u * (1.0 if qn is None else qn[r][None, :])).sum(axis=1)
-                u = u * np.where(ss > 0, np.sqrt(dim[r] / np.where(ss > 0, ss, 1.0)), 1.0)[:, None]
-            U[ro[r]:ro[r + 1]] = u
-        q = np.concatenate([-0.5 * (k[r][None, :] * U[ro[r]:ro[r + 1]] ** 2).sum(axis=1) for r in range(R)])
-    return {"U": U, "q": q, "g": g, "K": K, "dim": dim, "s": s, "psi_r": psi_r, "info": info}
+    return p
 
 
-def _score_rows_rec(p, ro, mat_off, backend, return_device):
-    """_score_rows with the terms of every recording's own model (pca_inputs' dict)"""
-    if backend == "hip":
-        from . import ops
-        out, mo = ops.score_dense_rec(p["U"], ro, p["q"], p["g"], p["K"])
-        assert (mo == mat_off).all()
-        return out if return_device else out.cpu().numpy()
-    out = np.empty(int(mat_off[-1]), dtype=np.float32)
-    for r in range(ro.size - 1):
-        u, qq = p["U"][ro[r]:ro[r + 1]], p["q"][ro[r]:ro[r + 1]]
-        s = np.triu(((u * p["g"][r][None, :]) @ u.T + qq[:, None]) + qq[None, :] + p["K"][r])
-        s = s + np.triu(s, 1).T
-        out[mat_off[r]:mat_off[r + 1]] = s.astype(np.float32).ravel()
-    return out
+def _inputs(emb, rec, kind, target_energy=None, vbx_rows=False, mean=None, transform=None, plda=None, smoothing=0.0,
+            normalize_length=True, simple_length_normalization=False, backend="host", ws_budget_bytes=1 << 31):
+    """The one way from the embeddings to the operands of the dense score -> (U, q, g, K, extra).  plda: the embeddings are centred
+    and projected once and the model is smoothed once, whatever follows.  target_energy: the operands are pca_rows' (g [R][D], K [R])
+    and extra holds pca_dim; vbx_rows: extra holds X and Phi for VBx: the global rows and psi, with or without the PCA."""
+    if target_energy is not None:
+        _check_energy(target_energy, kind)
+    if kind != "plda":
+        return dense_inputs(emb, kind, mean, transform, backend=backend) + ({},)
+    z, model = _plda_z(emb, mean, transform, plda, smoothing, backend)
+    norm = (normalize_length, simple_length_normalization)
+    U, q, g, K = _plda_rows(z, model, *norm, backend) if target_energy is None or vbx_rows else (None,) * 4
+    extra = {"X": U, "Phi": model[2]} if vbx_rows else {}
+    if target_energy is not None:
+        p = pca_rows(z, rec, model, target_energy, *norm, backend, ws_budget_bytes)
+        U, q, g, K = p["U"], p["q"], p["g"], p["K"]
+        extra["pca_dim"] = [int(d) for d in p["dim"]]
+    return U, q, g, K, extra
 
 
 def score_dense(emb, rec_off, kind="cosine", mean=None, transform=None, plda=None, smoothing=0.0, normalize_length=True,
@@ -225,26 +229,26 @@ def score_dense(emb, rec_off, kind="cosine", mean=None, transform=None, plda=Non
     bit for bit.  `hip` with return_device: the scores stay on the GPU (what cluster(..., backend="hip") takes).  target_energy (a
     number in (0, 1), kind plda): every recording is scored with its own PCA-adapted model (section 6p)."""
     emb = np.asarray(emb)
-    ro, mat_off = _rec_off(rec_off, emb.shape[0])
-    if target_energy is not None:
-        _check_energy(target_energy, kind)
-        p = pca_inputs(emb, ro, target_energy, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
-        return _score_rows_rec(p, ro, mat_off, backend, return_device), mat_off
-    U, q, g, K = dense_inputs(emb, kind, mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)
-    return _score_rows(U, q, g, K, ro, mat_off, backend, return_device), mat_off
+    rec = RecBatch.of(rec_off, emb.shape[0])
+    U, q, g, K, _ = _inputs(emb, rec, kind, target_energy, False, mean, transform, plda, smoothing, normalize_length,
+                            simple_length_normalization, backend)
+    return _score_rows(U, q, g, K, rec, backend, return_device), rec.mat_off
 
 
-def _score_rows(U, q, g, K, ro, mat_off, backend, return_device):
-    """the dense scores of rows that dense_inputs made (on `hip`: device tensors in, and with return_device a device tensor out)"""
+def _score_rows(U, q, g, K, rec, backend, return_device):
+    """the dense scores of the operands dense_inputs made (g [D], K a number) or pca_rows did (g [R][D], K [R]: every recording's
+    own terms); rec: rec_off [R + 1] or a RecBatch.  On `hip`: device tensors in, and with return_device a device tensor out."""
+    rec = RecBatch.of(rec, U.shape[0])
     if backend == "hip":
         from . import ops
-        out, mo = ops.score_dense(U, ro, q, g, K)
-        assert (mo == mat_off).all()
+        out = ops.score_dense(U, rec, q, g, K)[0]
         return out if return_device else out.cpu().numpy()
+    ro, mat_off = rec.rec_off, rec.mat_off
+    g, K = np.broadcast_to(g, (rec.R, U.shape[1])), np.broadcast_to(K, (rec.R,))
     out = np.empty(int(mat_off[-1]), dtype=np.float32)
-    for r in range(ro.size - 1):
+    for r in range(rec.R):
         u, qq = U[ro[r]:ro[r + 1]], q[ro[r]:ro[r + 1]]
-        s = np.triu(((u * g[None, :]) @ u.T + qq[:, None]) + qq[None, :] + K)
+        s = np.triu(((u * g[r][None, :]) @ u.T + qq[:, None]) + qq[None, :] + K[r])
         s = s + np.triu(s, 1).T                                     # the upper triangle, mirrored
         out[mat_off[r]:mat_off[r + 1]] = s.astype(np.float32).ravel()
     return out
@@ -327,33 +331,28 @@ def cluster(scores, rec_off, threshold=None, num_speakers=None, backend="host", 
     clamp to n; None: 1).  -> (labels int32 [Ntot] from 1, numbered by lowest member window; merges int32 [Ntot][2] and merge_cost
     float64 [Ntot], recording r in the slots from rec_off[r]; n_merges int32 [R]) as numpy arrays.  The merge list of a correct
     implementation is unique: both back ends give the same bits."""
-    ro = np.asarray(rec_off)
-    ro, mat_off = _rec_off(ro, int(ro[-1]) if ro.ndim == 1 and ro.size else 0)
-    R, Ntot = ro.size - 1, int(ro[-1])
+    rec = RecBatch.of(rec_off)
+    ro, mat_off, R, Ntot = rec.rec_off, rec.mat_off, rec.R, rec.Ntot
     minc = _per_recording(num_speakers, R, np.int64, 1, "num_speakers")
     if (minc < 1).any():
         raise ValueError("num_speakers must be at least 1")
     thr = _per_recording(threshold, R, np.float64, -np.inf, "threshold")
     if np.isnan(thr).any():
         raise ValueError("a threshold is NaN")
-    minc = np.minimum(minc, np.diff(ro))                            # (fits int32)
+    minc = np.minimum(minc, rec.n)                                  # (fits int32)
     if backend == "hip":
         import torch
         from . import ops
         sd = scores if torch.is_tensor(scores) else torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).cuda()
-        lab, mer, cost, nm = ops.ahc_batch(sd, ro, minc.astype(np.int32), thr, ws_budget_bytes)
-        return lab.cpu().numpy(), mer.cpu().numpy(), cost.cpu().numpy(), nm.cpu().numpy()
+        return tuple(t.cpu().numpy() for t in ops.ahc_batch(sd, rec, minc.astype(np.int32), thr, ws_budget_bytes))
     assert backend == "host", backend
     s = np.asarray(scores.cpu().numpy() if hasattr(scores, "cpu") else scores, dtype=np.float32)
     if s.size < mat_off[-1]:
         raise ValueError("the scores hold %d values, rec_off asks for %d" % (s.size, mat_off[-1]))
-    labels = np.empty(Ntot, dtype=np.int32)
-    merges = np.zeros((Ntot, 2), dtype=np.int32)
-    cost = np.zeros(Ntot, dtype=np.float64)
-    nm = np.empty(R, dtype=np.int32)
+    labels, nm = np.empty(Ntot, dtype=np.int32), np.empty(R, dtype=np.int32)
+    merges, cost = np.zeros((Ntot, 2), dtype=np.int32), np.zeros(Ntot, dtype=np.float64)
     for r in range(R):
-        n = int(ro[r + 1] - ro[r])
-        lab, mer, cs = _ahc_host(s[mat_off[r]:mat_off[r + 1]].reshape(n, n), minc[r], thr[r])
+        lab, mer, cs = _ahc_host(s[mat_off[r]:mat_off[r + 1]].reshape(rec.n[r], rec.n[r]), minc[r], thr[r])
         labels[ro[r]:ro[r + 1]] = lab
         nm[r] = len(mer)
         if mer:
@@ -372,9 +371,9 @@ def vbx_inputs(emb, mean=None, transform=None, plda=None, smoothing=0.0, normali
     """-> (X [Ntot][D'] fp64, Phi [D'] fp64): the rows of dense_inputs(kind="plda") - Plda::TransformIvector for one utterance per
     side, the space where the within-class covariance is I - and the between-class variances psi of the smoothed model.  numpy on
     `host`, device tensors on `hip`."""
-    U = dense_inputs(emb, "plda", mean, transform, plda, smoothing, normalize_length, simple_length_normalization, backend)[0]
-    psi = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))[2]
-    return U, (_plda._up(psi) if backend == "hip" else psi)
+    z, model = _plda_z(emb, mean, transform, plda, smoothing, backend)
+    U = _plda_rows(z, model, normalize_length, simple_length_normalization, backend)[0]
+    return U, (_plda._up(model[2]) if backend == "hip" else model[2])
 
 
 def vbx_init(init_labels, rec_off, init_smoothing=7.0):
@@ -382,8 +381,8 @@ def vbx_init(init_labels, rec_off, init_smoothing=7.0):
     (state s: the s-th smallest), gamma_ts = softmax_s(init_smoothing [label_t == s]) over its S states, pi_s = 1 / S; the columns
     at or beyond S are 0"""
     lab = np.asarray(init_labels)
-    ro, _ = _rec_off(rec_off, lab.shape[0])
-    R = ro.size - 1
+    rec = RecBatch.of(rec_off, lab.shape[0])
+    ro, R = rec.rec_off, rec.R
     idx = [np.unique(lab[ro[r]:ro[r + 1]], return_inverse=True)[1] for r in range(R)]
     ns = np.array([int(i.max()) + 1 for i in idx], dtype=np.int32)
     Smax = int(ns.max())
@@ -472,8 +471,8 @@ def vbx(X, Phi, rec_off, init_labels=None, gamma=None, pi=None, n_states=None, F
     if not epsilon < np.inf:
         raise ValueError("epsilon must be a number below +inf, got %r" % (epsilon,))
     Ntot, D = X.shape
-    ro, _ = _rec_off(rec_off, Ntot)
-    R = ro.size - 1
+    rec = RecBatch.of(rec_off, Ntot)
+    ro, R = rec.rec_off, rec.R
     if (init_labels is None) == (gamma is None):
         raise ValueError("give exactly one of init_labels and gamma")
     if init_labels is not None:
@@ -481,7 +480,7 @@ def vbx(X, Phi, rec_off, init_labels=None, gamma=None, pi=None, n_states=None, F
             raise ValueError("pi and n_states go with gamma, not with init_labels")
         if np.shape(init_labels) != (Ntot,):
             raise ValueError("init_labels must hold one label per window (%d), got %s" % (Ntot, np.shape(init_labels)))
-        gamma, pi, ns = vbx_init(init_labels, ro, init_smoothing)
+        gamma, pi, ns = vbx_init(init_labels, rec, init_smoothing)
     else:
         gamma = np.array(gamma, dtype=np.float64)
         if gamma.ndim != 2 or gamma.shape[0] != Ntot or gamma.shape[1] < 1:
@@ -504,12 +503,12 @@ def vbx(X, Phi, rec_off, init_labels=None, gamma=None, pi=None, n_states=None, F
         from . import ops
         if Smax > ops.vbx_max_states():
             raise ValueError("the hip back end takes at most %d states per recording, got %d" % (ops.vbx_max_states(), Smax))
-        if int(np.diff(ro).max()) > ops.ahc_max_n():
-            raise ValueError("vbx: a recording has %d windows, the cap is %d" % (int(np.diff(ro).max()), ops.ahc_max_n()))
+        if int(rec.n.max()) > ops.ahc_max_n():
+            raise ValueError("vbx: a recording has %d windows, the cap is %d" % (int(rec.n.max()), ops.ahc_max_n()))
         Xd = X if torch.is_tensor(X) else _plda._up(np.asarray(X, dtype=np.float64))
         Pd = Phi if torch.is_tensor(Phi) else _plda._up(phi_host)
         gd, pd = _plda._up(gamma), _plda._up(pi)
-        ed, nd = ops.vbx_batch(Xd.contiguous(), Pd, ro, ns, gd, pd, Fa, Fb, loop_prob, int(max_iters), epsilon,
+        ed, nd = ops.vbx_batch(Xd.contiguous(), Pd, rec, ns, gd, pd, Fa, Fb, loop_prob, int(max_iters), epsilon,
                                ws_budget_bytes=ws_budget_bytes)
         gamma, pi, elbo, nit = gd.cpu().numpy(), pd.cpu().numpy(), ed.cpu().numpy(), nd.cpu().numpy()
     else:
@@ -625,7 +624,7 @@ def read_reco2num_spk(path):
 
 
 def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=None, recordings=None, backend="host", channel=0,
-            return_scores=False, vbx=None, target_energy=None, **score_args):
+            return_scores=False, vbx=None, target_energy=None, ws_budget_bytes=1 << 31, **score_args):
     """embeddings: key -> vector (scoring.read_embeddings), segments: read_segments' list; exactly one of threshold and
     reco2num_spk (recording -> speakers).  -> dict(recordings, rec_off, mat_off, keys (batch order), labels, scores (numpy with
     return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges).
@@ -633,11 +632,9 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
     then seed VBx (section 6o; kind must be plda), `labels` and `rttm` hold its result and the dict gains ahc_labels, vbx_elbo,
     vbx_n_iters and vbx_pi; on `hip` the rows stay on the device between scoring and VBx.  target_energy: None, or the energy in
     (0, 1) of the per-recording PCA (section 6p; kind must be plda): the clustering then runs on the adapted scores and the dict gains
-    pca_dim (one int per recording); VBx keeps the global rows and the global psi."""
+    pca_dim (one int per recording); VBx keeps the global rows and the global psi.  ws_budget_bytes: as in pca_rows, cluster, vbx."""
     if (threshold is None) == (reco2num_spk is None):
         raise ValueError("give exactly one of threshold and reco2num_spk")
-    if target_energy is not None:
-        _check_energy(target_energy, kind)
     if vbx is not None:
         if kind != "plda":
             raise ValueError("vbx needs kind='plda' (its rows and variances are the PLDA's), got %r" % (kind,))
@@ -661,28 +658,17 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
         emb = embeddings.mat[[embeddings.index[k] for k in keys]]
     else:
         emb = np.stack([np.asarray(embeddings[k], dtype=np.float64) for k in keys])
-    extra = {}
-    if target_energy is not None:
-        ro, mat_off = _rec_off(rec_off, emb.shape[0])
-        p = pca_inputs(emb, ro, target_energy, backend=backend, **score_args)
-        scores = _score_rows_rec(p, ro, mat_off, backend, backend == "hip")
-        extra["pca_dim"] = [int(d) for d in p["dim"]]
-        if vbx is not None:
-            U = dense_inputs(emb, kind, backend=backend, **score_args)[0]
-    elif vbx is None:
-        scores, mat_off = score_dense(emb, rec_off, kind, backend=backend, return_device=(backend == "hip"), **score_args)
-    else:
-        ro, mat_off = _rec_off(rec_off, emb.shape[0])
-        U, q, g, K = dense_inputs(emb, kind, backend=backend, **score_args)
-        scores = _score_rows(U, q, g, K, ro, mat_off, backend, backend == "hip")
-    labels, merges, cost, nm = cluster(scores, rec_off, threshold, num, backend)
+    rec = RecBatch(rec_off, emb.shape[0])                           # (the one layout every stage below takes)
+    U, q, g, K, extra = _inputs(np.asarray(emb), rec, kind, target_energy, vbx is not None, backend=backend,
+                                ws_budget_bytes=ws_budget_bytes, **score_args)
+    scores = _score_rows(U, q, g, K, rec, backend, backend == "hip")
+    labels, merges, cost, nm = cluster(scores, rec, threshold, num, backend, ws_budget_bytes)
     segs = [segments[i] for i in flat]
     if vbx is not None:
-        psi = _plda.smooth(tuple(np.asarray(v, dtype=np.float64) for v in score_args["plda"]), float(score_args.get("smoothing", 0.0)))[2]
-        res = _vbx(U, psi, rec_off, init_labels=labels, backend=backend, **vbx)
+        res = _vbx(extra.pop("X"), extra.pop("Phi"), rec, init_labels=labels, backend=backend, ws_budget_bytes=ws_budget_bytes, **vbx)
         extra.update({"ahc_labels": labels, "vbx_elbo": res["elbo"], "vbx_n_iters": res["n_iters"], "vbx_pi": res["pi"]})
         labels = res["labels"]
-    out = {"recordings": order, "rec_off": rec_off, "mat_off": mat_off, "keys": keys, "labels": labels,
+    out = {"recordings": order, "rec_off": rec_off, "mat_off": rec.mat_off, "keys": keys, "labels": labels,
            "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),
            "merges": merges, "merge_cost": cost, "n_merges": nm}
     out.update(extra)

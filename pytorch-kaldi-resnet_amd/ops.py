@@ -4,12 +4,14 @@ import collections
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import hip, tiling
 from .hip import (CONV_CK32, CONV_M16, CONV_PIPE, CONV_WS, DY_PRESPLIT, IN_PRESPLIT, SIDE_PRESPLIT, WGRAD_GROUPS, EPI_ADD, EPI_AFFINE, EPI_BNBWD, EPI_RELU,
                   EPI_STATS, EPI_WMASK, IN_AFFINE_RELU, IN_BNBWD, MASK_ACT, MASK_NONE, MASK_RAW,
                   call, ptr, stream)
+from .recbatch import RecBatch
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -1309,7 +1311,6 @@ def plda_llr(en, te, ia, ib, psi, count, tab_count, tab_log):
 # ---- windowed extraction (csrc/window.hip) ------------------------------------------------------------------
 def _plan_i32(*cols):
     """host plan columns -> one contiguous int32 numpy array [len(cols)][N]; anything that is not an integer is refused"""
-    import numpy as np
     out = []
     for c in cols:
         a = np.asarray(c)
@@ -1350,7 +1351,6 @@ def window_mean(emb, seg_off, weight):
     U = so.size - 1
     assert emb.dtype == torch.float32
     if not isinstance(weight, torch.Tensor):
-        import numpy as np
         weight = torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float32)).to(emb.device)
     assert weight.dtype == torch.float32 and weight.numel() == N
     out = torch.empty(max(U, 0), D, device=emb.device, dtype=torch.float32)
@@ -1364,7 +1364,6 @@ def window_mean(emb, seg_off, weight):
 def diar_tables(rec_off, Ntot):
     """host rec_off [R + 1] -> (rec_off as contiguous int64, tab int64 [3][R + 1] = rec_off, mat_off, tile_off), both on the host.
     A rec_off that does not start at 0, is not strictly increasing or does not end at Ntot raises (spk_diar_tables)."""
-    import numpy as np
     ro = np.asarray(rec_off)
     if ro.dtype.kind not in "iu" or ro.ndim != 1 or ro.size < 2:
         raise TypeError("rec_off must be a one-dimensional integer array of at least two entries")
@@ -1374,33 +1373,48 @@ def diar_tables(rec_off, Ntot):
     return ro, tab
 
 
-def score_dense_q(U, k, scale):
-    """U [N][D], k [D] float64 -> q [N] float64, q_i = scale sum_d k_d U_id^2 (spk_score_dense_q)"""
+def _batch(rec, Ntot=None):
+    """rec: a RecBatch (of Ntot rows), or host rec_off [R + 1], which the library checks first (spk_diar_tables: RuntimeError)"""
+    if not isinstance(rec, RecBatch):
+        diar_tables(rec, np.asarray(rec)[-1] if Ntot is None else Ntot)
+    return RecBatch.of(rec, Ntot)
+
+
+def score_dense_q(U, k, scale, rec=None):
+    """U [N][D] float64 -> q [N] float64, q_i = scale sum_d k_d U_id^2 with k [D] (spk_score_dense_q), or with k [R][D] and rec (a
+    RecBatch or host rec_off) the k of row i's recording (spk_score_dense_q_rec)"""
     N, D = U.shape
-    assert U.dtype == torch.float64 and k.dtype == torch.float64 and k.numel() == D
+    assert U.dtype == torch.float64 and k.dtype == torch.float64 and k.is_contiguous()
     q = torch.empty(N, device=U.device, dtype=torch.float64)
-    call("spk_score_dense_q", ptr(U), ptr(k), float(scale), ptr(q), N, D, stream(), nbytes=8.0 * N * D)
+    if k.dim() == 1:
+        assert k.numel() == D
+        call("spk_score_dense_q", ptr(U), ptr(k), float(scale), ptr(q), N, D, stream(), nbytes=8.0 * N * D)
+        return q
+    b = _batch(rec, N)
+    assert k.numel() == b.R * D
+    call("spk_score_dense_q_rec", ptr(U), b.rec_off.ctypes.data, ptr(b.table(U.device)), ptr(k), float(scale), ptr(q), N, D, b.R,
+         stream(), nbytes=8.0 * N * D)
     return q
 
 
-def score_dense(U, rec_off, q, g, K, out=None):
-    """U [Ntot][D], q [Ntot], g [D] float64 (device), rec_off: host integers [R + 1] -> (out float32 [sum n^2], mat_off int64 [R + 1]
-    on the host): recording r's n x n matrix S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) at out[mat_off[r]:], symmetric
-    bit for bit (spk_score_dense).  `out`: a float32 device tensor of at least mat_off[R] elements to write into; a bad rec_off
-    raises and leaves it untouched."""
+def score_dense(U, rec, q, g, K, out=None):
+    """U [Ntot][D], q [Ntot] float64 (device), rec: a RecBatch or host rec_off [R + 1] -> (out float32 [sum n^2], mat_off int64
+    [R + 1] on the host): recording r's n x n matrix S[i][j] = (float)(q_i + q_j + K + sum_d g_d U_id U_jd) at out[mat_off[r]:],
+    symmetric bit for bit.  g [D] float64 (device), K a number: one model (spk_score_dense); g [R][D], K a float64 device tensor [R]:
+    recording r's own (spk_score_dense_rec).  `out`: a float32 device tensor of >= mat_off[R] elements; a bad rec_off leaves it untouched."""
     Ntot, D = U.shape
-    ro, tab = diar_tables(rec_off, Ntot)
-    R = ro.size - 1
-    assert U.dtype == torch.float64 and q.dtype == torch.float64 and g.dtype == torch.float64
-    assert q.numel() == Ntot and g.numel() == D
-    total = int(tab[1, R])
+    b = _batch(rec, Ntot)
+    per_rec = torch.is_tensor(K)
+    assert U.dtype == torch.float64 and q.dtype == torch.float64 and g.dtype == torch.float64 and q.numel() == Ntot
+    assert (K.dtype == torch.float64 and K.numel() == b.R and g.numel() == b.R * D and g.is_contiguous()) if per_rec else g.numel() == D
+    total = int(b.mat_off[-1])
     if out is None:
         out = torch.empty(total, device=U.device, dtype=torch.float32)
     assert out.dtype == torch.float32 and out.numel() >= total
-    td = torch.from_numpy(tab).to(U.device)
-    call("spk_score_dense", ptr(U), ro.ctypes.data, ptr(td), ptr(q), ptr(g), float(K), ptr(out), Ntot, D, R, stream(),
-         flops=1.0 * total * D, nbytes=4.0 * total + 8.0 * Ntot * D)
-    return out, tab[1].copy()
+    call("spk_score_dense_rec" if per_rec else "spk_score_dense", ptr(U), b.rec_off.ctypes.data, ptr(b.table(U.device)), ptr(q),
+         ptr(g), ptr(K) if per_rec else float(K), ptr(out), Ntot, D, b.R, stream(), flops=1.0 * total * D,
+         nbytes=4.0 * total + 8.0 * Ntot * D)
+    return out, b.mat_off.copy()
 
 
 def ahc_threads():
@@ -1413,42 +1427,29 @@ def ahc_max_n():
     return hip.lib().spk_ahc_max_n()
 
 
-def ahc_batch(scores, rec_off, min_clusters, threshold, ws_budget_bytes=1 << 31):
-    """scores: float32 device tensor, the matrices of score_dense laid end to end; rec_off: host integers [R + 1]; min_clusters [R]
-    integers; threshold [R] floats, -inf = none -> (labels int32 [Ntot], merges int32 [Ntot][2], merge_cost float64 [Ntot],
-    n_merges int32 [R]) on the device (spk_ahc_batch; the rule: include/spkhip.h).  The batch is split into launches of consecutive
-    recordings whose fp64 tables fit ws_budget_bytes (one recording always goes)."""
-    import numpy as np
-    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
-    Ntot = int(ro[-1])
-    ro, tab = diar_tables(ro, Ntot)
-    R = ro.size - 1
-    n = np.diff(ro)
-    if int(n.max()) > ahc_max_n():
-        raise ValueError("ahc_batch: a recording has %d windows, the cap is %d" % (int(n.max()), ahc_max_n()))
-    assert scores.dtype == torch.float32 and scores.numel() >= int(tab[1, R])
+def ahc_batch(scores, rec, min_clusters, threshold, ws_budget_bytes=1 << 31):
+    """scores: float32 device tensor, the matrices of score_dense laid end to end; rec: a RecBatch or host rec_off [R + 1];
+    min_clusters [R] integers; threshold [R] floats, -inf = none -> (labels int32 [Ntot], merges int32 [Ntot][2], merge_cost float64
+    [Ntot], n_merges int32 [R]) on the device (spk_ahc_batch; the rule: include/spkhip.h), in launches of consecutive recordings
+    whose fp64 tables fit ws_budget_bytes (RecBatch.chunks; one recording always goes)."""
+    b = _batch(rec)
+    R, Ntot = b.R, b.Ntot
+    if int(b.n.max()) > ahc_max_n():
+        raise ValueError("ahc_batch: a recording has %d windows, the cap is %d" % (int(b.n.max()), ahc_max_n()))
+    assert scores.dtype == torch.float32 and scores.numel() >= int(b.mat_off[R])
     dev = scores.device
     mc = torch.from_numpy(np.ascontiguousarray(min_clusters, dtype=np.int32)).to(dev)
     th = torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float64)).to(dev)
     assert mc.numel() == R and th.numel() == R
-    labels = torch.empty(Ntot, device=dev, dtype=torch.int32)
-    merges = torch.zeros(Ntot, 2, device=dev, dtype=torch.int32)
-    cost = torch.zeros(Ntot, device=dev, dtype=torch.float64)
-    nm = torch.empty(R, device=dev, dtype=torch.int32)
-    lo = 0
-    while lo < R:
-        hi = lo + 1
-        while hi < R and 8 * int(tab[1, hi + 1] - tab[1, lo]) <= ws_budget_bytes:
-            hi += 1
-        sub, stab = diar_tables(ro[lo:hi + 1] - ro[lo], int(ro[hi] - ro[lo]))
-        need = int(stab[1, hi - lo])
+    labels, nm = torch.empty(Ntot, device=dev, dtype=torch.int32), torch.empty(R, device=dev, dtype=torch.int32)
+    merges, cost = torch.zeros(Ntot, 2, device=dev, dtype=torch.int32), torch.zeros(Ntot, device=dev, dtype=torch.float64)
+    for lo, hi in b.chunks(lambda lo, hi: 8 * int(b.mat_off[hi] - b.mat_off[lo]), ws_budget_bytes):
+        sb, r0, r1 = b.sub(lo, hi)
+        need, m0 = int(sb.mat_off[-1]), int(b.mat_off[lo])
         ws = torch.empty(need, device=dev, dtype=torch.float64)
-        td = torch.from_numpy(stab).to(dev)
-        r0, r1, m0 = int(ro[lo]), int(ro[hi]), int(tab[1, lo])
-        call("spk_ahc_batch", scores[m0:].data_ptr(), sub.ctypes.data, ptr(td), mc[lo:hi].data_ptr(), th[lo:hi].data_ptr(), ptr(ws),
-             need, labels[r0:r1].data_ptr(), merges[r0:r1].data_ptr(), cost[r0:r1].data_ptr(), nm[lo:hi].data_ptr(), r1 - r0,
-             hi - lo, stream(), nbytes=12.0 * need)
-        lo = hi
+        call("spk_ahc_batch", scores[m0:].data_ptr(), sb.rec_off.ctypes.data, ptr(sb.table(dev)), mc[lo:hi].data_ptr(),
+             th[lo:hi].data_ptr(), ptr(ws), need, labels[r0:r1].data_ptr(), merges[r0:r1].data_ptr(), cost[r0:r1].data_ptr(),
+             nm[lo:hi].data_ptr(), r1 - r0, hi - lo, stream(), nbytes=12.0 * need)
     return labels, merges, cost, nm
 
 
@@ -1465,7 +1466,6 @@ def vbx_max_states():
 
 def vbx_ws_elems(rec_off, Smax, D):
     """doubles of workspace spk_vbx_batch needs for the batch; a shape it refuses raises"""
-    import numpy as np
     ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
     n = hip.lib().spk_vbx_ws_elems(ro.ctypes.data, ro.size - 1, int(Smax), int(D))
     if n < 0:
@@ -1473,18 +1473,15 @@ def vbx_ws_elems(rec_off, Smax, D):
     return int(n)
 
 
-def vbx_batch(X, Phi, rec_off, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=40, epsilon=1e-6, elbo=None,
+def vbx_batch(X, Phi, rec, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=40, epsilon=1e-6, elbo=None,
               n_iters=None, ws_budget_bytes=1 << 31):
-    """X [Ntot][D], Phi [D], gamma [Ntot][Smax], pi [R][Smax]: float64 device tensors; rec_off [R + 1] and n_states [R]: host
-    integers.  Runs the VB-HMM of every recording (spk_vbx_batch; the rule: DESIGN.md section 6o) and updates gamma and pi in place.
-    -> (elbo float64 [R][max_iters], n_iters int32 [R]) on the device; recording r fills elbo[r][:n_iters[r]] and leaves the other
-    slots as they were (NaN in a tensor made here).  The batch is split into launches of consecutive recordings whose workspace fits
-    ws_budget_bytes (one recording always goes); a recording's result does not depend on the split."""
-    import numpy as np
+    """X [Ntot][D], Phi [D], gamma [Ntot][Smax], pi [R][Smax]: float64 device tensors; rec: a RecBatch or host rec_off [R + 1];
+    n_states [R]: host integers.  Runs the VB-HMM of every recording (spk_vbx_batch; the rule: DESIGN.md section 6o) and updates
+    gamma and pi in place -> (elbo float64 [R][max_iters], n_iters int32 [R]) on the device; recording r fills elbo[r][:n_iters[r]] and leaves the other
+    slots as they were (NaN in a tensor made here).  Launches whose workspace fits ws_budget_bytes (RecBatch.chunks): the same bits."""
     Ntot, D = X.shape
-    ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
-    ro, _ = diar_tables(ro, Ntot)
-    R = ro.size - 1
+    b = _batch(rec, Ntot)
+    R = b.R
     ns = np.ascontiguousarray(np.asarray(n_states), dtype=np.int32)
     Smax = gamma.shape[1]
     assert X.dtype == torch.float64 and Phi.dtype == torch.float64 and gamma.dtype == torch.float64 and pi.dtype == torch.float64
@@ -1499,20 +1496,14 @@ def vbx_batch(X, Phi, rec_off, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0
     assert n_iters.dtype == torch.int32 and n_iters.numel() == R and n_iters.is_contiguous()
     per_row, per_rec = 8 * (3 + 2 * Smax), 8 * Smax * D
     nsd = torch.from_numpy(ns).to(dev)
-    lo = 0
-    while lo < R:
-        hi = lo + 1
-        while hi < R and per_row * int(ro[hi + 1] - ro[lo]) + per_rec * (hi + 1 - lo) <= ws_budget_bytes:
-            hi += 1
-        sub = np.ascontiguousarray(ro[lo:hi + 1] - ro[lo])
-        need = vbx_ws_elems(sub, Smax, D)
+    for lo, hi in b.chunks(lambda lo, hi: per_row * int(b.rec_off[hi] - b.rec_off[lo]) + per_rec * (hi - lo), ws_budget_bytes):
+        sb, r0, r1 = b.sub(lo, hi)
+        need = vbx_ws_elems(sb.rec_off, Smax, D)
         ws = torch.empty(need, device=dev, dtype=torch.float64)
-        sd = torch.from_numpy(sub).to(dev)
-        r0, r1 = int(ro[lo]), int(ro[hi])
-        call("spk_vbx_batch", X[r0:r1].data_ptr(), ptr(Phi), sub.ctypes.data, ptr(sd), ns[lo:hi].ctypes.data, nsd[lo:hi].data_ptr(),
-             gamma[r0:r1].data_ptr(), pi[lo:hi].data_ptr(), float(Fa), float(Fb), float(loop_prob), int(max_iters), float(epsilon),
-             ptr(ws), need, elbo[lo:hi].data_ptr(), n_iters[lo:hi].data_ptr(), r1 - r0, D, hi - lo, Smax, stream(), nbytes=8.0 * need)
-        lo = hi
+        call("spk_vbx_batch", X[r0:r1].data_ptr(), ptr(Phi), sb.rec_off.ctypes.data, ptr(sb.table(dev)), ns[lo:hi].ctypes.data,
+             nsd[lo:hi].data_ptr(), gamma[r0:r1].data_ptr(), pi[lo:hi].data_ptr(), float(Fa), float(Fb), float(loop_prob),
+             int(max_iters), float(epsilon), ptr(ws), need, elbo[lo:hi].data_ptr(), n_iters[lo:hi].data_ptr(), r1 - r0, D, hi - lo, Smax,
+             stream(), nbytes=8.0 * need)
     return elbo, n_iters
 
 
@@ -1531,7 +1522,6 @@ def syevj_batch(A, orders=None):
     """A [R][ld][ld] float64 (device), symmetric (the upper triangles are read); orders: host integers [R] in [1, ld] (default ld) ->
     (w [R][ld] descending, vec [R][ld][ld] with row k the eigenvector of w[k], sweeps int32 [R], info int32 [R]) on the device
     (spk_syevj_batch); zeros at and beyond a matrix's order."""
-    import numpy as np
     R, ld = A.shape[0], A.shape[1]
     assert A.dtype == torch.float64 and A.dim() == 3 and A.shape[2] == ld and A.is_contiguous()
     od = np.full(R, ld, dtype=np.int32) if orders is None else np.ascontiguousarray(np.asarray(orders), dtype=np.int32)
@@ -1553,7 +1543,6 @@ def syevj_batch(A, orders=None):
 
 def pca_plda_ws_elems(rec_off, L):
     """doubles of workspace spk_pca_plda_batch needs for the batch; a shape it refuses raises"""
-    import numpy as np
     ro = np.ascontiguousarray(np.asarray(rec_off), dtype=np.int64)
     n = hip.lib().spk_pca_plda_ws_elems(ro.ctypes.data, ro.size - 1, int(L))
     if n < 0:
@@ -1561,40 +1550,30 @@ def pca_plda_ws_elems(rec_off, L):
     return int(n)
 
 
-def pca_plda_batch(Z, rec_off, W, B, T, psi, mean, E, ws_budget_bytes=1 << 31):
-    """Z [Ntot][L] float32 (device): the rows of plda.project; rec_off: host integers [R + 1]; W, B, T [L][L], psi and mean [L]
+def pca_plda_batch(Z, rec, W, B, T, psi, mean, E, ws_budget_bytes=1 << 31):
+    """Z [Ntot][L] float32 (device): the rows of plda.project; rec: a RecBatch or host rec_off [R + 1]; W, B, T [L][L], psi and mean [L]
     float64 (device) -> (dim int32 [R], s [R][L], psi_r [R][L], A_r [R][L][L], b_r [R][L], info int32 [R]) on the device: steps 1-5
-    of section 6p (spk_pca_plda_batch).  The batch is split into launches of consecutive recordings whose workspace fits
-    ws_budget_bytes (one recording always goes); a recording's result does not depend on the split."""
-    import numpy as np
+    of section 6p (spk_pca_plda_batch), in launches whose workspace fits ws_budget_bytes (RecBatch.chunks): the same bits however split."""
     Ntot, L = Z.shape
-    ro, _ = diar_tables(rec_off, Ntot)
-    R = ro.size - 1
+    b = _batch(rec, Ntot)
+    R = b.R
     if L > syevj_max_dim():
         raise ValueError("pca_plda_batch: L=%d, the hip back end takes at most %d dimensions" % (L, syevj_max_dim()))
     assert Z.dtype == torch.float32 and Z.is_contiguous()
     for t, n in ((W, L * L), (B, L * L), (T, L * L), (psi, L), (mean, L)):
         assert t.dtype == torch.float64 and t.numel() == n and t.is_contiguous()
     dev = Z.device
-    dim = torch.empty(R, device=dev, dtype=torch.int32)
-    info = torch.empty(R, device=dev, dtype=torch.int32)
-    s = torch.empty(R, L, device=dev, dtype=torch.float64)
-    psi_r = torch.empty(R, L, device=dev, dtype=torch.float64)
+    dim, info = (torch.empty(R, device=dev, dtype=torch.int32) for _ in range(2))
+    s, psi_r, b_r = (torch.empty(R, L, device=dev, dtype=torch.float64) for _ in range(3))
     A_r = torch.empty(R, L, L, device=dev, dtype=torch.float64)
-    b_r = torch.empty(R, L, device=dev, dtype=torch.float64)
     per = 8 * (pca_plda_ws_elems(np.array([0, 1]), L) - 1)
-    lo = 0
-    while lo < R:
-        hi = min(R, lo + max(1, int(ws_budget_bytes // per)), lo + 65535)
-        sub, stab = diar_tables(ro[lo:hi + 1] - ro[lo], int(ro[hi] - ro[lo]))
-        need = pca_plda_ws_elems(sub, L)
+    for lo, hi in b.chunks(lambda lo, hi: per * (hi - lo), ws_budget_bytes, max_recs=65535):
+        sb, r0, r1 = b.sub(lo, hi)
+        need = pca_plda_ws_elems(sb.rec_off, L)
         ws = torch.empty(need, device=dev, dtype=torch.float64)
-        td = torch.from_numpy(stab).to(dev)
-        r0, r1 = int(ro[lo]), int(ro[hi])
-        call("spk_pca_plda_batch", Z[r0:r1].data_ptr(), sub.ctypes.data, ptr(td), ptr(W), ptr(B), ptr(T), ptr(psi), ptr(mean), float(E),
-             ptr(ws), need, dim[lo:hi].data_ptr(), s[lo:hi].data_ptr(), psi_r[lo:hi].data_ptr(), A_r[lo:hi].data_ptr(),
-             b_r[lo:hi].data_ptr(), info[lo:hi].data_ptr(), r1 - r0, L, hi - lo, stream(), nbytes=8.0 * need)
-        lo = hi
+        call("spk_pca_plda_batch", Z[r0:r1].data_ptr(), sb.rec_off.ctypes.data, ptr(sb.table(dev)), ptr(W), ptr(B), ptr(T), ptr(psi),
+             ptr(mean), float(E), ptr(ws), need, dim[lo:hi].data_ptr(), s[lo:hi].data_ptr(), psi_r[lo:hi].data_ptr(),
+             A_r[lo:hi].data_ptr(), b_r[lo:hi].data_ptr(), info[lo:hi].data_ptr(), r1 - r0, L, hi - lo, stream(), nbytes=8.0 * need)
     return dim, s, psi_r, A_r, b_r, info
 
 
@@ -1609,47 +1588,17 @@ def pca_score_terms(psi_r):
     return g, k, qn, K
 
 
-def affine_lennorm_rec(Z, rec_off, A_r, b_r, q_r, dim, scale):
-    """Z [Ntot][L] float32, A_r [R][L][L], b_r [R][L], q_r [R][L] or None (ones), dim int32 [R] (device) -> U [Ntot][L] float64:
-    recording r's rows through its own map, Do = dim[r] in the scale, zeros beyond dim[r] (spk_affine_lennorm_rec)"""
+def affine_lennorm_rec(Z, rec, A_r, b_r, q_r, dim, scale):
+    """Z [Ntot][L] float32, A_r [R][L][L], b_r [R][L], q_r [R][L] or None (ones), dim int32 [R] (device); rec: a RecBatch or host
+    rec_off [R + 1] -> U [Ntot][L] float64: recording r's rows through its own map, Do = dim[r] in the scale, zeros beyond dim[r]
+    (spk_affine_lennorm_rec)"""
     Ntot, L = Z.shape
-    ro, tab = diar_tables(rec_off, Ntot)
-    R = ro.size - 1
+    b = _batch(rec, Ntot)
+    R = b.R
     assert Z.dtype == torch.float32 and Z.is_contiguous() and dim.dtype == torch.int32 and dim.numel() == R
     assert A_r.dtype == torch.float64 and A_r.numel() == R * L * L and b_r.dtype == torch.float64 and b_r.numel() == R * L
     assert q_r is None or (q_r.dtype == torch.float64 and q_r.numel() == R * L)
     U = torch.empty(Ntot, L, device=Z.device, dtype=torch.float64)
-    td = torch.from_numpy(tab).to(Z.device)
-    call("spk_affine_lennorm_rec", ptr(Z), ro.ctypes.data, ptr(td), ptr(A_r), ptr(b_r), ptr(q_r), ptr(dim), 1 if scale else 0, ptr(U),
-         Ntot, L, R, stream(), flops=2.0 * Ntot * L * L)
+    call("spk_affine_lennorm_rec", ptr(Z), b.rec_off.ctypes.data, ptr(b.table(Z.device)), ptr(A_r), ptr(b_r), ptr(q_r), ptr(dim),
+         1 if scale else 0, ptr(U), Ntot, L, R, stream(), flops=2.0 * Ntot * L * L)
     return U
-
-
-def score_dense_q_rec(U, rec_off, k, scale):
-    """U [Ntot][D], k [R][D] float64 -> q [Ntot], q_i = scale sum_d k[r(i)][d] U_id^2 (spk_score_dense_q_rec)"""
-    Ntot, D = U.shape
-    ro, tab = diar_tables(rec_off, Ntot)
-    R = ro.size - 1
-    assert U.dtype == torch.float64 and k.dtype == torch.float64 and k.numel() == R * D and k.is_contiguous()
-    q = torch.empty(Ntot, device=U.device, dtype=torch.float64)
-    td = torch.from_numpy(tab).to(U.device)
-    call("spk_score_dense_q_rec", ptr(U), ro.ctypes.data, ptr(td), ptr(k), float(scale), ptr(q), Ntot, D, R, stream(),
-         nbytes=8.0 * Ntot * D)
-    return q
-
-
-def score_dense_rec(U, rec_off, q, g, K, out=None):
-    """score_dense with g [R][D] and K [R] (device, float64) per recording (spk_score_dense_rec)"""
-    Ntot, D = U.shape
-    ro, tab = diar_tables(rec_off, Ntot)
-    R = ro.size - 1
-    assert U.dtype == torch.float64 and q.dtype == torch.float64 and g.dtype == torch.float64 and K.dtype == torch.float64
-    assert q.numel() == Ntot and g.numel() == R * D and K.numel() == R and g.is_contiguous()
-    total = int(tab[1, R])
-    if out is None:
-        out = torch.empty(total, device=U.device, dtype=torch.float32)
-    assert out.dtype == torch.float32 and out.numel() >= total
-    td = torch.from_numpy(tab).to(U.device)
-    call("spk_score_dense_rec", ptr(U), ro.ctypes.data, ptr(td), ptr(q), ptr(g), ptr(K), ptr(out), Ntot, D, R, stream(),
-         flops=1.0 * total * D, nbytes=4.0 * total + 8.0 * Ntot * D)
-    return out, tab[1].copy()

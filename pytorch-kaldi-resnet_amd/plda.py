@@ -306,8 +306,8 @@ def compute_plda(vecs, utt2spk, transform, num_em_iters=10, mean=None, backend="
 
 # ---- scoring --------------------------------------------------------------------------------------------------------------------
 def smooth(plda, smoothing):
-    """ivector-copy-plda --smoothing: psi /= c, transform rows *= c^-1/2 with c = 1 + smoothing psi (0.0 changes nothing)"""
-    mean, T, psi = plda
+    """ivector-copy-plda --smoothing: psi /= c, transform rows *= c^-1/2 with c = 1 + smoothing psi (0.0 changes nothing) -> float64"""
+    mean, T, psi = (np.asarray(v, dtype=np.float64) for v in plda)
     if smoothing == 0.0:
         return mean, T, psi
     c = 1.0 + smoothing * psi
@@ -349,7 +349,7 @@ def plda_score(enroll, test, trials_path, mean, transform, plda, num_utts=None, 
                simple_length_normalization=False, smoothing=0.0, score_path=None, backend="host", return_device=False):
     """scores (float32) and labels for '<enroll> <test> target|nontarget' lines.  num_utts: utt -> enrolment count (default 1);
     the test side always counts 1.  An unknown key raises KeyError."""
-    plda = smooth(tuple(np.asarray(v, dtype=np.float64) for v in plda), float(smoothing))
+    plda = smooth(plda, smoothing)
     psi = plda[2]
     pairs, labels = [], []
     for line in open(trials_path):

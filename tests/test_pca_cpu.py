@@ -126,7 +126,7 @@ def test_no_target_energy_is_todays_path(diarize):
     a, mo = diarize.score_dense(emb, ro, "plda", **args)
     b, _ = diarize.score_dense(emb, ro, "plda", target_energy=None, **args)
     U, q, g, K = diarize.dense_inputs(emb, "plda", **args)
-    want = diarize._score_rows(U, q, g, K, ro.astype(np.int64), mo, "host", False)
+    want = diarize._score_rows(U, q, g, K, ro.astype(np.int64), "host", False)
     assert a.tobytes() == b.tobytes() == want.tobytes()
     keys = ["k%d" % i for i in range(11)]
     segs = [(k, "a" if i < 4 else "b", 0.2 * i, 0.2 * i + 0.4) for i, k in enumerate(keys)]

@@ -190,7 +190,7 @@ def test_pca_launch_under_the_rule(env, L):
     for E in [0.1, 0.5, 0.9] + ([0.999] if L in CLAMP_LS else []):
         p = diarize.pca_rows(Z, ro, model, E, backend="hip")
         U = p["U"].cpu().numpy()
-        scores, mat_off = env["ops"].score_dense_rec(p["U"], ro, p["q"], p["g"], p["K"])
+        scores, mat_off = env["ops"].score_dense(p["U"], ro, p["q"], p["g"], p["K"])
         scores, gK, gg, qq = scores.cpu().numpy(), p["K"].cpu().numpy(), p["g"].cpu().numpy(), p["q"].cpu().numpy()
         assert (p["info"] == 0).all()
         for r, n in enumerate(NS):

@@ -66,6 +66,7 @@ def main():
         emb, planted = synth(ns, D, rng)
         rec_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
         R = len(ns)
+        rec = diarize.RecBatch(rec_off)                             # the layout, as diarize() builds one per call
         Ud, qd_unused, gd, K = diarize.dense_inputs(emb, "plda", transform=transform, plda=model, backend="hip")
         Uh, qh_unused, gh, Kh = diarize.dense_inputs(emb, "plda", transform=transform, plda=model, backend="host")
         kd = torch.from_numpy(diarize.plda_dense_terms(model[2])[1]).cuda()
@@ -76,9 +77,9 @@ def main():
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
             q = ops.score_dense_q(Ud, kd, -0.5)
-            scores, _ = ops.score_dense(Ud, rec_off, q, gd, K)
+            scores, _ = ops.score_dense(Ud, rec, q, gd, K)
             ev[1].record()
-            out = ops.ahc_batch(scores, rec_off, four, none)
+            out = ops.ahc_batch(scores, rec, four, none)
             ev[2].record()
             torch.cuda.synchronize()
             return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), out[0].cpu().numpy()
@@ -104,7 +105,7 @@ def main():
             t2 = time.perf_counter()
             return (t1 - t0) * 1e3, (t2 - t1) * 1e3, labels
 
-        hip_leg()                                                   # warm-up: code objects, allocator
+        hip_leg()                                                   # warm-up: code objects, allocator, the layout's device table
         t = {"hip_scores": [], "hip_cluster": [], "host_scores": [], "host_cluster": []}
         for _ in range(a.reps):
             s, c, lab_hip = hip_leg()

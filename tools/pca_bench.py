@@ -3,7 +3,7 @@
 
   workload   64 recordings of 800 windows, L = 128, four planted speakers per recording, E = 0.1 and E = 0.9;
   legs       `hip`: spk_pca_plda_batch, then spk_pca_score_terms, spk_affine_lennorm_rec, spk_score_dense_q_rec and
-             spk_score_dense_rec, from the projected rows already in HBM, timed by device events; `host`: diarize.pca_rows and the
+             spk_score_dense_rec, from the projected rows and the batch's offset table already in HBM, timed by device events; `host`: diarize.pca_rows and the
              numpy scores, timed by the host clock.  The two legs alternate `--reps` times in one process after one warm-up;
   alone      the same `hip` leg on the first recording only: one workgroup per recording, so this is the slowest workgroup's time;
   eig        spk_syevj_batch alone on the 64 covariances (order L) and on 64 matrices Q diag(psi_r) Q^T of the retained orders (the
@@ -77,7 +77,7 @@ def main():
         def rest():
             g, k, qn, K = ops.pca_score_terms(psi_r)
             U = ops.affine_lennorm_rec(Z, rec_off, A_r, b_r, qn, dim, True)
-            return ops.score_dense_rec(U, rec_off, ops.score_dense_q_rec(U, rec_off, k, -0.5), g, K)[0]
+            return ops.score_dense(U, rec_off, ops.score_dense_q(U, k, -0.5, rec_off), g, K)[0]
 
         t_rest, scores = timed(rest)
         assert int(info.abs().max()) == 0
@@ -87,21 +87,22 @@ def main():
         t0 = time.perf_counter()
         p = diarize.pca_rows(Zh, ro, model, E, backend="host")
         t1 = time.perf_counter()
-        s = diarize._score_rows_rec(p, ro, np.arange(R + 1, dtype=np.int64) * n * n, "host", False)
+        s = diarize._score_rows(p["U"], p["q"], p["g"], p["K"], ro, "host", False)
         return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, p["dim"], s
 
-    hip_leg(Zd, ro, 0.9)                                            # warm-up: code objects, allocator
-    hip_leg(Zd[:n], ro[:2], 0.9)
+    rec, rec1 = diarize.RecBatch(ro), diarize.RecBatch(ro[:2])     # the layouts, as diarize() builds one per call
+    hip_leg(Zd, rec, 0.9)                                           # warm-up: code objects, allocator, the layouts' device tables
+    hip_leg(Zd[:n], rec1, 0.9)
     for E in (0.1, 0.9):
         t = {k: [] for k in ("hip_pca", "hip_rows_scores", "host_pca", "host_rows_scores", "hip_pca_one_recording")}
         for _ in range(a.reps):
-            tp, tr, dim_hip, psi_hip, s_hip = hip_leg(Zd, ro, E)
+            tp, tr, dim_hip, psi_hip, s_hip = hip_leg(Zd, rec, E)
             t["hip_pca"].append(tp)
             t["hip_rows_scores"].append(tr)
             hp, hr, dim_host, s_host = host_leg(E)
             t["host_pca"].append(hp)
             t["host_rows_scores"].append(hr)
-            t["hip_pca_one_recording"].append(hip_leg(Zd[:n], ro[:2], E)[0])
+            t["hip_pca_one_recording"].append(hip_leg(Zd[:n], rec1, E)[0])
         leg = {k: stats(v) for k, v in t.items()}
         leg["host_over_hip_pca"] = leg["host_pca"]["median_ms"] / leg["hip_pca"]["median_ms"]
         leg["host_over_hip_all"] = ((leg["host_pca"]["median_ms"] + leg["host_rows_scores"]["median_ms"])

