@@ -530,6 +530,22 @@ int spk_fbank_dither_noise(float* out /*[nframes][L]*/, long long utt_id, unsign
 int spk_vad_count(const float* log_energy, const int* T, int B, int Tcap, double energy_threshold, double mean_scale,
                   int frames_context, double proportion, int* vad /*[B][Tcap]*/, int* idx /*[B][Tcap]*/, int* count /*[B]*/,
                   void* stream);
+/* VAD decisions -> speech segments, the step in front of windowed extraction for diarization (the role of
+ * Kaldi's diarization/vad_to_segments.sh, but the rule below is this project's contract, not a port).  Row b has T[b] frames
+ * (clamped to [0, Tcap]); frame t is voiced iff vad[b][t] != 0.  padding p >= 0, max_gap g >= 0, min_length m >= 1, in frames:
+ *   1. runs: the maximal intervals [s_i, e_i) of voiced frames, ascending;
+ *   2. padding: a_i = max(0, s_i - p), b_i = min(T, e_i + p);
+ *   3. run 0 opens a segment; run i > 0 opens a new one iff a_i - b_{i-1} > g, else it joins the current one (also when the
+ *      padded runs overlap).  A segment is [a of its opening run, b of its last run);
+ *   4. a segment with b - a < m is dropped, the others are emitted in order.
+ * nseg[b] = the number of emitted segments of row b, also when it exceeds Scap; seg[b][0 .. min(nseg[b], Scap)) = their
+ * (start, end) pairs, every other word of seg is left as it was.  Integers only: the same bits on every run, wherever a row sits
+ * in the batch.  Refused before any launch (rc < 0): negative B / Tcap / padding / max_gap / Scap, Tcap > 2^31 - 1025,
+ * min_length < 1, and with B > 0 a NULL T or nseg, a NULL vad with Tcap > 0, a NULL seg with Scap > 0.  B == 0 returns 0 without
+ * a launch. */
+int spk_vad_segments(const int* vad /*[B][Tcap] device*/, const int* T /*[B] device*/, int B, int Tcap, int padding, int max_gap,
+                     int min_length, int* seg /*[B][Scap][2] device: start, end*/, int Scap, int* nseg /*[B] device*/,
+                     void* stream);
 /* centred sliding CMN (window cmn_window, fp64 sums; 0 = none) of x [B][F][Tcap] over T[b] frames, then the frames idx[b][0 ..
  * count[b]) (idx and count NULL: all T[b] frames) compacted into out [B][F][Tout] with zero tails.  prefix: fp64 workspace of
  * B * F * (Tcap + 1) doubles (may be NULL when cmn_window == 0). */

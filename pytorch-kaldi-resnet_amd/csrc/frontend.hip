@@ -343,6 +343,93 @@ __global__ __launch_bounds__(64) void vad_kernel(const float* __restrict__ loge,
     if (lane == 0) count[b] = carry;
 }
 
+// VAD decisions -> speech segments (the rule is in include/spkhip.h): one wave per row, one pass over the
+// frames.  Per 64-frame chunk the wave takes the ballot of the voiced frames; run starts (v[t] && !v[t-1]) and run ends
+// (!v[t] && v[t-1], the exclusive end of the run) are bits of two masks made from it and the last bit of the chunk before.  Every
+// decision is local to a run start: the run end before it is the highest end bit below the lane (or the carry of earlier chunks),
+// so the lane knows whether its run opens a segment; the start that opened the segment it closes is the highest opener bit below
+// the lane (or the carry), so it knows the closed segment's extent and whether min_length keeps it; the output index is the
+// count of kept segments so far plus a prefix popcount.  Starts and ends are frame numbers, so nothing but masks crosses lanes.
+// The last segment is closed at T by lane 0.  A round is SEG_CHUNKS chunks: the loads of the next round are issued before the
+// chunks of this one are looked at.
+constexpr int SEG_CHUNKS = 8;
+
+__device__ inline int seg_top(unsigned long long m) { return 63 - __clzll((long long)m); }     // highest set bit, m != 0
+
+__global__ __launch_bounds__(64) void vad_segments_kernel(const int* __restrict__ vad, const int* __restrict__ Tv, int Tcap, int pad,
+                                                          int gap, int minlen, int* __restrict__ seg, int Scap,
+                                                          int* __restrict__ nseg) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int T = min(max(Tv[b], 0), Tcap);
+    const int* v = vad + (size_t)b * Tcap;
+    int* out = seg + (size_t)b * Scap * 2;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int last_end = -1;      // exclusive end of the last run that ended in an earlier chunk (-1: none yet)
+    int open_t = -1;        // first frame of the run that opened the current segment (-1: no run yet)
+    int nout = 0;           // segments kept so far
+    unsigned long long pv = 0;      // v[t0 - 1]
+    int w[SEG_CHUNKS], wn[SEG_CHUNKS];
+#pragma unroll
+    for (int u = 0; u < SEG_CHUNKS; ++u) {
+        const int t = u * 64 + lane;
+        wn[u] = t < T ? v[t] : 0;
+    }
+    for (int tb = 0; tb < T; tb += 64 * SEG_CHUNKS) {
+#pragma unroll
+        for (int u = 0; u < SEG_CHUNKS; ++u) {      // the next round's loads fly while this round's chunks are looked at
+            w[u] = wn[u];
+            const int t = tb + (SEG_CHUNKS + u) * 64 + lane;
+            wn[u] = t < T ? v[t] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < SEG_CHUNKS; ++u) {
+            const int t0 = tb + u * 64;
+            if (t0 < T) {       // wave-uniform
+                const unsigned long long vm = __ballot(w[u] != 0);
+                const unsigned long long prev = (vm << 1) | pv;
+                const unsigned long long sm = vm & ~prev, em = ~vm & prev;
+                const int t = t0 + lane;
+                const unsigned long long eb = em & below;
+                const int e_prev = eb ? t0 + seg_top(eb) : last_end;
+                const bool first = e_prev < 0;                                       // run 0: nothing ended before it
+                const int a = max(t - pad, 0);
+                const int b_prev = (int)min((long long)e_prev + pad, (long long)T);  // unused for run 0
+                const bool opener = ((sm >> lane) & 1ull) && (first || a - b_prev > gap);
+                const unsigned long long om = __ballot(opener);
+                const unsigned long long ob = om & below;
+                const int a_open = max((ob ? t0 + seg_top(ob) : open_t) - pad, 0);
+                const bool keep = opener && !first && b_prev - a_open >= minlen;
+                const unsigned long long km = __ballot(keep);
+                if (keep) {
+                    const int i = nout + __popcll(km & below);
+                    if (i < Scap) {
+                        out[2 * (size_t)i] = a_open;
+                        out[2 * (size_t)i + 1] = b_prev;
+                    }
+                }
+                nout += __popcll(km);
+                if (em) last_end = t0 + seg_top(em);
+                if (om) open_t = t0 + seg_top(om);
+                pv = vm >> 63;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (open_t >= 0) {      // the segment that is open at T; a run that reaches T (a multiple of 64) ends there
+            const int a_open = max(open_t - pad, 0);
+            const int b_last = (int)min((long long)(pv ? T : last_end) + pad, (long long)T);
+            if (b_last - a_open >= minlen) {
+                if (nout < Scap) {
+                    out[2 * (size_t)nout] = a_open;
+                    out[2 * (size_t)nout + 1] = b_last;
+                }
+                ++nout;
+            }
+        }
+        nseg[b] = nout;
+    }
+}
+
 // fp64 prefix sums of every (b, m) row over its T[b] frames: pre[row][0] = 0, pre[row][t + 1] = sum x[0..t]; one wave per row
 __global__ __launch_bounds__(256) void cmn_prefix_kernel(const float* __restrict__ x, const int* __restrict__ Tv, int B, int F,
                                                          int Tcap, double* __restrict__ pre) {
@@ -593,6 +680,21 @@ extern "C" int spk_vad_count(const float* log_energy, const int* T, int B, int T
     hipLaunchKernelGGL(vad_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, log_energy, T, Tcap, energy_threshold,
                        mean_scale, frames_context, proportion, vad, idx, count);
     SPK_LAUNCH_CHECK("spk_vad_count");
+    return 0;
+}
+
+extern "C" int spk_vad_segments(const int* vad, const int* T, int B, int Tcap, int padding, int max_gap, int min_length, int* seg,
+                                int Scap, int* nseg, void* stream) {
+    // Tcap: the frame index of a lane past the last round's prefetch must stay an int
+    SPK_REQUIRE(B >= 0 && Tcap >= 0 && Tcap <= 0x7fffffff - 2 * 64 * SEG_CHUNKS && Scap >= 0, "spk_vad_segments: B=%d Tcap=%d Scap=%d", B,
+                Tcap, Scap);
+    SPK_REQUIRE(padding >= 0 && max_gap >= 0 && min_length >= 1, "spk_vad_segments: padding=%d max_gap=%d (>= 0) min_length=%d (>= 1)",
+                padding, max_gap, min_length);
+    if (B == 0) return 0;
+    SPK_REQUIRE(T && nseg && (vad || Tcap == 0) && (seg || Scap == 0), "spk_vad_segments: null pointer");
+    hipLaunchKernelGGL(vad_segments_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, vad, T, Tcap, padding, max_gap,
+                       min_length, seg, Scap, nseg);
+    SPK_LAUNCH_CHECK("spk_vad_segments");
     return 0;
 }
 

@@ -405,7 +405,8 @@ class Engine:
                 return emb
             return self.embed_eval(x)
 
-    def predict_windows(self, x, lengths, window, period, min_window=None, average=False, precision="f32", batch_size=None):
+    def predict_windows(self, x, lengths, window, period, min_window=None, average=False, precision="f32", batch_size=None,
+                        segments=None):
         """Windowed extraction, eval mode only.  x [B, F, T]: a padded batch, lengths: per-utterance frame
         counts (0 <= L[b] <= T; None: T frames each).  The windows of ingest.plan_windows(lengths, window, period, min_window)
         (min_window None: 1) are gathered into padded batches of at most batch_size rows (default B; ingest.window_batches,
@@ -414,7 +415,12 @@ class Engine:
         -> (emb [N, D], utt [N], start [N], length [N]) in plan order (the last three numpy int64), or with average=True
         (emb [U', D], utt [U']): per utterance that has a window, the mean of its window embeddings weighted by window length
         (spk_window_mean).  self.windows_skipped: the utterances shorter than min_window.  After a precision="f16" call
-        self.half_overflow holds the count of every WINDOW, in plan order (also with average=True)."""
+        self.half_overflow holds the count of every WINDOW, in plan order (also with average=True).
+        segments: a tuple (seg_utt, seg_start, seg_end) of speech segments, frames [seg_start[j], seg_end[j])
+        of utterance seg_utt[j], sorted by utterance and disjoint within one, none ending beyond lengths[seg_utt[j]].  The plan is
+        then ingest.plan_segment_windows: the window rule inside every segment.  `start` stays in utterance frames,
+        self.windows_skipped lists the SEGMENTS shorter than min_window, average=True averages all windows of an utterance (a
+        speech-only chunk average), and an utterance without a segment yields no row."""
         import numpy as np
         from . import ingest
         if precision not in ("f32", "f16"):
@@ -439,7 +445,16 @@ class Engine:
                 raise ValueError("lengths has shape %s for a batch of %d utterances" % (L.shape, B))
             if B and (int(L.min()) < 0 or int(L.max()) > T):
                 raise ValueError("lengths must lie in [0, T=%d], got min %d max %d" % (T, int(L.min()), int(L.max())))
-        plan = ingest.plan_windows(L, window, period, 1 if min_window is None else min_window)
+        if segments is None:
+            plan = ingest.plan_windows(L, window, period, 1 if min_window is None else min_window)
+        else:
+            su, ss, se = (np.asarray(v, dtype=np.int64).reshape(-1) for v in segments)
+            if su.size and (int(su.min()) < 0 or int(su.max()) >= B):
+                raise ValueError("segments name utterance %d of a batch of %d" % (int(su.min()) if int(su.min()) < 0 else int(su.max()), B))
+            if su.size == se.size and (se > L[su]).any():
+                j = int(np.nonzero(se > L[su])[0][0])
+                raise ValueError("segment %d ends at frame %d, beyond the %d frames of utterance %d" % (j, se[j], L[su[j]], su[j]))
+            plan = ingest.plan_segment_windows(su, ss, se, window, period, 1 if min_window is None else min_window)
         self.windows_skipped = plan.skipped
         N = plan.utt.size
         D = self.m.fc1.weight.shape[0]

@@ -9,6 +9,8 @@ config files, builds the window / twiddle / mel / resampling tables in fp64 and 
 Training from audio adds the span form of the two frame kernels (fbank_span / mfcc_span: the frames of a part of
 an utterance, bit for bit the frames of the whole), pcm16_to_f32, AugmentPool (the device-resident form of WavAugmentation) and
 ChunkFrontend, which ingest.WavTrainLoader runs on its copy stream.
+Speech segments: SegmentOptions, vad_segments (spk_vad_segments: the VAD decisions of a batch -> speech segments, on
+the device) and Frontend(..., segments=): all frames kept, the segments in frames of the recording - the front of the diarization chain.
 The one deliberate difference from Kaldi: dither is a counter-based N(0,1) draw keyed by (seed, utt_id, frame, position), and the VAD
 sees the same dithered frames as the fbank (Kaldi draws a second dither for its MFCC pass).
 """
@@ -220,6 +222,20 @@ class CmnOptions(_KaldiOptions):
             raise ValueError("CmnOptions: only center=true is supported (pass center=True, as the recipe does)")
         if self.cmn_window < 1:
             raise ValueError("CmnOptions: cmn_window >= 1")
+
+
+@dataclasses.dataclass
+class SegmentOptions:
+    """VAD decisions -> speech segments (the rule: include/spkhip.h, spk_vad_segments), in frames: every run
+    of voiced frames is padded by `padding` on both sides, runs whose padded ends are at most `max_gap` apart are joined, and a
+    segment shorter than `min_length` is dropped.  The defaults are the project's choice, not a measurement."""
+    padding: int = 10
+    max_gap: int = 30
+    min_length: int = 50
+
+    def __post_init__(self):
+        if self.padding < 0 or self.max_gap < 0 or self.min_length < 1:
+            raise ValueError("SegmentOptions: padding >= 0, max_gap >= 0 and min_length >= 1")
 
 
 # ---- host tables (fp64, rounded to fp32 once) ----
@@ -1275,6 +1291,37 @@ def vad(log_energy, T, opts):
     return v, idx, cnt.cpu().numpy().astype(np.int64)
 
 
+SEGMENT_CAP = 1024      # segments per row the first launch of vad_segments has room for
+
+
+def vad_segments(vad, T, opts):
+    """spk_vad_segments: the VAD decisions vad [B, Tcap] (int32 cuda; voiced iff != 0) of T[b] frames -> the speech segments under
+    SegmentOptions `opts`, as (row, start, end): flat int64 host arrays in row and then time order - what ingest.segments_from_vad
+    gives for the same input.  One launch with room for SEGMENT_CAP segments per row, one more with room for the largest count
+    when a row has more; only the counts and the written pairs are downloaded, never the VAD tensor."""
+    if vad.dim() != 2 or vad.dtype != torch.int32 or not vad.is_cuda:
+        raise ValueError("vad_segments: vad must be a [B, Tcap] int32 cuda tensor")
+    B, Tcap = vad.shape
+    dev = vad.device
+    vad = vad.contiguous()
+    tdev = torch.as_tensor(_host_ints(T, np.int32)).to(dev)
+    if tdev.numel() != B:
+        raise ValueError("vad_segments: T has %d entries for %d rows" % (tdev.numel(), B))
+    nseg = torch.empty(B, dtype=torch.int32, device=dev)
+    cap = SEGMENT_CAP
+    while True:
+        seg = torch.empty(B, cap, 2, dtype=torch.int32, device=dev)
+        hip.call("spk_vad_segments", hip.ptr(vad), hip.ptr(tdev), B, Tcap, int(opts.padding), int(opts.max_gap), int(opts.min_length),
+                 hip.ptr(seg), cap, hip.ptr(nseg), hip.stream())
+        n = nseg.cpu().numpy().astype(np.int64)
+        if n.size == 0 or int(n.max()) <= cap:
+            break
+        cap = int(n.max())
+    written = torch.arange(cap, device=dev)[None, :] < nseg[:, None]
+    pairs = seg[written].cpu().numpy().astype(np.int64)        # [sum n, 2], row-major: by row, then in order
+    return np.repeat(np.arange(B, dtype=np.int64), n), np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+
+
 def _cmn_select(x, T, idx, count, cmn, Tout):
     B, F, Tcap = x.shape
     dev = x.device
@@ -1310,10 +1357,16 @@ class Frontend:
 
     input_rate: the rate of the samples handed in (one rate per batch; the call's input_rate overrides the constructor's), resampled
     to fbank_opts.sample_frequency first.  speed: a decimal string or Fraction ("0.9"): the audio is played `speed` times as fast,
-    i.e. resampled from input_rate * speed to sample_frequency - one resampling for both.  Every row must still hold a frame after it."""
+    i.e. resampled from input_rate * speed to sample_frequency - one resampling for both.  Every row must still hold a frame after it.
 
-    def __init__(self, fbank_opts, vad=None, cmn=None, input_rate=None, speed=None):
-        self.fbank_opts, self.vad_opts, self.cmn_opts = fbank_opts, vad, cmn
+    segments: a SegmentOptions (needs `vad`).  The call then returns (feats, T, (row, start, end)): the
+    features of ALL frames - the sliding CMN over all frames, no voiced-frame selection, lengths = the frame counts T - and the
+    speech segments that vad_segments makes of the VAD decisions, in frames of the recording."""
+
+    def __init__(self, fbank_opts, vad=None, cmn=None, input_rate=None, speed=None, segments=None):
+        if segments is not None and vad is None:
+            raise ValueError("Frontend: segments needs vad (the segments are made of the VAD decisions)")
+        self.fbank_opts, self.vad_opts, self.cmn_opts, self.segment_opts = fbank_opts, vad, cmn, segments
         self.input_rate = None if input_rate is None else _int_rate(input_rate, "Frontend")
         self.speed = speed
         self.rates(self.input_rate)     # refuse a bad speed / rate pair here, not at the first batch
@@ -1335,7 +1388,11 @@ class Frontend:
             if self.cmn_opts is not None:
                 feats = sliding_cmn(feats, T, self.cmn_opts)
             return feats, T
-        _, idx, cnt = vad(loge, T, self.vad_opts)
+        v, idx, cnt = vad(loge, T, self.vad_opts)
+        if self.segment_opts is not None:
+            if self.cmn_opts is not None:
+                feats = sliding_cmn(feats, T, self.cmn_opts)
+            return feats, T, vad_segments(v, T, self.segment_opts)
         return select_voiced(feats, T, idx, cnt, self.cmn_opts)
 
 

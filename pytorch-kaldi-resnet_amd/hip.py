@@ -104,6 +104,7 @@ _SIGS = {
     "spk_pcm16_to_f32": [_P, _P, _I, _L, _P, _P],
     "spk_fbank_dither_noise":[_P, _L, ctypes.c_ulonglong, _I, _I, _I, _P],
     "spk_vad_count": [_P, _P, _I, _I, _D, _D, _I, _D, _P, _P, _P, _P],
+    "spk_vad_segments": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P],
     "spk_cmn_select": [_P] * 6 + [_I] * 5 + [_P],
     "spk_resample_tile": [_I, _I, _I],
     "spk_resample_fwd": [_P, _P, _I, _L, _P, _P, _I, _I, _I, _P, _P, _L, _P],

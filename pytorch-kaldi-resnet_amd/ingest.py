@@ -274,6 +274,112 @@ def window_batches(length, batch_size, max_pad_ratio=0.1, quantum=8):
     return pad_batches(length, batch_size, max_pad_ratio, quantum)
 
 
+# ---- speech segments: VAD decisions -> segments, and the windows inside them ----
+def segments_from_vad(v, T, opts):
+    """The segment rule of include/spkhip.h: spk_vad_segments on the host (numpy only; the `host` back end of
+    scripts/vad_to_segments.py and the reference of features.vad_segments).  v [Tcap] or [B, Tcap]: frame t of row b is voiced iff
+    v[b, t] != 0 and t < T[b] (T clamped to [0, Tcap]; a scalar for one row).  opts: padding >= 0, max_gap >= 0, min_length >= 1
+    in frames (features.SegmentOptions).  -> (row, start, end), flat int64 arrays, one entry per segment in row and then time order."""
+    p, g, m = int(opts.padding), int(opts.max_gap), int(opts.min_length)
+    if p < 0 or g < 0 or m < 1:
+        raise ValueError("segments_from_vad: padding >= 0, max_gap >= 0 and min_length >= 1, got %d %d %d" % (p, g, m))
+    v = np.asarray(v)
+    if v.ndim == 1:
+        v = v[None, :]
+    if v.ndim != 2:
+        raise ValueError("segments_from_vad: v must be [Tcap] or [B, Tcap], got shape %s" % (v.shape,))
+    B, Tcap = v.shape
+    Tv = np.clip(np.asarray(T, dtype=np.int64).reshape(-1), 0, Tcap)
+    if Tv.shape != (B,):
+        raise ValueError("segments_from_vad: T has %d entries for %d rows" % (Tv.size, B))
+    voiced = np.zeros((B, Tcap + 2), dtype=np.int8)           # a silent frame on either side: every run has both edges
+    voiced[:, 1:-1] = (v != 0) & (np.arange(Tcap)[None, :] < Tv[:, None])
+    d = np.diff(voiced, axis=1)                                # [B, Tcap + 1]: +1 at a run's first frame, -1 at its exclusive end
+    row, s = np.nonzero(d == 1)                                # row-major: by row, then ascending
+    e = np.nonzero(d == -1)[1]
+    a = np.maximum(s - p, 0)
+    b = np.minimum(e + p, Tv[row])
+    opens = np.ones(row.size, dtype=bool)
+    opens[1:] = (row[1:] != row[:-1]) | (a[1:] - b[:-1] > g)
+    first = np.nonzero(opens)[0]
+    last = np.append(first[1:], row.size)[:first.size] - 1     # the last run of each segment (none without a run)
+    seg_row, seg_a, seg_b = row[first], a[first], b[last]
+    keep = seg_b - seg_a >= m
+    return seg_row[keep].astype(np.int64), seg_a[keep].astype(np.int64), seg_b[keep].astype(np.int64)
+
+
+SegmentWindowPlan = collections.namedtuple("SegmentWindowPlan", "utt start length seg skipped")
+SegmentWindowPlan.__doc__ = """plan_segment_windows' result: flat int64 arrays, one entry per window in segment order and then window
+order - the utterance, the first frame IN THE UTTERANCE, the frame count and the segment of the window - and `skipped`, the segments
+shorter than min_window (ascending)"""
+
+
+def plan_segment_windows(seg_utt, seg_start, seg_end, window, period, min_window):
+    """The window rule inside speech segments (numpy only): segment j = frames [seg_start[j], seg_end[j]) of utterance seg_utt[j]
+    gets exactly the windows of plan_windows([seg_end[j] - seg_start[j]], window, period, min_window), shifted by seg_start[j].
+    The segments come sorted by utterance, and ascending and disjoint within one (touching is allowed)."""
+    u = np.asarray(seg_utt, dtype=np.int64).reshape(-1)
+    s = np.asarray(seg_start, dtype=np.int64).reshape(-1)
+    e = np.asarray(seg_end, dtype=np.int64).reshape(-1)
+    if not u.size == s.size == e.size:
+        raise ValueError("plan_segment_windows: seg_utt, seg_start and seg_end have %d, %d and %d entries" % (u.size, s.size, e.size))
+
+    def refuse(mask, msg):
+        if mask.any():
+            j = int(np.nonzero(mask)[0][0])
+            raise ValueError("plan_segment_windows: segment %d (utterance %d, frames [%d, %d)) %s" % (j, u[j], s[j], e[j], msg))
+
+    refuse(s < 0, "starts before frame 0")
+    refuse(e <= s, "is empty")
+    if u.size:
+        refuse(np.append(False, u[1:] < u[:-1]), "comes after a segment of a later utterance: seg_utt must not decrease")
+        refuse(np.append(False, (u[1:] == u[:-1]) & (s[1:] < e[:-1])), "starts before the end of the segment before it")
+    plan = plan_windows(e - s, window, period, min_window)
+    return SegmentWindowPlan(u[plan.utt], plan.start + s[plan.utt], plan.length, plan.utt, plan.skipped)
+
+
+def time_to_frame(t, frame_shift):
+    """frame of a time: floor(t / frame_shift + 0.5), evaluated on the decimal values as written (t: the text of a segments file,
+    or a number taken by its shortest representation), so that a time on a half-frame boundary always rounds up"""
+    import fractions
+    import math
+    return math.floor(fractions.Fraction(str(t)) / fractions.Fraction(str(frame_shift)) + fractions.Fraction(1, 2))
+
+
+def read_segments_file(path, recordings, frame_shift):
+    """A Kaldi segments file, '<segment-id> <recording> <start s> <end s>' per line, for scripts/decode.py --segments ->
+    {recording: (start frames, end frames)}, int64 arrays ascending in time (time_to_frame; ends not yet clipped to the recording).
+    ValueError naming the lines: a malformed line, a recording that is not in `recordings`, a segment that is empty after rounding,
+    segments of one recording that overlap."""
+    known = set(recordings)
+    per = {}
+    for n, line in enumerate(open(path), 1):
+        tok = line.split()
+        if not tok:
+            continue
+        where = "%s:%d" % (path, n)
+        if len(tok) != 4:
+            raise ValueError("%s: expected '<segment-id> <recording> <start> <end>', got %r" % (where, line.rstrip("\n")))
+        try:
+            s, e = time_to_frame(tok[2], frame_shift), time_to_frame(tok[3], frame_shift)
+        except (ValueError, ZeroDivisionError):
+            raise ValueError("%s: times %r %r are not numbers" % (where, tok[2], tok[3]))
+        if tok[1] not in known:
+            raise ValueError("%s: recording %r is not in the wav.scp" % (where, tok[1]))
+        if s < 0 or e <= s:
+            raise ValueError("%s: segment %s is empty after rounding to frames [%d, %d)" % (where, tok[0], s, e))
+        per.setdefault(tok[1], []).append((s, e, n))
+    out = {}
+    for rec, segs in per.items():
+        segs.sort()
+        for (s0, e0, n0), (s1, e1, n1) in zip(segs, segs[1:]):
+            if s1 < e0:
+                raise ValueError("%s:%d and %s:%d: segments of recording %r overlap (frames [%d, %d) and [%d, %d))"
+                                 % (path, n0, path, n1, rec, s0, e0, s1, e1))
+        out[rec] = (np.array([s for s, _, _ in segs], dtype=np.int64), np.array([e for _, e, _ in segs], dtype=np.int64))
+    return out
+
+
 # ---- the draws of an epoch: one seeded index function for NativeTrainLoader (archives) and WavTrainLoader (audio) ----
 def read_utt2spkid(utt2spkid_file):
     utt2spk = {}

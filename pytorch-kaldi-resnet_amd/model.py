@@ -244,15 +244,19 @@ class NeuralSpeakerModel(nn.Module):
         activations that left fp16's range; a row with a non-zero count must be predicted again with precision="f32"."""
         return self.engine().predict(x, lengths, precision)
 
-    def predict_windows(self, x, lengths, window, period, min_window=None, average=False, precision="f32", batch_size=None):
+    def predict_windows(self, x, lengths, window, period, min_window=None, average=False, precision="f32", batch_size=None,
+                        segments=None):
         """Windowed extraction of a padded batch x [B, F, T] with per-utterance frame counts `lengths` (None: T each), eval mode
         only: a window of `window` frames every `period` frames (ingest.plan_windows; the last, shorter window of an utterance is
         kept when it has at least min_window frames, default 1; an utterance shorter than min_window yields none and is listed in
         engine().windows_skipped).  Each window is embedded alone, in batches of at most batch_size (default B) rows.
         -> (emb [N, 256], utt [N], start [N], length [N]) - one row per window, the last three numpy int64 - or, average=True,
         (emb [U', 256], utt [U']): the window embeddings of every utterance averaged with the window lengths as weights.
-        precision as in predict(); after an "f16" call engine().half_overflow [N] holds the count of every window."""
-        return self.engine().predict_windows(x, lengths, window, period, min_window, average, precision, batch_size)
+        precision as in predict(); after an "f16" call engine().half_overflow [N] holds the count of every window.
+        segments: (seg_utt, seg_start, seg_end), speech segments in utterance frames (features.vad_segments, or a segments file):
+        the windows are then planned inside every segment (ingest.plan_segment_windows), `start` stays in utterance frames and
+        engine().windows_skipped lists the segments shorter than min_window."""
+        return self.engine().predict_windows(x, lengths, window, period, min_window, average, precision, batch_size, segments)
 
     def loadParameters(self, loaded_state):
         """scripts/model.py:415-432: name match, strip 'module.', skip on shape mismatch, same messages."""

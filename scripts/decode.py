@@ -67,7 +67,20 @@ parser.add_argument("--window", type=int, default=None,
                          "least --min-window frames.  One vector per window under the key <utt>-<start:08d>-<end:08d> (frame "
                          "indices, end exclusive) and a file segments.<name> next to the embeddings with lines '<key> <utt> "
                          "<start s> <end s>'.  With --wav-scp the indices count the frames the model sees, that is after the VAD's "
-                         "frame selection")
+                         "frame selection; --vad-segments or --segments keep times in the recording")
+parser.add_argument("--vad-segments", action="store_true",
+                    help="with --wav-scp --vad-config --window: diarization-style extraction.  The VAD decisions become speech "
+                         "segments on the GPU (--seg-padding / --seg-max-gap / --seg-min-length), no frame is removed (the sliding "
+                         "CMN runs over the whole recording) and the windows slide inside every segment: keys and segments.<name> "
+                         "carry frames and times of the recording, and speech_segments.<name> lists the segments used")
+parser.add_argument("--seg-padding", type=int, default=None, help="with --vad-segments: frames added on both sides of a voiced run (default 10)")
+parser.add_argument("--seg-max-gap", type=int, default=None,
+                    help="with --vad-segments: padded runs at most this many frames apart are joined into one segment (default 30)")
+parser.add_argument("--seg-min-length", type=int, default=None, help="with --vad-segments: segments shorter than this are dropped (default 50)")
+parser.add_argument("--segments", default=None,
+                    help="with --wav-scp --window, instead of --vad-config / --vad-segments: a Kaldi segments file '<segment-id> "
+                         "<recording> <start s> <end s>' (recordings: the keys of --wav-scp); the windows slide inside these segments. "
+                         "Frame of a time t: floor(t / --frame-shift + 0.5); ends are clipped to the recording's frame count")
 parser.add_argument("--period", type=int, default=None, help="with --window: frames between window starts (default: --window)")
 parser.add_argument("--min-window", type=int, default=None,
                     help="with --window: shortest last window that is kept, and shortest utterance that is extracted at all "
@@ -120,6 +133,30 @@ def main():
             parser.error("--window and --period must be >= 1, got --window %d --period %d" % (args.window, args.period))
         if not 1 <= args.min_window <= args.window:
             parser.error("--min-window must lie in [1, --window %d], got %d" % (args.window, args.min_window))
+    if args.vad_segments and not (args.wav_scp and args.vad_config and args.window is not None):
+        parser.error("--vad-segments needs --wav-scp, --vad-config and --window")
+    for flag in ("seg_padding", "seg_max_gap", "seg_min_length"):
+        if getattr(args, flag) is not None and not args.vad_segments:
+            parser.error("--%s needs --vad-segments" % flag.replace("_", "-"))
+    if args.segments is not None:
+        if args.vad_config or args.vad_segments:
+            parser.error("--segments and --vad-config / --vad-segments are mutually exclusive (the file gives the segments)")
+        if not (args.wav_scp and args.window is not None):
+            parser.error("--segments needs --wav-scp and --window")
+    if args.vad_segments or args.segments is not None:
+        import pytorch_kaldi_resnet_amd  # noqa: F401
+        from pytorch_kaldi_resnet_amd import features, ingest
+        try:
+            if args.vad_segments:
+                d = features.SegmentOptions()
+                args.segment_opts = features.SegmentOptions(
+                    padding=d.padding if args.seg_padding is None else args.seg_padding,
+                    max_gap=d.max_gap if args.seg_max_gap is None else args.seg_max_gap,
+                    min_length=d.min_length if args.seg_min_length is None else args.seg_min_length)
+            else:
+                args.file_segments = ingest.read_segments_file(args.segments, features.read_wav_scp(args.wav_scp)[0], args.frame_shift)
+        except (OSError, ValueError) as e:
+            parser.error("--%s: %s" % ("vad-segments" if args.vad_segments else "segments", e))
     if args.pad_batches and not args.native_reader:
         parser.error("--pad-batches needs --native-reader")
     if args.pad_batches and args.chunk_size >= 0:
@@ -237,18 +274,23 @@ class WindowPredictor:
     --average-windows a row per window, keyed <utt>-<start:08d>-<end:08d>; with it a row per utterance, the length-weighted mean
     of its windows (spk_window_mean).  --half: the windows whose activations left fp16's range (engine().half_overflow, one count
     per window) are gathered and predicted again in fp32, before any averaging.  Utterances shorter than --min-window are named
-    on stderr and counted."""
+    on stderr and counted.  segments (--vad-segments / --segments): (row, start, end) speech segments of the batch in frames of the
+    recording; the windows slide inside them, the segments shorter than --min-window are the ones named and counted, and
+    self.speech_lines holds the speech_segments lines of the segments that were used."""
 
     def __init__(self, model, args):
         self.model, self.a = model, args
-        self.redone = self.total = self.skipped = self.utts = 0
+        self.redone = self.total = self.skipped = self.utts = self.segs = 0
+        self.speech_lines = []
 
-    def __call__(self, x, lengths, names):
+    def __call__(self, x, lengths, names, segments=None):
         from pytorch_kaldi_resnet_amd import ingest, ops
         a, m = self.a, self.model
         x = x.contiguous()
         lengths = np.asarray(lengths, dtype=np.int64)
         kw = dict(window=a.window, period=a.period, min_window=a.min_window, batch_size=a.batch_size)
+        if segments is not None:
+            kw["segments"] = segments
         if a.average_windows and not a.half:
             emb, utt = m.predict_windows(x, lengths, average=True, **kw)
         else:
@@ -265,8 +307,18 @@ class WindowPredictor:
                 uu, first = np.unique(utt, return_index=True)
                 emb, utt = ops.window_mean(emb, np.append(first, utt.size), length.astype(np.float32)), uu
         skipped = m.engine().windows_skipped
-        for b in skipped:
-            sys.stderr.write("=> skipping {}: {} frames, shorter than --min-window {}\n".format(names[b], int(lengths[b]), a.min_window))
+        if segments is None:
+            for b in skipped:
+                sys.stderr.write("=> skipping {}: {} frames, shorter than --min-window {}\n".format(names[b], int(lengths[b]), a.min_window))
+        else:
+            row, s0, s1 = segments
+            for j in skipped:
+                sys.stderr.write("=> skipping segment {}-{:08d}-{:08d}: shorter than --min-window {}\n".format(
+                    names[row[j]], int(s0[j]), int(s1[j]), a.min_window))
+            used = np.setdiff1d(np.arange(len(row)), skipped)
+            self.speech_lines = ["%s-%08d-%08d %s %.3f %.3f\n" % (names[row[j]], s0[j], s1[j], names[row[j]], s0[j] * a.frame_shift,
+                                                                  s1[j] * a.frame_shift) for j in used]
+            self.segs += len(row)
         self.skipped += len(skipped)
         self.utts += len(names)
         pred = emb.cpu().numpy()
@@ -280,7 +332,10 @@ class WindowPredictor:
     def report(self):
         if self.a.half:
             print("=> {} of {} windows left the fp16 range and were extracted in fp32".format(self.redone, self.total))
-        print("=> {} of {} utterances shorter than --min-window were skipped".format(self.skipped, self.utts))
+        if self.a.vad_segments or self.a.segments is not None:
+            print("=> {} of {} segments shorter than --min-window were skipped".format(self.skipped, self.segs))
+        else:
+            print("=> {} of {} utterances shorter than --min-window were skipped".format(self.skipped, self.utts))
 
 
 def _emit(f, seg, keys, pred, seglines, args):
@@ -411,6 +466,23 @@ def native_generator(model, args):
     predict.report()
 
 
+def _file_segments(per, names, lengths):
+    """--segments: the (row, start, end) of a batch of recordings from ingest.read_segments_file's table, ends clipped to the
+    recording's frame count; a segment that starts at or beyond it is reported and left out"""
+    row, start, end = [], [], []
+    for r, name in enumerate(names):
+        s, e = per.get(name, (np.zeros(0, dtype=np.int64),) * 2)
+        e = np.minimum(e, int(lengths[r]))
+        for j in np.nonzero(e <= s)[0]:
+            sys.stderr.write("=> skipping segment {}-{:08d}: it starts beyond the {} frames of the recording\n".format(name, int(s[j]), int(lengths[r])))
+        ok = e > s
+        row.append(np.full(int(ok.sum()), r, dtype=np.int64))
+        start.append(s[ok])
+        end.append(e[ok])
+    cat = lambda v: np.concatenate(v) if v else np.zeros(0, dtype=np.int64)
+    return cat(row), cat(start), cat(end)
+
+
 def wav_generator(model, args):
     """--wav-scp: batches of utterances of one sample rate sorted by sample count (at most 10 % padded samples; files at another
     rate than the fbank's are resampled on the GPU, given --allow-downsample / --allow-upsample) read by the native WAV reader into
@@ -420,7 +492,8 @@ def wav_generator(model, args):
     from pytorch_kaldi_resnet_amd import features, ingest, kaldi_io
     fb, vad_opts, cmn = features.options_from_configs(args.fbank_config, args.vad_config, args.cmn_window,
                                                       mfcc_config=args.mfcc_config or None)
-    frontend = features.Frontend(fb, vad_opts, cmn)
+    by_segment = args.vad_segments or args.segments is not None
+    frontend = features.Frontend(fb, vad_opts, cmn, segments=args.segment_opts if args.vad_segments else None)
     keys, table, batches, short = features.wav_scp_batches(args.wav_scp, fb, args.batch_size, args.allow_downsample,
                                                            args.allow_upsample)
     print("Totally " + str(len(keys)) + " samples")
@@ -440,6 +513,7 @@ def wav_generator(model, args):
 
     predict = Predictor(model, args.half) if args.window is None else WindowPredictor(model, args)
     seg = _segments_file(args, name)
+    speech = open(os.path.join(args.out_path, "speech_segments." + name), "w") if by_segment else None
     with open(os.path.join(args.out_path, name), "wb") as f, torch.no_grad(), ThreadPoolExecutor(1) as rd, \
             ThreadPoolExecutor(1) as wr:
         nxt = rd.submit(load, 0) if mine else None
@@ -449,8 +523,21 @@ def wav_generator(model, args):
             buf = nxt.result()
             nxt = rd.submit(load, n + 1) if n + 1 < len(mine) else None
             wave = buf.cuda(args.gpu, non_blocking=True)
-            feats, lengths = frontend(wave, table.nsamp[b], [features.utt_id(keys[i]) for i in b], seed,
-                                      input_rate=int(table.rate[b[0]]))        # a batch holds files of one rate
+            out = frontend(wave, table.nsamp[b], [features.utt_id(keys[i]) for i in b], seed,
+                           input_rate=int(table.rate[b[0]]))        # a batch holds files of one rate
+            if by_segment:      # every frame is kept: the windows slide inside the speech segments, times stay the recording's
+                feats, lengths = out[0], np.asarray(out[1], dtype=np.int64)
+                segments = out[2] if args.vad_segments else _file_segments(args.file_segments, [keys[i] for i in b], lengths)
+                for r in np.setdiff1d(np.arange(len(b)), segments[0]):
+                    print("=> skipping {}: no speech segment".format(keys[b[r]]))
+                pred, ks, seglines = predict(feats, lengths, [keys[i] for i in b], segments)
+                speech.write("".join(predict.speech_lines))
+                if pending is not None:
+                    pending.result()
+                pending = wr.submit(_emit, f, seg, ks, pred, seglines, args)
+                done += len(b)
+                continue
+            feats, lengths = out
             keep = np.nonzero(lengths > 0)[0]
             for r in np.nonzero(lengths == 0)[0]:
                 print("=> skipping {}: no voiced frames".format(keys[b[r]]))
@@ -471,6 +558,8 @@ def wav_generator(model, args):
             pending.result()
         if seg is not None:
             seg.close()
+        if speech is not None:
+            speech.close()
         dt = time.time() - t0
         print("=> extracted {} utterances in {:.2f} s ({:.0f} utt/s, read + front end + predict + write)".format(
             done, dt, done / max(dt, 1e-9)))
