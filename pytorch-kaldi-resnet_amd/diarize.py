@@ -624,7 +624,8 @@ def read_reco2num_spk(path):
 
 
 def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=None, recordings=None, backend="host", channel=0,
-            return_scores=False, vbx=None, target_energy=None, ws_budget_bytes=1 << 31, **score_args):
+            return_scores=False, vbx=None, target_energy=None, ws_budget_bytes=1 << 31, ref=None, tune=None, uem=None, der_collar=0.25,
+            der_ignore_overlap=False, der_tick=0.001, **score_args):
     """embeddings: key -> vector (scoring.read_embeddings), segments: read_segments' list; exactly one of threshold and
     reco2num_spk (recording -> speakers).  -> dict(recordings, rec_off, mat_off, keys (batch order), labels, scores (numpy with
     return_scores, else None: on `hip` the matrices then never leave the device), rttm (lines), merges, merge_cost, n_merges).
@@ -632,8 +633,17 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
     then seed VBx (section 6o; kind must be plda), `labels` and `rttm` hold its result and the dict gains ahc_labels, vbx_elbo,
     vbx_n_iters and vbx_pi; on `hip` the rows stay on the device between scoring and VBx.  target_energy: None, or the energy in
     (0, 1) of the per-recording PCA (section 6p; kind must be plda): the clustering then runs on the adapted scores and the dict gains
-    pca_dim (one int per recording); VBx keeps the global rows and the global psi.  ws_budget_bytes: as in pca_rows, cluster, vbx."""
-    if (threshold is None) == (reco2num_spk is None):
+    pca_dim (one int per recording); VBx keeps the global rows and the global psi.  ws_budget_bytes: as in pca_rows, cluster, vbx.
+    ref: None, or the reference (an RTTM path or parse_rttm's dict): the dict gains `der`, der()'s result for the RTTM lines returned
+    (section 6r; uem, der_collar, der_ignore_overlap and der_tick are der()'s uem, collar, ignore_overlap and tick).  tune: None, or
+    thresholds to sweep in place of `threshold` (needs ref): the recordings are clustered once, tune_threshold scores every cut, and
+    every output is that of the best threshold; the dict gains der_table, best_threshold and der_host_jobs."""
+    if tune is not None:
+        if threshold is not None or reco2num_spk is not None:
+            raise ValueError("tune takes the place of threshold and reco2num_spk")
+        if ref is None:
+            raise ValueError("tune needs the reference (ref)")
+    elif (threshold is None) == (reco2num_spk is None):
         raise ValueError("give exactly one of threshold and reco2num_spk")
     if vbx is not None:
         if kind != "plda":
@@ -662,8 +672,18 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
     U, q, g, K, extra = _inputs(np.asarray(emb), rec, kind, target_energy, vbx is not None, backend=backend,
                                 ws_budget_bytes=ws_budget_bytes, **score_args)
     scores = _score_rows(U, q, g, K, rec, backend, backend == "hip")
-    labels, merges, cost, nm = cluster(scores, rec, threshold, num, backend, ws_budget_bytes)
     segs = [segments[i] for i in flat]
+    der_args = dict(uem=uem, collar=der_collar, ignore_overlap=der_ignore_overlap, tick=der_tick)
+    if tune is None:
+        labels, merges, cost, nm = cluster(scores, rec, threshold, num, backend, ws_budget_bytes)
+    else:
+        ref = _load(ref, read_rttm)
+        _, merges, cost, nm = cluster(scores, rec, None, None, backend, ws_budget_bytes)
+        tt = tune_threshold((merges, cost, nm), segs, ref, tune, backend=backend, ws_budget_bytes=ws_budget_bytes, **der_args)
+        labels, nm = tt["labels"][tt["best_index"]].copy(), tt["prefix"][:, tt["best_index"]].astype(np.int32)
+        past = np.arange(rec.Ntot) - np.repeat(rec.rec_off[:-1], rec.n) >= np.repeat(nm, rec.n)
+        merges, cost = np.where(past[:, None], 0, merges).astype(np.int32), np.where(past, 0.0, cost)   # (as a run at that threshold leaves them)
+        extra.update({"der_table": tt["table"], "best_threshold": tt["best_threshold"], "der_host_jobs": tt["host_jobs"]})
     if vbx is not None:
         res = _vbx(extra.pop("X"), extra.pop("Phi"), rec, init_labels=labels, backend=backend, ws_budget_bytes=ws_budget_bytes, **vbx)
         extra.update({"ahc_labels": labels, "vbx_elbo": res["elbo"], "vbx_n_iters": res["n_iters"], "vbx_pi": res["pi"]})
@@ -672,4 +692,486 @@ def diarize(embeddings, segments, kind="cosine", threshold=None, reco2num_spk=No
            "scores": None if not return_scores else (scores.cpu().numpy() if hasattr(scores, "cpu") else scores), "rttm": make_rttm(segs, labels.tolist(), channel),
            "merges": merges, "merge_cost": cost, "n_merges": nm}
     out.update(extra)
+    if ref is not None:
+        out["der"] = der(ref, parse_rttm(out["rttm"], "the result"), backend=backend, ws_budget_bytes=ws_budget_bytes, **der_args)
     return out
+
+
+# ---- scoring: the diarization error rate -----------------------------------------------------------------------
+def to_ticks(t, tick=0.001):
+    """tick(t) = floor(t / tick_s + 0.5) as int64 (a number or an array)"""
+    return np.floor(np.asarray(t, dtype=np.float64) / float(tick) + 0.5).astype(np.int64)
+
+
+def _rttm_fields(f, where):
+    """the fields of one SPEAKER line -> (recording, speaker, start, dur)"""
+    if len(f) < 8:
+        raise ValueError("%s: expected 'SPEAKER <recording> <channel> <start> <dur> <NA> <NA> <speaker> ...', got %r" % (where, " ".join(f)))
+    try:
+        start, dur = float(f[3]), float(f[4])
+    except ValueError:
+        raise ValueError("%s: start and duration must be numbers, got %r and %r" % (where, f[3], f[4]))
+    if not (np.isfinite(start) and np.isfinite(dur)) or dur < 0:
+        raise ValueError("%s: start must be finite and the duration finite and not negative, got %r and %r" % (where, f[3], f[4]))
+    return f[1], f[7], start, dur
+
+
+def parse_rttm(lines, name="rttm"):
+    """RTTM lines -> {recording: [(speaker, start s, dur s)]} in order of first appearance; lines of another type than SPEAKER and
+    empty lines are skipped; a bad line raises ValueError naming it as <name>:<line>"""
+    out = {}
+    for ln, line in enumerate(lines, 1):
+        f = line.split()
+        if not f or f[0] != "SPEAKER":
+            continue
+        reco, spk, start, dur = _rttm_fields(f, "%s:%d" % (name, ln))
+        out.setdefault(reco, []).append((spk, start, dur))
+    return out
+
+
+def read_rttm(path):
+    with open(path) as fh:
+        return parse_rttm(fh, path)
+
+
+def read_uem(path):
+    """'<recording> <channel> <start s> <end s>' lines -> {recording: [(start, end)]}; a bad line raises ValueError naming it"""
+    out = {}
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            f = line.split()
+            if not f:
+                continue
+            if len(f) != 4:
+                raise ValueError("%s:%d: expected '<recording> <channel> <start> <end>', got %r" % (path, ln, line.strip()))
+            try:
+                start, end = float(f[2]), float(f[3])
+            except ValueError:
+                raise ValueError("%s:%d: start and end must be numbers, got %r and %r" % (path, ln, f[2], f[3]))
+            if not (np.isfinite(start) and np.isfinite(end)) or end < start:
+                raise ValueError("%s:%d: the region must be finite and must not end before it starts, got %r and %r" % (path, ln, f[2], f[3]))
+            out.setdefault(f[0], []).append((start, end))
+    return out
+
+
+def _union(s, e):
+    """intervals [s, e) (int64 arrays; empty ones dropped) -> (starts, ends) of their union, sorted and disjoint (touching ones joined)"""
+    s, e = np.asarray(s, dtype=np.int64), np.asarray(e, dtype=np.int64)
+    keep = e > s
+    s, e = s[keep], e[keep]
+    if s.size == 0:
+        return s, e
+    o = np.argsort(s, kind="stable")
+    s, e = s[o], e[o]
+    run = np.maximum.accumulate(e)
+    new = np.concatenate([[True], s[1:] > run[:-1]])
+    first = np.nonzero(new)[0]
+    return s[first], run[np.concatenate([first[1:] - 1, [s.size - 1]])]
+
+
+def _covers(s, e, a):
+    """is point a[k] inside the sorted disjoint intervals [s, e)? -> (bool [len(a)], index of the interval or -1)"""
+    if s.size == 0:
+        return np.zeros(a.shape, dtype=bool), np.full(a.shape, -1, dtype=np.int64)
+    i = np.searchsorted(s, a, side="right") - 1
+    ok = (i >= 0) & (a < e[np.maximum(i, 0)])
+    return ok, np.where(ok, i, -1)
+
+
+def der_reference(turns, uem=None, collar=0.25, ignore_overlap=False, tick=0.001):
+    """The reference side of one recording, prepared once: turns [(speaker, start s, dur s)], uem [(start s, end s)] or None ->
+    dict(speakers (names in order of first appearance), cs, ce int64 [nc]: the scored set S cut into cells - sorted disjoint intervals
+    on each of which the set of active reference speakers is constant -, act bool [Sr][nc], nr int64 [nc])"""
+    names = []
+    for t in turns:
+        if t[0] not in names:
+            names.append(t[0])
+    spk = np.array([names.index(t[0]) for t in turns], dtype=np.int64)
+    ts = to_ticks([t[1] for t in turns], tick) if turns else np.zeros(0, np.int64)
+    te = ts + (to_ticks([t[2] for t in turns], tick) if turns else np.zeros(0, np.int64))
+    keep = te > ts
+    spk, ts, te = spk[keep], ts[keep], te[keep]
+    c = int(to_ticks(collar, tick))
+    if uem is not None:
+        Ss, Se = _union(to_ticks([u[0] for u in uem], tick), to_ticks([u[1] for u in uem], tick))
+    elif ts.size:
+        Ss, Se = np.array([ts.min()]), np.array([te.max()])
+    else:
+        Ss, Se = np.zeros(0, np.int64), np.zeros(0, np.int64)
+    uni = [_union(ts[spk == i], te[spk == i]) for i in range(len(names))]
+    b = np.concatenate([ts, te])
+    Xs, Xe = _union(b - c, b + c) if c > 0 else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    pts = np.unique(np.concatenate([Ss, Se, Xs, Xe] + [v for u in uni for v in u]))
+    a, z = pts[:-1], pts[1:]
+    keep = _covers(Ss, Se, a)[0] & ~_covers(Xs, Xe, a)[0] if a.size else np.zeros(0, dtype=bool)
+    a, z = a[keep], z[keep]
+    act = np.array([_covers(u[0], u[1], a)[0] for u in uni], dtype=bool).reshape(len(names), a.size)
+    nr = act.sum(axis=0).astype(np.int64)
+    if ignore_overlap:
+        keep = nr < 2
+        a, z, act, nr = a[keep], z[keep], act[:, keep], nr[keep]
+    # (adjacent cells with the same speakers are joined: fewer cells, the same sums)
+    if a.size > 1:
+        same = (a[1:] == z[:-1]) & (act[:, 1:] == act[:, :-1]).all(axis=0)
+        first = np.nonzero(np.concatenate([[True], ~same]))[0]
+        last = np.concatenate([first[1:] - 1, [a.size - 1]])
+        a, z, act, nr = a[first], z[last], act[:, first], nr[first]
+    return {"speakers": names, "cs": a, "ce": z, "act": act, "nr": nr}
+
+
+def _assign(C):
+    """C int64 [a][b] >= 0 -> (opt, [(i, j)]): a one-to-one partial assignment that maximises the sum of C[i][j] (shortest augmenting
+    paths with potentials on -C, the smaller side as rows; exact in int64); pairs with C[i][j] = 0 are not reported"""
+    if C.shape[0] == 0 or C.shape[1] == 0:
+        return 0, []
+    tr = C.shape[0] > C.shape[1]
+    A = -(C.T if tr else C).astype(np.int64)
+    n, m = A.shape
+    INF = np.int64(1) << 61
+    u, v = np.zeros(n + 1, dtype=np.int64), np.zeros(m + 1, dtype=np.int64)
+    p, way = np.zeros(m + 1, dtype=np.int64), np.zeros(m + 1, dtype=np.int64)
+    for i in range(1, n + 1):
+        p[0], j0 = i, 0
+        minv = np.full(m + 1, INF, dtype=np.int64)
+        used = np.zeros(m + 1, dtype=bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            cur = A[i0 - 1] - u[i0] - v[1:]
+            upd = ~used[1:] & (cur < minv[1:])
+            minv[1:][upd] = cur[upd]
+            way[1:][upd] = j0
+            cand = np.where(used[1:], INF, minv[1:])
+            j1 = int(np.argmin(cand)) + 1
+            delta = cand[j1 - 1]
+            u[p[used]] += delta
+            v[used] -= delta
+            minv[~used] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    pairs = [((j - 1, int(p[j]) - 1) if tr else (int(p[j]) - 1, j - 1)) for j in range(1, m + 1) if p[j]]
+    pairs = sorted(q for q in pairs if C[q] > 0)
+    return int(sum(int(C[q]) for q in pairs)), pairs
+
+
+def _disjoint_pieces(lab, ps, pe):
+    """pieces (dense label, start, end) -> the same ticks per label as pieces that are disjoint within a label: sorted by (label,
+    start), a piece starts where the earlier pieces of its label end; empty ones are dropped"""
+    keep = pe > ps
+    lab, ps, pe = lab[keep], ps[keep], pe[keep]
+    if lab.size == 0:
+        return lab, ps, pe
+    o = np.lexsort((ps, lab))
+    lab, ps, pe = lab[o], ps[o], pe[o]
+    lo = int(min(ps.min(), 0))
+    big = int(pe.max()) - lo + 1
+    run = np.maximum.accumulate((pe - lo) + lab * big)              # the running end within a label (labels ascend)
+    prev = np.concatenate([[-1], run[:-1]])
+    cs = np.maximum(ps, np.where(prev >= lab * big, prev - lab * big + lo, ps))
+    keep = pe > cs
+    return lab[keep], cs[keep], pe[keep]
+
+
+def _score_host(prep, lab, ps, pe):
+    """One job by the rule of section 6r: the reference side of der_reference, hypothesis pieces (label, start, end: int arrays, any
+    labels, any order, overlapping freely) -> ((scored, miss, fa, conf, opt), [(reference speaker index, label)])"""
+    cs, ce, act, nr = prep["cs"], prep["ce"], prep["act"], prep["nr"]
+    uniq, inv = np.unique(np.asarray(lab, dtype=np.int64), return_inverse=True)
+    dl, ds, de = _disjoint_pieces(inv.astype(np.int64), np.asarray(ps, dtype=np.int64), np.asarray(pe, dtype=np.int64))
+    pts = np.unique(np.concatenate([cs, ce, ds, de]))
+    a = pts[:-1]
+    ln = np.diff(pts)
+    inS, cell = _covers(cs, ce, a) if a.size else (np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64))
+    ln = np.where(inS, ln, 0)
+    r = np.where(inS, nr[np.maximum(cell, 0)], 0) if nr.size else np.zeros(a.size, dtype=np.int64)
+    h = np.searchsorted(np.sort(ds), a, side="right") - np.searchsorted(np.sort(de), a, side="right")
+    scored = int((ln * r).sum())
+    miss = int((ln * np.maximum(r - h, 0)).sum())
+    fa = int((ln * np.maximum(h - r, 0)).sum())
+    both = int((ln * np.minimum(r, h)).sum())
+    C = np.zeros((act.shape[0], uniq.size), dtype=np.int64)
+    if ds.size and act.shape[0] and a.size:
+        k0, k1 = np.searchsorted(pts, ds), np.searchsorted(pts, de)          # the piece covers the elementary intervals k0 .. k1 - 1
+        cnt = k1 - k0
+        k = np.repeat(k0 - np.concatenate([[0], np.cumsum(cnt)[:-1]]), cnt) + np.arange(int(cnt.sum()))
+        j = np.repeat(dl, cnt)
+        sel = inS[k]
+        k, j = k[sel], j[sel]
+        np.add.at(C.T, j, (act[:, cell[k]] * ln[k][None, :]).T)
+    opt, pairs = _assign(C)
+    return (scored, miss, fa, both - opt, opt), [(i, int(uniq[j])) for i, j in pairs]
+
+
+def _der_value(miss, fa, conf, scored):
+    return float("nan") if scored == 0 else float(np.float64(miss + fa + conf) / np.float64(scored))
+
+
+def _prep_table(preps, max_ref):
+    """the reference sides as spk_der_batch takes them -> (rec_tab [R][4], cells [ncells][3]); a recording with more than max_ref
+    speakers gets Sr = -1 (its jobs are the host's)"""
+    rec_tab = np.zeros((len(preps), 4), dtype=np.int64)
+    cells, off = [], 0
+    for r, p in enumerate(preps):
+        Sr, nc = p["act"].shape
+        if Sr > max_ref:
+            rec_tab[r] = (off, 0, -1, 0)
+            continue
+        mask = np.zeros(nc, dtype=np.uint64)
+        for i in range(Sr):
+            mask |= p["act"][i].astype(np.uint64) << np.uint64(i)
+        cells.append(np.stack([p["cs"], p["ce"], mask.view(np.int64)], axis=1) if nc else np.zeros((0, 3), dtype=np.int64))
+        rec_tab[r] = (off, nc, Sr, 0)
+        off += nc
+    return rec_tab, (np.concatenate(cells) if cells else np.zeros((0, 3), dtype=np.int64))
+
+
+def score_jobs(preps, jobs, backend="host", ws_budget_bytes=1 << 31):
+    """preps: der_reference's dict per recording; jobs: [(recording index, labels, starts, ends)] (int arrays in ticks) -> (ints int64
+    [J][5] = scored, miss, fa, conf, opt; mappings: per job [(reference speaker index, label)]; host_jobs: how many jobs the `hip` back
+    end left to the host rule because they exceed the device limits).  Both back ends give the same integers."""
+    J = len(jobs)
+    ints, maps, on_host = np.zeros((J, 5), dtype=np.int64), [None] * J, list(range(J))
+    if backend == "hip" and J:
+        import torch
+        from . import ops
+        max_ref, max_hyp, max_turns = ops.der_limits()
+        rec_tab, cells = _prep_table(preps, max_ref)
+        dev_jobs, tab, labs, off, uniqs = [], [], [], 0, {}
+        for x, (r, lab, ps, pe) in enumerate(jobs):
+            uniq, inv = np.unique(np.asarray(lab, dtype=np.int64), return_inverse=True)
+            if rec_tab[r, 2] < 0 or uniq.size > max_hyp or inv.size > max_turns:
+                continue
+            dev_jobs.append(x)
+            uniqs[x] = uniq
+            tab.append((r, off, inv.size, uniq.size))
+            labs.append((inv + 1, ps, pe))
+            off += inv.size
+        on_host = [x for x in range(J) if x not in uniqs]
+        if dev_jobs:
+            rec_tab[rec_tab[:, 2] < 0, 2] = 0
+            cat = [np.concatenate([t[c] for t in labs]) for c in range(3)]
+            up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v, dtype=dt)).cuda()
+            out, mp = ops.der_batch(rec_tab, cells, tab, up(cat[0], np.int32), up(cat[1], np.int64), up(cat[2], np.int64), ws_budget_bytes)
+            out, mp = out.cpu().numpy(), mp.cpu().numpy()
+            for y, x in enumerate(dev_jobs):
+                ints[x] = out[y]
+                maps[x] = [(i, int(uniqs[x][l - 1])) for i, l in enumerate(mp[y][:preps[jobs[x][0]]["act"].shape[0]]) if l > 0]
+    else:
+        assert backend == "host" or not J, backend
+    for x in on_host:
+        r, lab, ps, pe = jobs[x]
+        ints[x], maps[x] = _score_host(preps[r], lab, ps, pe)
+    return ints, maps, (len(on_host) if backend == "hip" else 0)
+
+
+def _turn_ticks(turns, tick):
+    """[(speaker, start s, dur s)] -> (dense labels from 1 in order of first appearance, names, starts, ends in ticks)"""
+    names = []
+    for t in turns:
+        if t[0] not in names:
+            names.append(t[0])
+    lab = np.array([names.index(t[0]) + 1 for t in turns], dtype=np.int64)
+    s = to_ticks([t[1] for t in turns], tick) if turns else np.zeros(0, np.int64)
+    return lab, names, s, s + (to_ticks([t[2] for t in turns], tick) if turns else np.zeros(0, np.int64))
+
+
+def _summary(order, ints, maps=None):
+    per = {}
+    for x, reco in enumerate(order):
+        scored, miss, fa, conf, opt = (int(v) for v in ints[x])
+        per[reco] = {"scored": scored, "miss": miss, "fa": fa, "conf": conf, "opt": opt, "der": _der_value(miss, fa, conf, scored)}
+        if maps is not None:
+            per[reco]["mapping"] = maps[x]
+    tot = {k: sum(p[k] for p in per.values()) for k in ("scored", "miss", "fa", "conf", "opt")}
+    tot["der"] = _der_value(tot["miss"], tot["fa"], tot["conf"], tot["scored"])
+    return per, tot
+
+
+def _load(v, reader):
+    return reader(v) if isinstance(v, (str, bytes)) or hasattr(v, "__fspath__") else v
+
+
+def der(ref, hyp, uem=None, collar=0.25, ignore_overlap=False, tick=0.001, backend="host", ws_budget_bytes=1 << 31):
+    """The diarization error rate of section 6r.  ref, hyp: an RTTM path or {recording: [(speaker, start s, dur s)]}; uem: a UEM path,
+    {recording: [(start s, end s)]} or None.  -> dict(recordings; per_recording: recording -> dict(scored, miss, fa, conf, opt: ints in
+    ticks, der, mapping: {reference speaker: hypothesis speaker}); total: the integers summed and their der; host_jobs).  A recording
+    the hypothesis lacks is all miss; one the reference lacks raises ValueError unless the UEM covers it (it is then all false alarm)."""
+    ref, hyp, uem = _load(ref, read_rttm), _load(hyp, read_rttm), (None if uem is None else _load(uem, read_uem))
+    if not tick > 0:
+        raise ValueError("tick must be positive, got %r" % (tick,))
+    if not collar >= 0:
+        raise ValueError("collar must not be negative, got %r" % (collar,))
+    extra = [r for r in hyp if r not in ref and not (uem is not None and r in uem)]
+    if extra:
+        raise ValueError("recordings of the hypothesis that the reference lacks: " + " ".join(extra[:5]))
+    order = list(ref) + [r for r in hyp if r not in ref]
+    preps = [der_reference(ref.get(r, []), None if uem is None else uem.get(r), collar, ignore_overlap, tick) for r in order]
+    jobs, names = [], []
+    for x, r in enumerate(order):
+        lab, nm, s, e = _turn_ticks(hyp.get(r, []), tick)
+        jobs.append((x, lab, s, e))
+        names.append(nm)
+    ints, maps, host_jobs = score_jobs(preps, jobs, backend, ws_budget_bytes)
+    maps = [{preps[x]["speakers"][i]: names[x][l - 1] for i, l in m} for x, m in enumerate(maps)]
+    per, tot = _summary(order, ints, maps)
+    return {"recordings": order, "per_recording": per, "total": tot, "host_jobs": host_jobs}
+
+
+# ---- cutting one merge list at many thresholds ------------------------------------------------------------------------------------------
+def _prefix_len(cost, nm, th):
+    """per threshold of th [K]: the merges of the longest prefix of cost[:nm] whose costs all satisfy c <= -t -> int64 [K]"""
+    if nm <= 0:
+        return np.zeros(th.size, dtype=np.int64)
+    bad = ~(cost[:nm, None] <= -th[None, :])
+    return np.where(bad.any(axis=0), bad.argmax(axis=0), nm).astype(np.int64)
+
+
+def _thresholds(thresholds):
+    th = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+    if th.ndim != 1 or th.size < 1 or np.isnan(th).any():
+        raise ValueError("thresholds must be one or more numbers, none of them NaN")
+    return th
+
+
+def cut_merges(merges, merge_cost, n_merges, rec_off, thresholds, backend="host"):
+    """merges [Ntot][2], merge_cost [Ntot], n_merges [R] as cluster returns them (numpy, or on `hip` device tensors) -> labels int32
+    [K][Ntot]: row k equals the labels of cluster(scores, rec_off, threshold=thresholds[k]) bit for bit - the merge sequence does not
+    depend on the threshold, so a cut applies a prefix of it."""
+    rec = RecBatch.of(rec_off)
+    th = _thresholds(thresholds)
+    if backend == "hip":
+        import torch
+        from . import ops
+        up = lambda v, dt: v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=dt)).cuda()
+        return ops.ahc_cut_batch(up(merges, np.int32), up(merge_cost, np.float64), up(n_merges, np.int32), rec, th).cpu().numpy()
+    assert backend == "host", backend
+    host = lambda v: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v)
+    merges, cost, nm = host(merges).astype(np.int64), host(merge_cost).astype(np.float64), host(n_merges)
+    ro = rec.rec_off
+    out = np.empty((th.size, rec.Ntot), dtype=np.int32)
+    for r in range(rec.R):
+        n = int(rec.n[r])
+        for k, L in enumerate(_prefix_len(cost[ro[r]:ro[r + 1]], min(max(int(nm[r]), 0), n - 1), th)):
+            parent = np.arange(n)
+            parent[merges[ro[r]:ro[r] + L, 1]] = merges[ro[r]:ro[r] + L, 0]
+            while True:
+                nxt = parent[parent]
+                if (nxt == parent).all():
+                    break
+                parent = nxt
+            out[k, ro[r]:ro[r + 1]] = np.cumsum(parent == np.arange(n))[parent]
+    return out
+
+
+def cut_pieces(wstart, wend, labels):
+    """The hypothesis of a cut for one recording: windows in ticks sorted by (start, end) and their labels -> (starts, ends) with
+    make_rttm's adjacent-pair cut at (a + b) // 2"""
+    s, e = np.array(wstart, dtype=np.int64), np.array(wend, dtype=np.int64)
+    lab = np.asarray(labels)
+    if s.size > 1:
+        cut = (lab[1:] != lab[:-1]) & (wstart[1:] < wend[:-1])
+        mid = (np.asarray(wstart[1:], dtype=np.int64) + np.asarray(wend[:-1], dtype=np.int64)) >> 1
+        s[1:] = np.where(cut, mid, s[1:])
+        e[:-1] = np.where(cut, mid, e[:-1])
+    return s, e
+
+
+def _segment_batch(segments):
+    """segments in batch order -> (recordings, rec_off); the windows of a recording must follow one another"""
+    order, counts = [], []
+    for s in segments:
+        if order and s[1] == order[-1]:
+            counts[-1] += 1
+        else:
+            if s[1] in order:
+                raise ValueError("the windows of recording %s do not follow one another" % s[1])
+            order.append(s[1])
+            counts.append(1)
+    if not order:
+        raise ValueError("no windows")
+    return order, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def tune_threshold(scores_or_merges, segments, ref, thresholds, uem=None, collar=0.25, ignore_overlap=False, tick=0.001,
+                   backend="host", ws_budget_bytes=1 << 31):
+    """Sweeps the stopping threshold: one clustering, K cuts, R x K scorings.  scores_or_merges: the flat scores of score_dense (the
+    recordings are then clustered once, to one cluster) or cluster's (merges, merge_cost, n_merges); segments: (key, recording, start s,
+    end s) per window in batch order; ref: an RTTM path or dict; thresholds: K numbers.  -> dict(table: [(threshold, miss, fa, conf,
+    scored, DER)] over all recordings; best_threshold, best_index: the smallest miss + fa + conf, ties to the first; per_recording
+    int64 [R][K][5]; labels int32 [K][Ntot] (the cuts); prefix int32 [R][K] (merges applied); host_jobs: jobs the `hip` back end left
+    to the host rule).  Thresholds that apply the same prefix to a recording share one scoring.  On `hip` the labels and the pieces
+    stay on the device between the cut and the scoring."""
+    th = _thresholds(thresholds)
+    order, rec_off = _segment_batch(segments)
+    rec = RecBatch(rec_off, len(segments))
+    ref, uem = _load(ref, read_rttm), (None if uem is None else _load(uem, read_uem))
+    absent = [r for r in order if r not in ref and not (uem is not None and r in uem)]
+    if absent:
+        raise ValueError("recordings that the reference lacks: " + " ".join(absent[:5]))
+    if isinstance(scores_or_merges, (tuple, list)) and len(scores_or_merges) == 3:
+        merges, cost, nm = scores_or_merges
+    else:
+        merges, cost, nm = cluster(scores_or_merges, rec, None, None, backend, ws_budget_bytes)[1:]
+    host = lambda v: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v)
+    cost_h, nm_h = host(cost).astype(np.float64), host(nm)
+    R, K, ro = rec.R, th.size, rec.rec_off
+    prefix = np.array([_prefix_len(cost_h[ro[r]:ro[r + 1]], min(max(int(nm_h[r]), 0), int(rec.n[r]) - 1), th) for r in range(R)],
+                      dtype=np.int32)
+    preps = [der_reference(ref.get(r, []), None if uem is None else uem.get(r), collar, ignore_overlap, tick) for r in order]
+    ws = to_ticks([s[2] for s in segments], tick)
+    we = to_ticks([s[3] for s in segments], tick)
+    perm = np.concatenate([ro[r] + np.lexsort((we[ro[r]:ro[r + 1]], ws[ro[r]:ro[r + 1]])) for r in range(R)])
+    ws, we = ws[perm], we[perm]
+    ints = np.zeros((R, K, 5), dtype=np.int64)
+    host_jobs = 0
+    if backend == "hip":
+        import torch
+        from . import ops
+        up = lambda v, dt: v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=dt)).cuda()
+        lab_d = ops.ahc_cut_batch(up(merges, np.int32), up(cost, np.float64), up(nm, np.int32), rec, th)
+        srt_d = lab_d if (perm == np.arange(perm.size)).all() else lab_d.index_select(1, up(perm, np.int64)).contiguous()
+        ps_d, pe_d = ops.der_pieces(srt_d, up(ws, np.int64), up(we, np.int64), rec)
+        max_ref, max_hyp, max_turns = ops.der_limits()
+        rec_tab, cells = _prep_table(preps, max_ref)
+        Sh = rec.n[:, None] - prefix
+        dev = (rec_tab[:, 2] >= 0)[:, None] & (Sh <= max_hyp) & (rec.n <= max_turns)[:, None]
+        first = np.array([(lambda u: u[1][u[2]])(np.unique(prefix[r], return_index=True, return_inverse=True)) for r in range(R)])
+        own = first == np.arange(K)[None, :]                         # (thresholds with the same prefix share one job)
+        rk = np.argwhere(dev & own)
+        labels = None
+        if rk.size:
+            rec_tab[rec_tab[:, 2] < 0, 2] = 0
+            tab = np.stack([rk[:, 0], rk[:, 1] * rec.Ntot + ro[rk[:, 0]], rec.n[rk[:, 0]], Sh[rk[:, 0], rk[:, 1]]], axis=1)
+            out = ops.der_batch(rec_tab, cells, tab, srt_d.view(-1), ps_d.view(-1), pe_d.view(-1), ws_budget_bytes)[0]
+            ints[rk[:, 0], rk[:, 1]] = out.cpu().numpy()
+        rest = np.argwhere(~dev & own)
+        host_jobs = len(rest)
+        labels = lab_d.cpu().numpy()
+        for r, k in rest:
+            lab = labels[k, perm[ro[r]:ro[r + 1]]]
+            s, e = cut_pieces(ws[ro[r]:ro[r + 1]], we[ro[r]:ro[r + 1]], lab)
+            ints[r, k] = _score_host(preps[r], lab, s, e)[0]
+        ints = ints[np.arange(R)[:, None], first]
+    else:
+        assert backend == "host", backend
+        labels = cut_merges(merges, cost, nm, rec, th, "host")
+        for r in range(R):
+            seen = {}
+            for k in range(K):
+                if prefix[r, k] not in seen:                        # (thresholds with the same prefix have the same hypothesis)
+                    lab = labels[k, perm[ro[r]:ro[r + 1]]]
+                    s, e = cut_pieces(ws[ro[r]:ro[r + 1]], we[ro[r]:ro[r + 1]], lab)
+                    seen[prefix[r, k]] = _score_host(preps[r], lab, s, e)[0]
+                ints[r, k] = seen[prefix[r, k]]
+    tot = ints.sum(axis=0)
+    table = [(float(th[k]), int(tot[k, 1]), int(tot[k, 2]), int(tot[k, 3]), int(tot[k, 0]),
+              _der_value(int(tot[k, 1]), int(tot[k, 2]), int(tot[k, 3]), int(tot[k, 0]))) for k in range(K)]
+    err = tot[:, 1] + tot[:, 2] + tot[:, 3]
+    best = int(np.argmin(err))                                      # (the first of equal sums)
+    return {"table": table, "best_threshold": float(th[best]), "best_index": best, "per_recording": ints, "labels": labels,
+            "prefix": prefix, "recordings": order, "host_jobs": host_jobs}

@@ -150,6 +150,17 @@ _SIGS = {
     "spk_augment_fwd": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P],
 }
 
+# diarization scoring (include/spkder.h, csrc/der.hip): declared in a header of its own and counted apart from include/spkhip.h
+_DER_SIGS = {
+    "spk_ahc_cut_batch": [_P] * 6 + [_I, _P, _L, _I, _P],
+    "spk_der_pieces": [_P] * 5 + [_I, _P, _P, _L, _I, _P],
+    "spk_der_max_ref": [],
+    "spk_der_max_hyp": [],
+    "spk_der_max_turns": [],
+    "spk_der_ws_elems": [_I, _I, _I],                   # host only; returns long long
+    "spk_der_batch": [_P, _P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _L, _P, _L, _P, _P, _P],
+}
+
 _lib = None
 
 
@@ -188,13 +199,14 @@ def lib():
         l.spk_error_sweep_workspace.argtypes = [_I, _I]
         l.spk_scatter_f64_workspace.restype = ctypes.c_size_t
         l.spk_scatter_f64_workspace.argtypes = [_L, _I]
-        for name, sig in _SIGS.items():
+        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()):
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
         l.spk_vbx_ws_elems.restype = ctypes.c_longlong
         l.spk_syevj_ws_elems.restype = ctypes.c_longlong
         l.spk_pca_plda_ws_elems.restype = ctypes.c_longlong
+        l.spk_der_ws_elems.restype = ctypes.c_longlong
         if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
             l.spk_stats_pool_row_form(0)
         _lib = l
@@ -209,6 +221,11 @@ def has_experimental():
 def exported_symbols():
     return ["spk_version", "spk_last_error", "spk_conv_wgrad_workspace", "spk_bn_finalize_workspace", "spk_gemm_workspace",
             "spk_sort_trials_workspace", "spk_error_sweep_workspace", "spk_scatter_f64_workspace"] + list(_SIGS)
+
+
+def der_symbols():
+    """the exports include/spkder.h declares"""
+    return list(_DER_SIGS)
 
 
 def ptr(t):

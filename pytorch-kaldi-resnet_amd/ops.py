@@ -1507,6 +1507,90 @@ def vbx_batch(X, Phi, rec, n_states, gamma, pi, Fa=0.3, Fb=17.0, loop_prob=0.99,
     return elbo, n_iters
 
 
+# ---- diarization scoring (csrc/der.hip) -----------------------------------------------------------------------
+def der_limits():
+    """(reference speakers, hypothesis labels, hypothesis pieces) one spk_der_batch job takes"""
+    l = hip.lib()
+    return l.spk_der_max_ref(), l.spk_der_max_hyp(), l.spk_der_max_turns()
+
+
+def der_ws_elems(pieces, Sr, Sh):
+    """8-byte words of workspace of one job; a shape over the limits raises"""
+    n = hip.lib().spk_der_ws_elems(int(pieces), int(Sr), int(Sh))
+    if n < 0:
+        hip.check(int(n), "spk_der_ws_elems")
+    return int(n)
+
+
+def ahc_cut_batch(merges, merge_cost, n_merges, rec, thresholds):
+    """merges int32 [Ntot][2], merge_cost float64 [Ntot], n_merges int32 [R]: device tensors as ahc_batch returns them; rec: a RecBatch
+    or host rec_off; thresholds [K] floats -> labels int32 [K][Ntot] on the device (spk_ahc_cut_batch)"""
+    b = _batch(rec)
+    dev = merges.device
+    th = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float64)).to(dev)
+    K = th.numel()
+    assert merges.dtype == torch.int32 and merges.shape == (b.Ntot, 2) and merge_cost.dtype == torch.float64 and merge_cost.numel() == b.Ntot
+    assert n_merges.dtype == torch.int32 and n_merges.numel() == b.R
+    labels = torch.empty(K, b.Ntot, device=dev, dtype=torch.int32)
+    call("spk_ahc_cut_batch", ptr(merges), ptr(merge_cost), ptr(n_merges), b.rec_off.ctypes.data, ptr(b.table(dev)), ptr(th), K,
+         ptr(labels), b.Ntot, b.R, stream(), nbytes=4.0 * K * b.Ntot)
+    return labels
+
+
+def der_pieces(labels, wstart, wend, rec):
+    """labels int32 [K][Ntot], wstart / wend int64 [Ntot] (ticks, the windows of every recording in (start, end) order): device tensors
+    -> (pstart, pend) int64 [K][Ntot]: the windows with the adjacent-pair midpoint cut (spk_der_pieces)"""
+    K, Ntot = labels.shape
+    b = _batch(rec, Ntot)
+    assert labels.dtype == torch.int32 and wstart.dtype == torch.int64 and wend.dtype == torch.int64
+    assert wstart.numel() == Ntot and wend.numel() == Ntot
+    ps, pe = torch.empty(K, Ntot, device=labels.device, dtype=torch.int64), torch.empty(K, Ntot, device=labels.device, dtype=torch.int64)
+    call("spk_der_pieces", ptr(labels), ptr(wstart), ptr(wend), b.rec_off.ctypes.data, ptr(b.table(labels.device)), K, ptr(ps), ptr(pe),
+         Ntot, b.R, stream(), nbytes=20.0 * K * Ntot)
+    return ps, pe
+
+
+def der_batch(rec_tab, cells, jobs, plab, pstart, pend, ws_budget_bytes=1 << 31):
+    """rec_tab int64 [R][4] = (first cell, cells, Sr, 0) and cells int64 [ncells][3] = (start, end, mask): host arrays, the reference
+    side of every recording; jobs int64 [J][4] = (recording, first piece, pieces, Sh): host; plab int32, pstart, pend int64 [npieces]:
+    device tensors -> (out int64 [J][5] = scored, miss, fa, conf, opt; mapping int32 [J][max_ref]) on the device (spk_der_batch), in
+    launches of consecutive jobs whose workspaces fit ws_budget_bytes (one job always goes).  A job over the limits raises."""
+    rec_tab = np.ascontiguousarray(rec_tab, dtype=np.int64).reshape(-1, 4)
+    cells = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1, 3)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1, 4)
+    J, R = jobs.shape[0], rec_tab.shape[0]
+    dev = plab.device
+    assert plab.dtype == torch.int32 and pstart.dtype == torch.int64 and pend.dtype == torch.int64
+    assert plab.is_contiguous() and pstart.is_contiguous() and pend.is_contiguous() and pstart.numel() == plab.numel() == pend.numel()
+    max_ref = hip.lib().spk_der_max_ref()
+    out = torch.zeros(J, 5, device=dev, dtype=torch.int64)
+    mapping = torch.full((J, max_ref), -1, device=dev, dtype=torch.int32)
+    if J == 0:
+        return out, mapping
+    if (jobs[:, 0] < 0).any() or (jobs[:, 0] >= R).any():
+        raise ValueError("der_batch: a job names a recording outside the table of %d" % R)
+    need = np.array([der_ws_elems(p, rec_tab[r, 2], sh) for r, _, p, sh in jobs], dtype=np.int64)
+    rt_dev = torch.from_numpy(rec_tab).to(dev)
+    cells_dev = torch.from_numpy(cells).to(dev) if cells.size else torch.zeros(1, 3, device=dev, dtype=torch.int64)
+    budget = max(int(ws_budget_bytes) // 8, 1)
+    lo = 0
+    while lo < J:
+        hi, tot = lo + 1, int(need[lo])
+        while hi < J and tot + int(need[hi]) <= budget:
+            tot += int(need[hi])
+            hi += 1
+        jt = np.zeros((hi - lo, 6), dtype=np.int64)
+        jt[:, :4] = jobs[lo:hi]
+        jt[1:, 4] = np.cumsum(need[lo:hi])[:-1]
+        jt_dev = torch.from_numpy(jt).to(dev)
+        ws = torch.empty(max(tot, 1), device=dev, dtype=torch.int64)
+        call("spk_der_batch", rec_tab.ctypes.data, ptr(rt_dev), ptr(cells_dev), cells.shape[0], R, jt.ctypes.data, ptr(jt_dev), hi - lo,
+             ptr(plab), ptr(pstart), ptr(pend), plab.numel(), ptr(ws), max(tot, 1), out[lo:hi].data_ptr(), mapping[lo:hi].data_ptr(),
+             stream(), nbytes=8.0 * tot)
+        lo = hi
+    return out, mapping
+
+
 # ---- per-recording PCA of the dense PLDA scores (csrc/pca.hip; DESIGN.md section 6p) ------------------------------------------------
 def syevj_max_dim():
     """the largest order spk_syevj_batch takes"""
