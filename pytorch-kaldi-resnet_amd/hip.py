@@ -161,6 +161,19 @@ _DER_SIGS = {
     "spk_der_batch": [_P, _P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _L, _P, _L, _P, _P, _P],
 }
 
+# calibration and fusion of trial scores (include/spkcal.h, csrc/cal.hip): the third header, counted apart from the other two
+_CAL_SIGS = {
+    "spk_cal_max_k": [],
+    "spk_cal_tile": [_I],
+    "spk_cal_apply": [_P, _P, _I, _P, _I, _P],
+    "spk_cal_cllr_ws_elems": [_I],                      # host only; the three *_ws_elems return long long
+    "spk_cal_train_ws_elems": [_I, _I],
+    "spk_cal_pav_ws_elems": [_I],
+    "spk_cal_cllr": [_P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _P],
+    "spk_cal_train": [_P, _P, _I, _I, _L, _D, _D, _D, _D, _I, _P, _P, _P, _L, _P],
+    "spk_cal_pav": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -199,7 +212,7 @@ def lib():
         l.spk_error_sweep_workspace.argtypes = [_I, _I]
         l.spk_scatter_f64_workspace.restype = ctypes.c_size_t
         l.spk_scatter_f64_workspace.argtypes = [_L, _I]
-        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()):
+        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()) + list(_CAL_SIGS.items()):
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
@@ -207,6 +220,8 @@ def lib():
         l.spk_syevj_ws_elems.restype = ctypes.c_longlong
         l.spk_pca_plda_ws_elems.restype = ctypes.c_longlong
         l.spk_der_ws_elems.restype = ctypes.c_longlong
+        for name in ("spk_cal_cllr_ws_elems", "spk_cal_train_ws_elems", "spk_cal_pav_ws_elems"):
+            getattr(l, name).restype = ctypes.c_longlong
         if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
             l.spk_stats_pool_row_form(0)
         _lib = l
@@ -226,6 +241,11 @@ def exported_symbols():
 def der_symbols():
     """the exports include/spkder.h declares"""
     return list(_DER_SIGS)
+
+
+def cal_symbols():
+    """the exports include/spkcal.h declares"""
+    return list(_CAL_SIGS)
 
 
 def ptr(t):

@@ -1686,3 +1686,75 @@ def affine_lennorm_rec(Z, rec, A_r, b_r, q_r, dim, scale):
     call("spk_affine_lennorm_rec", ptr(Z), b.rec_off.ctypes.data, ptr(b.table(Z.device)), ptr(A_r), ptr(b_r), ptr(q_r), ptr(dim),
          1 if scale else 0, ptr(U), Ntot, L, R, stream(), flops=2.0 * Ntot * L * L)
     return U
+
+
+# ---- calibration and fusion of trial scores (csrc/cal.hip) ------------------------------------------------------
+def cal_sizes():
+    """(trials per block, pools per PAV tile, doubles of the training state, threads per block) of csrc/cal.hip"""
+    l = hip.lib()
+    return tuple(l.spk_cal_tile(i) for i in range(4))
+
+
+def _cal_ws(name, *shape):
+    n = getattr(hip.lib(), name)(*shape)
+    if n < 0:
+        raise ValueError("%s%r: a shape the calibration kernels refuse" % (name, tuple(shape)))
+    return int(n)
+
+
+def cal_apply(cols, theta):
+    """cols [K][T] float64 (device), theta: host [K + 1] -> llr [T] float64 (spk_cal_apply)"""
+    K, T = cols.shape
+    assert cols.dtype == torch.float64 and cols.is_contiguous()
+    th = np.ascontiguousarray(theta, dtype=np.float64)
+    assert th.size == K + 1
+    llr = torch.empty(T, device=cols.device, dtype=torch.float64)
+    call("spk_cal_apply", ptr(cols), th.ctypes.data, K, ptr(llr), T, stream(), nbytes=8.0 * (K + 1) * T)
+    return llr
+
+
+def cal_cllr(llr, label, costs, eta):
+    """llr [T] float64, label [T] uint8 (device); costs: P <= 8 triples and their Bayes thresholds eta (host) -> (out_d [2 + P],
+    out_i [2 + 2 P]) on the device, laid out as include/spkcal.h says (spk_cal_cllr)"""
+    T, P = llr.numel(), len(costs)
+    assert llr.dtype == torch.float64 and label.dtype == torch.uint8 and label.numel() == T and len(eta) == P
+    cd = np.ascontiguousarray([[float(v) for v in c] for c in costs], dtype=np.float64).reshape(P, 3)
+    ed = np.ascontiguousarray(eta, dtype=np.float64).reshape(P)
+    out_d = torch.empty(2 + P, device=llr.device, dtype=torch.float64)
+    out_i = torch.empty(2 + 2 * P, device=llr.device, dtype=torch.int64)
+    need = _cal_ws("spk_cal_cllr_ws_elems", T)
+    ws = torch.empty(need, device=llr.device, dtype=torch.int64)
+    call("spk_cal_cllr", ptr(llr), ptr(label), cd.ctypes.data if P else None, ed.ctypes.data if P else None, P, ptr(out_d), ptr(out_i),
+         ptr(ws), need, T, stream(), nbytes=9.0 * T)
+    return out_d, out_i
+
+
+def cal_train(cols, label, n_tar, p_target, tau, l2, epsilon, max_iters):
+    """cols [K][T] float64, label [T] uint8 (device) -> (state float64 [96], istate int64 [4]) on the device once the max_iters
+    launch pairs the call enqueues have run (spk_cal_train; nothing is downloaded here)"""
+    K, T = cols.shape
+    assert cols.dtype == torch.float64 and cols.is_contiguous() and label.dtype == torch.uint8 and label.numel() == T
+    state = torch.empty(hip.lib().spk_cal_tile(2), device=cols.device, dtype=torch.float64)
+    istate = torch.empty(4, device=cols.device, dtype=torch.int64)
+    need = _cal_ws("spk_cal_train_ws_elems", T, K)
+    ws = torch.empty(need, device=cols.device, dtype=torch.float64)
+    call("spk_cal_train", ptr(cols), ptr(label), K, T, int(n_tar), float(p_target), float(tau), float(l2), float(epsilon), int(max_iters),
+         ptr(state), ptr(istate), ptr(ws), need, stream(), nbytes=(8.0 * K + 1) * T)
+    return state, istate
+
+
+def cal_pav(score, label, order, upto=0):
+    """score [T] float64, label [T] uint8, order [T] from sort_trials (device) -> {'tie', 'pools': int64 [T][2] (the first counts[0] /
+    counts[3] rows hold pools), 'counts': int64 [8], 'pool_of': int32 [T], 'min_cllr': float64 [1]} on the device (spk_cal_pav)"""
+    T = score.numel()
+    assert score.dtype == torch.float64 and label.dtype == torch.uint8 and order.dtype == torch.int32
+    assert label.numel() == T and order.numel() == T
+    dev = score.device
+    r = {"tie": torch.empty(T, 2, device=dev, dtype=torch.int64), "pools": torch.empty(T, 2, device=dev, dtype=torch.int64),
+         "counts": torch.zeros(8, device=dev, dtype=torch.int64), "pool_of": torch.empty(T, device=dev, dtype=torch.int32),
+         "min_cllr": torch.zeros(1, device=dev, dtype=torch.float64)}
+    need = _cal_ws("spk_cal_pav_ws_elems", T)
+    ws = torch.empty(need, device=dev, dtype=torch.int64)
+    call("spk_cal_pav", ptr(score), ptr(label), ptr(order), ptr(r["tie"]), ptr(r["pools"]), ptr(r["counts"]), ptr(r["pool_of"]),
+         ptr(r["min_cllr"]), ptr(ws), need, T, int(upto), stream(), nbytes=13.0 * T)
+    return r

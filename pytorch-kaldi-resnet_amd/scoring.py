@@ -347,13 +347,30 @@ def min_dcf(scores, labels, p_target=0.01, c_miss=1, c_fa=1, backend="host"):
     return d, thr
 
 
+def _calibrated(report, scores, labels, costs, calibration, backend):
+    """the report with 'cllr', 'min_cllr' and 'act_dcf' (one per cost triple) of the scores through a one-system calibration model
+    (calibration.Model or its file); on `hip` the scores and the log-likelihood ratios stay on the device"""
+    from . import calibration as cal
+    model = cal.load(calibration) if isinstance(calibration, str) else calibration
+    if len(model.weights) != 1:
+        raise ValueError("score_and_report calibrates one system, the model has %d" % len(model.weights))
+    llr = cal.apply(model, scores, backend)
+    ev = cal.evaluate(llr, labels, costs, backend)
+    report["cllr"] = ev["cllr"]
+    report["min_cllr"] = cal.min_cllr(llr, labels, backend)[0]
+    report["act_dcf"] = [a["act_dcf"] for a in ev["act_dcf"]]
+    return report
+
+
 def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_stats=None, costs=DEFAULT_COSTS, backend="host",
-                     score_path=None, plda=None, transform=None, num_utts=None):
+                     score_path=None, plda=None, transform=None, num_utts=None, calibration=None):
     """The whole scoring stage in one process: cosine per trial, adaptive S-norm when both statistics tables are given
     (utt -> (mean, std), topk_mean_std / read_mean_std), error-rate sweep.  -> the error_rates report.  On `hip` the embeddings
     and the index arrays go up and only the report comes down (and the scores, if score_path asks for them).
     plda = (mean, transform, psi) with the LDA `transform` (and optionally num_utts: utt -> enrolment count) scores the trials with
-    the PLDA back end instead of the cosine (plda.plda_score); S-norm does not apply to it."""
+    the PLDA back end instead of the cosine (plda.plda_score); S-norm does not apply to it.
+    calibration: a one-system calibration.Model (or its file): the report gains 'cllr', 'min_cllr' and 'act_dcf' of the calibrated
+    scores (section 6s); without it the report is what it was."""
     if plda is not None:
         from . import plda as plda_mod
         assert transform is not None, "the plda back end needs the LDA transform"
@@ -365,7 +382,8 @@ def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_st
             scores = scores.to(torch.float64)            # (widening: exact)
         else:
             scores = scores.astype(np.float64)
-        return error_rates(scores, labels, costs, backend)
+        report = error_rates(scores, labels, costs, backend)
+        return report if calibration is None else _calibrated(report, scores, labels, costs, calibration, backend)
     pairs, labels, ia, ib, me, mt = _read_trials(trials_path, enroll, test, mean)
     snorm = enroll_stats is not None or test_stats is not None
     if snorm:
@@ -384,6 +402,8 @@ def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_st
         if snorm:
             scores = _snorm_host(scores, ja, jb, emu, esd, tmu, tsd)
     report = error_rates(scores, labels, costs, backend)
+    if calibration is not None:
+        report = _calibrated(report, scores, labels, costs, calibration, backend)
     if score_path:
         host = scores.cpu().numpy() if backend == "hip" else scores
         with open(score_path, "w") as f:

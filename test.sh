@@ -6,6 +6,8 @@
 #   scripts/compute_plda.py); <dir> receives the scores and the report and, for snorm, holds topk_mean_std.
 #   SPK_SCORE_BACKEND=hip runs every step on the GPU (default host: the same files, byte for byte; plda: the same
 #   scores to the rounding of its float32 stages).
+#   SPK_CALIBRATION=<model> (scripts/calibrate.py train, one system): stage 12 also writes the calibrated scores <scores>_cal and
+#   stage 13 the report <eer file>_cal: Cllr, minCllr and actDCF at p-target 0.01 and 0.001.
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
 
@@ -63,6 +65,11 @@ if [ $backend == 'snorm' ]; then
   eer_file=${eer_file}_adapt_snorm
 fi
 
+if [ -n "$SPK_CALIBRATION" ] && [ $stage -le 12 ]; then
+  python $here/scripts/calibrate.py apply --model $SPK_CALIBRATION --scores $dir/$score_file \
+      --score-out $dir/${score_file}_cal --backend $impl > $dir/log/calibrate.log
+fi
+
 if [ $stage -le 13 ]; then
   eer=`python $here/scripts/compute_eer.py --backend $impl $dir/$score_file $voxceleb1_trials 2> /dev/null`
   mindcf1=`python $here/scripts/compute_min_dcf.py --backend $impl --p-target 0.01 $dir/$score_file $voxceleb1_trials 2> /dev/null`
@@ -72,4 +79,8 @@ if [ $stage -le 13 ]; then
   echo "minDCF(p-target=0.001): $mindcf2" >> $dir/$eer_file
   echo "backend: $backend"
   cat $dir/$eer_file
+  if [ -n "$SPK_CALIBRATION" ]; then
+    python $here/scripts/compute_cllr.py --backend $impl $dir/${score_file}_cal $voxceleb1_trials > $dir/${eer_file}_cal 2> /dev/null
+    cat $dir/${eer_file}_cal
+  fi
 fi
