@@ -19,6 +19,11 @@
 // reference's feature_pre.sh:178-196 and prepare_feats_for_egs.sh:68-71): the same template again, for rows that hold a span of
 // samples of an utterance; a frame is computed from its position in the utterance, so column j is bit for bit column frame0 + j of
 // the whole-utterance launch.  spk_pcm16_to_f32 converts the 16-bit samples as read from the file.
+//
+// Host side: the four exports put their parameters into one FeCall and go through fe_launch<MFCC, SPAN>, which holds every
+// argument check, the tile lookup, the kernel arguments and the launch once; what only some forms need sits under `if constexpr`.
+#include <type_traits>
+
 #include "spk_common.h"
 
 namespace {
@@ -92,7 +97,8 @@ struct FbankArgs {
 
 // the span form (spk_fbank_span_fwd, spk_mfcc_span_fwd): row b of `wave` holds samples [first[b], first[b] + nsamp[b]) of an
 // utterance of total[b] samples, and the launch computes frames frame0[b] .. frame0[b] + nframes[b] - 1 of THAT utterance.  The
-// fields of FbankArgs keep their place, so the kernel arguments of the whole-utterance kernels are what they were
+// fields of FbankArgs keep their place, so the kernel arguments of the whole-utterance kernels are what they were, and fe_launch
+// fills them by the same lines for all four kernels
 struct SpanArgs : FbankArgs {
     const long long* first;   // [B] sample of the utterance that row b starts with
     const long long* total;   // [B] samples of the utterance
@@ -500,64 +506,92 @@ long long fe_mfcc_lds_bytes(int FT, int L, int S, int P, int F, int C) {
     return (long long)fe_lds_bytes(FT, L, S, P, C) + (long long)C * (F | 1) * 4;
 }
 
-// the arguments fbank_kernel and mfcc_kernel share (checked by the caller); the cepstral fields are left empty
-FbankArgs fe_args(const float* wave, const int* nsamp, const long long* utt_ids, long long Nmax, const float* window,
-                  const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P, int F,
-                  int snip_edges, float dither, float preemph, int remove_dc, float energy_floor, unsigned long long seed, float* feats,
-                  float* log_energy, int* T_out, int Tcap, int FT) {
-    FbankArgs a;
-    a.wave = wave; a.nsamp = nsamp; a.utt_ids = utt_ids; a.Nmax = Nmax;
-    a.window = window; a.twiddle = twiddle; a.mel_w = mel_w; a.mel_lo = mel_lo; a.mel_off = mel_off;
-    a.L = L; a.S = S; a.P = P; a.F = F; a.snip = snip_edges ? 1 : 0; a.FT = FT; a.span = (FT - 1) * S + L;
+constexpr int FE_LDS_LIMIT = 64 * 1024;
+
+// frames per workgroup tile: the largest of 32, 16, 8, 4 whose tile fits the LDS (0: none does)
+template <bool MFCC>
+int fe_tile_frames(int L, int S, int P, int F, int C) {
+    for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
+        if ((MFCC ? fe_mfcc_lds_bytes(FT, L, S, P, F, C) : (long long)fe_lds_bytes(FT, L, S, P, F)) <= FE_LDS_LIMIT) return FT;
+    return 0;
+}
+
+// everything a front-end call is given, in the order of the parameters of spk_mfcc_span_fwd (include/spkhip.h).  first, total,
+// frame0 and nframes are null for the whole-utterance forms; dct, lifter, C, use_energy and htk_compat are empty for fbank
+struct FeCall {
+    const float* wave; const int* nsamp; const long long *first, *total; const int *frame0, *nframes; const long long* utt_ids;
+    int B; long long Nmax;
+    const float *window, *twiddle, *mel_w; const int *mel_lo, *mel_off; const float *dct, *lifter;
+    int L, S, P, F, C, snip_edges; float dither, preemph; int remove_dc; float energy_floor; int use_energy, htk_compat;
+    unsigned long long seed; float *feats, *log_energy; int* T_out; int Tcap; void* stream;
+};
+
+// the one host path of the four exports: every check (`name`: the export that was called, for the messages), the tile, the kernel
+// arguments, the launch.  Grid (ceil(Tcap / FT), B), FE_THREADS threads, the tile's LDS bytes
+template <bool MFCC, bool SPAN>
+int fe_launch(const char* name, const FeCall& c) {
+    SPK_REQUIRE(c.wave && c.nsamp && c.window && c.twiddle && c.mel_w && c.mel_lo && c.mel_off && c.feats && c.log_energy && c.T_out,
+                "%s: null pointer", name);
+    if constexpr (SPAN) SPK_REQUIRE(c.first && c.total && c.frame0 && c.nframes, "%s: null pointer", name);
+    if constexpr (MFCC) SPK_REQUIRE(c.dct && c.lifter, "%s: null pointer", name);
+    SPK_REQUIRE(c.dither == 0.f || c.utt_ids, "%s: dither != 0 needs utt_ids", name);
+    SPK_REQUIRE(c.B > 0 && c.B <= 65535 && c.Nmax > 0 && c.Tcap > 0, "%s: B=%d Nmax=%lld Tcap=%d", name, c.B, c.Nmax, c.Tcap);
+    SPK_REQUIRE(c.P >= 4 && c.P <= 1024 && (c.P & (c.P - 1)) == 0, "%s: padded window P=%d must be a power of two in [4, 1024]", name, c.P);
+    SPK_REQUIRE(c.L >= 2 && c.L <= c.P && c.S >= 1, "%s: frame length L=%d (<= P=%d), shift S=%d", name, c.L, c.P, c.S);
+    if constexpr (MFCC) {
+        SPK_REQUIRE(c.F >= 1 && c.F <= c.P, "%s: num_mel_bins F=%d (the log-mels of a frame reuse its FFT buffer of P=%d floats)", name,
+                    c.F, c.P);
+        SPK_REQUIRE(c.C >= 1 && c.C <= c.F, "%s: num_ceps C=%d must be in [1, num_mel_bins F=%d]", name, c.C, c.F);
+    } else {
+        SPK_REQUIRE(c.F >= 1 && c.F <= 1024, "%s: num_mel_bins F=%d", name, c.F);
+    }
+    SPK_REQUIRE(c.dither >= 0.f && c.preemph >= 0.f && c.preemph <= 1.f && c.energy_floor >= 0.f, "%s: dither=%g preemph=%g energy_floor=%g",
+                name, c.dither, c.preemph, c.energy_floor);
+    const int FT = fe_tile_frames<MFCC>(c.L, c.S, c.P, c.F, c.C);
+    if constexpr (MFCC) SPK_REQUIRE(FT > 0, "%s: L=%d S=%d P=%d F=%d C=%d do not fit the LDS tile", name, c.L, c.S, c.P, c.F, c.C);
+    else SPK_REQUIRE(FT > 0, "%s: L=%d S=%d P=%d F=%d do not fit the LDS tile", name, c.L, c.S, c.P, c.F);
+    typename std::conditional<SPAN, SpanArgs, FbankArgs>::type a;
+    a.wave = c.wave; a.nsamp = c.nsamp; a.utt_ids = c.utt_ids; a.Nmax = c.Nmax;
+    a.window = c.window; a.twiddle = c.twiddle; a.mel_w = c.mel_w; a.mel_lo = c.mel_lo; a.mel_off = c.mel_off;
+    a.L = c.L; a.S = c.S; a.P = c.P; a.F = c.F; a.snip = c.snip_edges ? 1 : 0; a.FT = FT; a.span = (FT - 1) * c.S + c.L;
     int lg = 0;
-    while ((1 << lg) < P / 2) ++lg;
+    while ((1 << lg) < c.P / 2) ++lg;
     a.logM = lg;
-    a.dither = dither; a.preemph = preemph; a.remove_dc = remove_dc ? 1 : 0;
-    a.log_floor = energy_floor > 0.f ? logf(energy_floor) : -__builtin_inff();
-    a.seed = seed; a.feats = feats; a.loge = log_energy; a.T_out = T_out; a.Tcap = Tcap;
-    a.dct = nullptr; a.lifter = nullptr; a.C = 0; a.Fp = 0; a.use_energy = 0; a.htk = 0;
-    return a;
+    a.dither = c.dither; a.preemph = c.preemph; a.remove_dc = c.remove_dc ? 1 : 0;
+    a.log_floor = c.energy_floor > 0.f ? logf(c.energy_floor) : -__builtin_inff();
+    a.seed = c.seed; a.feats = c.feats; a.loge = c.log_energy; a.T_out = c.T_out; a.Tcap = c.Tcap;
+    if constexpr (MFCC) {
+        a.dct = c.dct; a.lifter = c.lifter; a.C = c.C; a.Fp = c.F | 1; a.use_energy = c.use_energy ? 1 : 0; a.htk = c.htk_compat ? 1 : 0;
+    } else {
+        a.dct = nullptr; a.lifter = nullptr; a.C = 0; a.Fp = 0; a.use_energy = 0; a.htk = 0;
+    }
+    if constexpr (SPAN) {
+        a.first = c.first; a.total = c.total; a.frame0 = c.frame0; a.nframes = c.nframes;
+    }
+    const int lds = MFCC ? (int)fe_mfcc_lds_bytes(FT, c.L, c.S, c.P, c.F, c.C) : fe_lds_bytes(FT, c.L, c.S, c.P, c.F);
+    const dim3 grid((unsigned)spk_ceil_div(c.Tcap, FT), (unsigned)c.B);
+    if constexpr (SPAN) hipLaunchKernelGGL(MFCC ? mfcc_span_kernel : fbank_span_kernel, grid, dim3(FE_THREADS), lds, (hipStream_t)c.stream, a);
+    else hipLaunchKernelGGL(MFCC ? mfcc_kernel : fbank_kernel, grid, dim3(FE_THREADS), lds, (hipStream_t)c.stream, a);
+    SPK_LAUNCH_CHECK(name);
+    return 0;
 }
 
 }  // namespace
 
-constexpr int FE_LDS_LIMIT = 64 * 1024;
-
 // ---- exports (include/spkhip.h) ----
-extern "C" int spk_fbank_tile_frames(int L, int S, int P, int F) {
-    for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
-        if (fe_lds_bytes(FT, L, S, P, F) <= FE_LDS_LIMIT) return FT;
-    return 0;
-}
+extern "C" int spk_fbank_tile_frames(int L, int S, int P, int F) { return fe_tile_frames<false>(L, S, P, F, 0); }
 
-extern "C" int spk_mfcc_tile_frames(int L, int S, int P, int F, int C) {
-    for (int FT = 32; FT >= FE_WAVES; FT >>= 1)
-        if (fe_mfcc_lds_bytes(FT, L, S, P, F, C) <= FE_LDS_LIMIT) return FT;
-    return 0;
-}
+extern "C" int spk_mfcc_tile_frames(int L, int S, int P, int F, int C) { return fe_tile_frames<true>(L, S, P, F, C); }
 
 extern "C" int spk_fbank_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax,
                              const float* window, const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off,
                              int L, int S, int P, int F, int snip_edges, float dither, float preemph, int remove_dc,
                              float energy_floor, unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap,
                              void* stream) {
-    SPK_REQUIRE(wave && nsamp && window && twiddle && mel_w && mel_lo && mel_off && feats && log_energy && T_out,
-                "spk_fbank_fwd: null pointer");
-    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_fbank_fwd: dither != 0 needs utt_ids");
-    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_fbank_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
-    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_fbank_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
-    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_fbank_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
-    SPK_REQUIRE(F >= 1 && F <= 1024, "spk_fbank_fwd: num_mel_bins F=%d", F);
-    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
-                "spk_fbank_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
-    const int FT = spk_fbank_tile_frames(L, S, P, F);
-    SPK_REQUIRE(FT > 0, "spk_fbank_fwd: L=%d S=%d P=%d F=%d do not fit the LDS tile", L, S, P, F);
-    FbankArgs a = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
-                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
-    const int lds = fe_lds_bytes(FT, L, S, P, F);
-    hipLaunchKernelGGL(fbank_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds, (hipStream_t)stream, a);
-    SPK_LAUNCH_CHECK("spk_fbank_fwd");
-    return 0;
+    const FeCall c = {wave, nsamp, nullptr, nullptr, nullptr, nullptr, utt_ids, B, Nmax, window, twiddle, mel_w, mel_lo, mel_off,
+                      nullptr, nullptr, L, S, P, F, 0, snip_edges, dither, preemph, remove_dc, energy_floor, 0, 0, seed, feats,
+                      log_energy, T_out, Tcap, stream};
+    return fe_launch<false, false>("spk_fbank_fwd", c);
 }
 
 extern "C" int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long* utt_ids, int B, long long Nmax,
@@ -565,34 +599,10 @@ extern "C" int spk_mfcc_fwd(const float* wave, const int* nsamp, const long long
                             const float* dct, const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither,
                             float preemph, int remove_dc, float energy_floor, int use_energy, int htk_compat,
                             unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
-    SPK_REQUIRE(wave && nsamp && window && twiddle && mel_w && mel_lo && mel_off && dct && lifter && feats && log_energy && T_out,
-                "spk_mfcc_fwd: null pointer");
-    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_mfcc_fwd: dither != 0 needs utt_ids");
-    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_mfcc_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
-    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_mfcc_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
-    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_mfcc_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
-    SPK_REQUIRE(F >= 1 && F <= P, "spk_mfcc_fwd: num_mel_bins F=%d (the log-mels of a frame reuse its FFT buffer of P=%d floats)", F, P);
-    SPK_REQUIRE(C >= 1 && C <= F, "spk_mfcc_fwd: num_ceps C=%d must be in [1, num_mel_bins F=%d]", C, F);
-    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
-                "spk_mfcc_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
-    const int FT = spk_mfcc_tile_frames(L, S, P, F, C);
-    SPK_REQUIRE(FT > 0, "spk_mfcc_fwd: L=%d S=%d P=%d F=%d C=%d do not fit the LDS tile", L, S, P, F, C);
-    FbankArgs a = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
-                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
-    a.dct = dct; a.lifter = lifter; a.C = C; a.Fp = F | 1; a.use_energy = use_energy ? 1 : 0; a.htk = htk_compat ? 1 : 0;
-    const int lds = (int)fe_mfcc_lds_bytes(FT, L, S, P, F, C);
-    hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
-                       (hipStream_t)stream, a);
-    SPK_LAUNCH_CHECK("spk_mfcc_fwd");
-    return 0;
-}
-
-// the span fields of a checked FbankArgs
-static SpanArgs fe_span_args(const FbankArgs& f, const long long* first, const long long* total, const int* frame0, const int* nframes) {
-    SpanArgs a;
-    static_cast<FbankArgs&>(a) = f;
-    a.first = first; a.total = total; a.frame0 = frame0; a.nframes = nframes;
-    return a;
+    const FeCall c = {wave, nsamp, nullptr, nullptr, nullptr, nullptr, utt_ids, B, Nmax, window, twiddle, mel_w, mel_lo, mel_off,
+                      dct, lifter, L, S, P, F, C, snip_edges, dither, preemph, remove_dc, energy_floor, use_energy, htk_compat, seed,
+                      feats, log_energy, T_out, Tcap, stream};
+    return fe_launch<true, false>("spk_mfcc_fwd", c);
 }
 
 extern "C" int spk_fbank_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
@@ -600,25 +610,10 @@ extern "C" int spk_fbank_span_fwd(const float* wave, const int* nsamp, const lon
                                   const float* twiddle, const float* mel_w, const int* mel_lo, const int* mel_off, int L, int S, int P,
                                   int F, int snip_edges, float dither, float preemph, int remove_dc, float energy_floor,
                                   unsigned long long seed, float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
-    SPK_REQUIRE(wave && nsamp && first && total && frame0 && nframes && window && twiddle && mel_w && mel_lo && mel_off && feats &&
-                log_energy && T_out, "spk_fbank_span_fwd: null pointer");
-    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_fbank_span_fwd: dither != 0 needs utt_ids");
-    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_fbank_span_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
-    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_fbank_span_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
-    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_fbank_span_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
-    SPK_REQUIRE(F >= 1 && F <= 1024, "spk_fbank_span_fwd: num_mel_bins F=%d", F);
-    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
-                "spk_fbank_span_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
-    const int FT = spk_fbank_tile_frames(L, S, P, F);
-    SPK_REQUIRE(FT > 0, "spk_fbank_span_fwd: L=%d S=%d P=%d F=%d do not fit the LDS tile", L, S, P, F);
-    SpanArgs a = fe_span_args(fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither,
-                                      preemph, remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT),
-                              first, total, frame0, nframes);
-    const int lds = fe_lds_bytes(FT, L, S, P, F);
-    hipLaunchKernelGGL(fbank_span_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
-                       (hipStream_t)stream, a);
-    SPK_LAUNCH_CHECK("spk_fbank_span_fwd");
-    return 0;
+    const FeCall c = {wave, nsamp, first, total, frame0, nframes, utt_ids, B, Nmax, window, twiddle, mel_w, mel_lo, mel_off,
+                      nullptr, nullptr, L, S, P, F, 0, snip_edges, dither, preemph, remove_dc, energy_floor, 0, 0, seed, feats,
+                      log_energy, T_out, Tcap, stream};
+    return fe_launch<false, true>("spk_fbank_span_fwd", c);
 }
 
 extern "C" int spk_mfcc_span_fwd(const float* wave, const int* nsamp, const long long* first, const long long* total, const int* frame0,
@@ -627,27 +622,10 @@ extern "C" int spk_mfcc_span_fwd(const float* wave, const int* nsamp, const long
                                  const float* lifter, int L, int S, int P, int F, int C, int snip_edges, float dither, float preemph,
                                  int remove_dc, float energy_floor, int use_energy, int htk_compat, unsigned long long seed,
                                  float* feats, float* log_energy, int* T_out, int Tcap, void* stream) {
-    SPK_REQUIRE(wave && nsamp && first && total && frame0 && nframes && window && twiddle && mel_w && mel_lo && mel_off && dct && lifter &&
-                feats && log_energy && T_out, "spk_mfcc_span_fwd: null pointer");
-    SPK_REQUIRE(dither == 0.f || utt_ids, "spk_mfcc_span_fwd: dither != 0 needs utt_ids");
-    SPK_REQUIRE(B > 0 && B <= 65535 && Nmax > 0 && Tcap > 0, "spk_mfcc_span_fwd: B=%d Nmax=%lld Tcap=%d", B, Nmax, Tcap);
-    SPK_REQUIRE(P >= 4 && P <= 1024 && (P & (P - 1)) == 0, "spk_mfcc_span_fwd: padded window P=%d must be a power of two in [4, 1024]", P);
-    SPK_REQUIRE(L >= 2 && L <= P && S >= 1, "spk_mfcc_span_fwd: frame length L=%d (<= P=%d), shift S=%d", L, P, S);
-    SPK_REQUIRE(F >= 1 && F <= P, "spk_mfcc_span_fwd: num_mel_bins F=%d (the log-mels of a frame reuse its FFT buffer of P=%d floats)", F, P);
-    SPK_REQUIRE(C >= 1 && C <= F, "spk_mfcc_span_fwd: num_ceps C=%d must be in [1, num_mel_bins F=%d]", C, F);
-    SPK_REQUIRE(dither >= 0.f && preemph >= 0.f && preemph <= 1.f && energy_floor >= 0.f,
-                "spk_mfcc_span_fwd: dither=%g preemph=%g energy_floor=%g", dither, preemph, energy_floor);
-    const int FT = spk_mfcc_tile_frames(L, S, P, F, C);
-    SPK_REQUIRE(FT > 0, "spk_mfcc_span_fwd: L=%d S=%d P=%d F=%d C=%d do not fit the LDS tile", L, S, P, F, C);
-    FbankArgs f = fe_args(wave, nsamp, utt_ids, Nmax, window, twiddle, mel_w, mel_lo, mel_off, L, S, P, F, snip_edges, dither, preemph,
-                          remove_dc, energy_floor, seed, feats, log_energy, T_out, Tcap, FT);
-    f.dct = dct; f.lifter = lifter; f.C = C; f.Fp = F | 1; f.use_energy = use_energy ? 1 : 0; f.htk = htk_compat ? 1 : 0;
-    SpanArgs a = fe_span_args(f, first, total, frame0, nframes);
-    const int lds = (int)fe_mfcc_lds_bytes(FT, L, S, P, F, C);
-    hipLaunchKernelGGL(mfcc_span_kernel, dim3((unsigned)spk_ceil_div(Tcap, FT), (unsigned)B), dim3(FE_THREADS), lds,
-                       (hipStream_t)stream, a);
-    SPK_LAUNCH_CHECK("spk_mfcc_span_fwd");
-    return 0;
+    const FeCall c = {wave, nsamp, first, total, frame0, nframes, utt_ids, B, Nmax, window, twiddle, mel_w, mel_lo, mel_off,
+                      dct, lifter, L, S, P, F, C, snip_edges, dither, preemph, remove_dc, energy_floor, use_energy, htk_compat, seed,
+                      feats, log_energy, T_out, Tcap, stream};
+    return fe_launch<true, true>("spk_mfcc_span_fwd", c);
 }
 
 extern "C" int spk_pcm16_to_f32(const short* pcm, const int* count, int B, long long Nmax, float* out, void* stream) {

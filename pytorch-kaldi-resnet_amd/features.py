@@ -1030,7 +1030,8 @@ class ChunkFrontend:
 
     def __init__(self, fbank_opts, cmn=None, seed=0, pool=None):
         self.opts, self.cmn, self.seed, self.pool = fbank_opts, cmn, seed, pool
-        self.dim = fbank_opts.num_ceps if isinstance(fbank_opts, MfccOptions) else fbank_opts.num_mel_bins
+        self.mfcc = isinstance(fbank_opts, MfccOptions)
+        self.dim = fbank_opts.num_ceps if self.mfcc else fbank_opts.num_mel_bins
 
     def __call__(self, pcm, count, first, total, frame0, nframes, rel, T, utt_ids=None, plan=None, times=None):
         B, Nmax = pcm.shape
@@ -1059,7 +1060,8 @@ class ChunkFrontend:
                 wave.index_copy_(0, rows, self.pool.apply(wave.index_select(0, rows), count.index_select(0, rows), plan))
                 return wave
             wave = stage("augment", aug)
-        feats, _ = stage("frontend", lambda: _span_launch(self.opts, wave, count, first, total, frame0, nframes, utt_ids, self.seed, Tcap))
+        feats, _ = stage("frontend", lambda: _launch(self.mfcc, self.opts, wave, count, utt_ids, self.seed, Tcap,
+                                                     span=(first, total, frame0, nframes)))
         W = int(self.cmn.cmn_window) if self.cmn is not None else 0
         F = feats.shape[1]
 
@@ -1074,47 +1076,75 @@ class ChunkFrontend:
 
 
 # ---- functional API ----
-def _frame_inputs(what, wave, nsamp, opts, utt_ids, Tcap):
-    """the argument checks and device inputs fbank and mfcc share (`what` names the caller in the messages):
-    (wave, B, Nmax, T, Tcap, ns, ids, tables)"""
-    if wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+def _launch(mfcc, opts, wave, ns, ids, seed, Tcap, out=None, span=None):
+    """the one front-end launch, on device arguments alone (no check of their values, nothing read back).  mfcc: spk_mfcc_* with
+    the cepstral options of an MfccOptions, else spk_fbank_*; span: None for the whole-utterance kernels, or the device tensors
+    (first, total, frame0, nframes) of the span kernels.  Returns (feats [B, R, Tcap] - `out` when given -, log_energy [B, Tcap])"""
+    B, Nmax = wave.shape
+    dev = wave.device
+    tab = _tables(opts, dev)
+    feats = torch.empty(B, opts.num_ceps if mfcc else opts.num_mel_bins, Tcap, device=dev) if out is None else out
+    loge = torch.empty(B, Tcap, device=dev)
+    tdev = torch.empty(B, dtype=torch.int32, device=dev)
+    name = (("spk_fbank_fwd", "spk_fbank_span_fwd"), ("spk_mfcc_fwd", "spk_mfcc_span_fwd"))[bool(mfcc)][span is not None]
+    p = hip.ptr
+    # the arguments that only the MFCC exports take, in their three places of the parameter list
+    tables, ceps, order = ((), (), ()) if not mfcc else ((p(tab.dct), p(tab.lifter)), (opts.num_ceps,),
+                                                         (int(opts.use_energy), int(opts.htk_compat)))
+    hip.call(name, p(wave), p(ns), *(p(t) for t in span or ()), p(ids), B, Nmax, p(tab.window), p(tab.twiddle), p(tab.mel_w),
+             p(tab.mel_lo), p(tab.mel_off), *tables, opts.frame_len, opts.frame_sh, opts.padded_len, opts.num_mel_bins, *ceps,
+             int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient), int(opts.remove_dc_offset),
+             float(opts.energy_floor), *order, int(seed) & (2 ** 64 - 1), p(feats), p(loge), p(tdev), Tcap, hip.stream())
+    return feats, loge
+
+
+def _checked(what, mfcc, wave, opts, utt_ids, Tcap, out, rows, min_cap):
+    """the argument checks that the whole-utterance and the span forms share, in front of any device work (`what` names the
+    caller in the messages).  rows(B, Nmax): the form's own checks of its per-row host integers -> (frames per row, [(array,
+    dtype), ..] the integer arguments of the launch); min_cap: the least Tcap the form picks by itself.
+    Returns (wave contiguous, frames per row, Tcap, the integer arguments on the device, utt_ids on the device or None)"""
+    if not getattr(wave, "is_cuda", False) or wave.dim() != 2 or wave.dtype != torch.float32:
         raise ValueError("%s: wave must be a float32 cuda tensor [B, Nmax]" % what)
     wave = wave.contiguous()
     B, Nmax = wave.shape
-    n = _host_ints(nsamp)
-    if n.size != B:
-        raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
-    L = opts.frame_len
-    if (n < L).any() or (n > Nmax).any():
-        bad = int(np.nonzero((n < L) | (n > Nmax))[0][0])
-        raise ValueError("%s: row %d has %d samples, outside [frame length %d, Nmax %d]" % (what, bad, int(n[bad]), L, Nmax))
-    T = np.asarray([opts.num_frames(int(v)) for v in n], dtype=np.int64)
-    Tcap = int(T.max()) if Tcap is None else int(Tcap)
-    if Tcap < T.max():
-        raise ValueError("%s: Tcap %d < longest utterance %d frames" % (what, Tcap, int(T.max())))
+    T, ints = rows(B, Nmax)
+    longest = max(int(T.max()), min_cap)
+    Tcap = longest if Tcap is None else int(Tcap)
+    if Tcap < longest:
+        raise ValueError("%s: Tcap %d < longest row, %d frames" % (what, Tcap, longest))
     if opts.dither != 0 and utt_ids is None:
         raise ValueError("%s: dither != 0 needs utt_ids (the key of each row's noise)" % what)
+    R = opts.num_ceps if mfcc else opts.num_mel_bins
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, R, Tcap)
+                            or not out.is_cuda or not out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous float32 cuda tensor [%d, %d, %d]" % (what, B, R, Tcap))
     dev = wave.device
-    tab = _tables(opts, dev)
-    ns = torch.from_numpy(n.astype(np.int32)).to(dev)
-    ids = torch.as_tensor(_host_ints(utt_ids), dtype=torch.int64).to(dev) if utt_ids is not None else None
-    return wave, B, Nmax, T, Tcap, ns, ids, tab
+
+    def dv(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+    return wave, T, Tcap, [dv(a, dtype) for a, dtype in ints], dv(_host_ints(utt_ids), np.int64) if utt_ids is not None else None
+
+
+def _whole(what, mfcc, wave, nsamp, opts, utt_ids, seed, Tcap, out=None):
+    """fbank and mfcc: every row is a whole utterance of at least one frame"""
+    def rows(B, Nmax):
+        n = _host_ints(nsamp)
+        if n.size != B:
+            raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
+        L = opts.frame_len
+        if (n < L).any() or (n > Nmax).any():
+            bad = int(np.nonzero((n < L) | (n > Nmax))[0][0])
+            raise ValueError("%s: row %d has %d samples, outside [frame length %d, Nmax %d]" % (what, bad, int(n[bad]), L, Nmax))
+        return np.asarray([opts.num_frames(int(v)) for v in n], dtype=np.int64), [(n, np.int32)]
+    wave, T, Tcap, (ns,), ids = _checked(what, mfcc, wave, opts, utt_ids, Tcap, out, rows, 0)
+    feats, loge = _launch(mfcc, opts, wave, ns, ids, seed, Tcap, out)
+    return feats, T, loge
 
 
 def fbank(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None):
     """wave: float32 cuda [B, Nmax] at int16 scale, nsamp: per-row sample counts (host or device ints, each >= frame length).
     Returns (feats [B, F, Tcap] cuda (zeros past T[b]), T int64 host array, log_energy [B, Tcap] cuda (raw log energy))."""
-    wave, B, Nmax, T, Tcap, ns, ids, tab = _frame_inputs("fbank", wave, nsamp, opts, utt_ids, Tcap)
-    dev = wave.device
-    feats = torch.empty(B, opts.num_mel_bins, Tcap, device=dev)
-    loge = torch.empty(B, Tcap, device=dev)
-    tdev = torch.empty(B, dtype=torch.int32, device=dev)
-    hip.call("spk_fbank_fwd", hip.ptr(wave), hip.ptr(ns), hip.ptr(ids), B, Nmax, hip.ptr(tab.window), hip.ptr(tab.twiddle),
-             hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off), opts.frame_len, opts.frame_sh, opts.padded_len,
-             opts.num_mel_bins, int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient),
-             int(opts.remove_dc_offset), float(opts.energy_floor), int(seed) & (2 ** 64 - 1), hip.ptr(feats), hip.ptr(loge),
-             hip.ptr(tdev), Tcap, hip.stream())
-    return feats, T, loge
+    return _whole("fbank", False, wave, nsamp, opts, utt_ids, seed, Tcap)
 
 
 def mfcc(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None, out=None):
@@ -1124,22 +1154,7 @@ def mfcc(wave, nsamp, opts, utt_ids=None, seed=0, Tcap=None, out=None):
     the VAD's input).  out: a preallocated contiguous float32 cuda tensor [B, C, Tcap] to write the features into."""
     if not isinstance(opts, MfccOptions):
         raise ValueError("mfcc: opts must be an MfccOptions")
-    wave, B, Nmax, T, Tcap, ns, ids, tab = _frame_inputs("mfcc", wave, nsamp, opts, utt_ids, Tcap)
-    dev = wave.device
-    C = opts.num_ceps
-    if out is None:
-        out = torch.empty(B, C, Tcap, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, C, Tcap) or not out.is_cuda
-          or not out.is_contiguous()):
-        raise ValueError("mfcc: out must be a contiguous float32 cuda tensor [%d, %d, %d]" % (B, C, Tcap))
-    loge = torch.empty(B, Tcap, device=dev)
-    tdev = torch.empty(B, dtype=torch.int32, device=dev)
-    hip.call("spk_mfcc_fwd", hip.ptr(wave), hip.ptr(ns), hip.ptr(ids), B, Nmax, hip.ptr(tab.window), hip.ptr(tab.twiddle),
-             hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off), hip.ptr(tab.dct), hip.ptr(tab.lifter), opts.frame_len,
-             opts.frame_sh, opts.padded_len, opts.num_mel_bins, C, int(opts.snip_edges), float(opts.dither),
-             float(opts.preemphasis_coefficient), int(opts.remove_dc_offset), float(opts.energy_floor), int(opts.use_energy),
-             int(opts.htk_compat), int(seed) & (2 ** 64 - 1), hip.ptr(out), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
-    return out, T, loge
+    return _whole("mfcc", True, wave, nsamp, opts, utt_ids, seed, Tcap, out)
 
 
 # ---- the span form: frames of a part of an utterance, equal to the frames of the whole (DESIGN.md section 6k) ----
@@ -1174,29 +1189,6 @@ def pcm16_to_f32(pcm, count, out=None):
     return out
 
 
-def _span_launch(opts, wave, ns, first, total, frame0, nframes, ids, seed, Tcap, out=None):
-    """the span launch on device arguments alone (no check of their values, nothing read back): (feats [B, R, Tcap], log_energy)"""
-    B, Nmax = wave.shape
-    dev = wave.device
-    tab = _tables(opts, dev)
-    is_mfcc = isinstance(opts, MfccOptions)
-    R = opts.num_ceps if is_mfcc else opts.num_mel_bins
-    feats = torch.empty(B, R, Tcap, device=dev) if out is None else out
-    loge = torch.empty(B, Tcap, device=dev)
-    tdev = torch.empty(B, dtype=torch.int32, device=dev)
-    head = (hip.ptr(wave), hip.ptr(ns), hip.ptr(first), hip.ptr(total), hip.ptr(frame0), hip.ptr(nframes), hip.ptr(ids), B, Nmax,
-            hip.ptr(tab.window), hip.ptr(tab.twiddle), hip.ptr(tab.mel_w), hip.ptr(tab.mel_lo), hip.ptr(tab.mel_off))
-    tail = (int(seed) & (2 ** 64 - 1), hip.ptr(feats), hip.ptr(loge), hip.ptr(tdev), Tcap, hip.stream())
-    if is_mfcc:
-        hip.call("spk_mfcc_span_fwd", *head, hip.ptr(tab.dct), hip.ptr(tab.lifter), opts.frame_len, opts.frame_sh, opts.padded_len,
-                 opts.num_mel_bins, R, int(opts.snip_edges), float(opts.dither), float(opts.preemphasis_coefficient),
-                 int(opts.remove_dc_offset), float(opts.energy_floor), int(opts.use_energy), int(opts.htk_compat), *tail)
-    else:
-        hip.call("spk_fbank_span_fwd", *head, opts.frame_len, opts.frame_sh, opts.padded_len, R, int(opts.snip_edges),
-                 float(opts.dither), float(opts.preemphasis_coefficient), int(opts.remove_dc_offset), float(opts.energy_floor), *tail)
-    return feats, loge
-
-
 def check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax):
     """the refusals of the span form, on host arrays, before any launch: every computed frame exists in the utterance and, after
     reflection, touches only samples that the row holds.  Returns the arrays as int64."""
@@ -1221,29 +1213,15 @@ def check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax):
     return n, f, N, f0, nf
 
 
-def _span(what, wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out=None):
-    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
-        raise ValueError("%s: wave must be a float32 cuda tensor [B, Nmax]" % what)
-    wave = wave.contiguous()
-    B, Nmax = wave.shape
-    n, f, N, f0, nf = check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax)
-    if n.size != B:
-        raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
-    Tcap = max(int(nf.max()), 1) if Tcap is None else int(Tcap)
-    if Tcap < nf.max() or Tcap < 1:
-        raise ValueError("%s: Tcap %d < longest span %d frames" % (what, Tcap, int(nf.max())))
-    if opts.dither != 0 and utt_ids is None:
-        raise ValueError("%s: dither != 0 needs utt_ids (the key of each row's noise)" % what)
-    dev = wave.device
-
-    def dv(a, dtype):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-    ids = dv(_host_ints(utt_ids), np.int64) if utt_ids is not None else None
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
-                            or not out.is_contiguous() or out.dim() != 3 or out.shape[0] != B or out.shape[2] != Tcap):
-        raise ValueError("%s: out must be a contiguous float32 cuda tensor [%d, rows, %d]" % (what, B, Tcap))
-    feats, loge = _span_launch(opts, wave, dv(n, np.int32), dv(f, np.int64), dv(N, np.int64), dv(f0, np.int32), dv(nf, np.int32), ids,
-                               seed, Tcap, out)
+def _span(what, mfcc, wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out=None):
+    """fbank_span and mfcc_span: check_spans on the rows; a row may have no frame, Tcap is at least 1"""
+    def rows(B, Nmax):
+        n, f, N, f0, nf = check_spans(what, opts, nsamp, first, total, frame0, nframes, Nmax)
+        if n.size != B:
+            raise ValueError("%s: %d sample counts for %d rows" % (what, n.size, B))
+        return nf, [(n, np.int32), (f, np.int64), (N, np.int64), (f0, np.int32), (nf, np.int32)]
+    wave, nf, Tcap, (ns, *span), ids = _checked(what, mfcc, wave, opts, utt_ids, Tcap, out, rows, 1)
+    feats, loge = _launch(mfcc, opts, wave, ns, ids, seed, Tcap, out, span)
     return feats, nf, loge
 
 
@@ -1257,15 +1235,15 @@ def fbank_span(wave, nsamp, first, total, frame0, nframes, opts, utt_ids=None, s
     its row (span_samples gives the samples a frame range needs)."""
     if isinstance(opts, MfccOptions):
         raise ValueError("fbank_span: opts must be a FbankOptions (mfcc_span takes MfccOptions)")
-    return _span("fbank_span", wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap)
+    return _span("fbank_span", False, wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap)
 
 
 def mfcc_span(wave, nsamp, first, total, frame0, nframes, opts, utt_ids=None, seed=0, Tcap=None, out=None):
     """fbank_span for compute-mfcc-feats (opts: MfccOptions): feats [B, num_ceps, Tcap], equal bit for bit to mfcc() on the whole
-    utterance"""
+    utterance.  out: as for mfcc, [B, num_ceps, Tcap]"""
     if not isinstance(opts, MfccOptions):
         raise ValueError("mfcc_span: opts must be an MfccOptions")
-    return _span("mfcc_span", wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out)
+    return _span("mfcc_span", True, wave, nsamp, first, total, frame0, nframes, opts, utt_ids, seed, Tcap, out)
 
 
 def dither_noise(utt, seed, frame0, nframes, L, device="cuda"):

@@ -27,6 +27,18 @@ _F = ctypes.c_float
 _D = ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
 
+
+def _frontend_sig(mfcc, span):
+    """spk_{fbank,mfcc}[_span]_fwd: one parameter list, with the four span pointers and the cepstral arguments where they apply"""
+    def cep(*t):
+        return list(t) if mfcc else []
+    return ([_P, _P] + [_P] * 4 * span + [_P, _I, _L]      # wave, nsamp, (first, total, frame0, nframes,) utt_ids, B, Nmax
+            + [_P] * 5 + cep(_P, _P)                        # window, twiddle, mel_w, mel_lo, mel_off (, dct, lifter)
+            + [_I] * 4 + cep(_I) + [_I, _F, _F, _I, _F]     # L, S, P, F (, C), snip_edges, dither, preemph, remove_dc, energy_floor
+            + cep(_I, _I)                                   # (use_energy, htk_compat)
+            + [ctypes.c_ulonglong, _P, _P, _P, _I, _P])     # seed, feats, log_energy, T_out, Tcap, stream
+
+
 _SIGS = {
     "spk_pack_conv_weight": [_P, _P, _I, _I, _I, _I, _I, _P],
     "spk_pack_conv_weight_split": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -96,11 +108,11 @@ _SIGS = {
     "spk_trial_cosine": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "spk_topk_mean_std": [_P, _P, _P, _I, _I, _I, _L, _P],
     "spk_fbank_tile_frames": [_I, _I, _I, _I],
-    "spk_fbank_fwd": [_P, _P, _P, _I, _L] + [_P] * 5 + [_I] * 5 + [_F, _F, _I, _F, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
+    "spk_fbank_fwd": _frontend_sig(False, False),
     "spk_mfcc_tile_frames": [_I, _I, _I, _I, _I],
-    "spk_mfcc_fwd": [_P, _P, _P, _I, _L] + [_P] * 7 + [_I] * 6 + [_F, _F, _I, _F, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
-    "spk_fbank_span_fwd": [_P] * 7 + [_I, _L] + [_P] * 5 + [_I] * 5 + [_F, _F, _I, _F, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
-    "spk_mfcc_span_fwd": [_P] * 7 + [_I, _L] + [_P] * 7 + [_I] * 6 + [_F, _F, _I, _F, _I, _I, ctypes.c_ulonglong, _P, _P, _P, _I, _P],
+    "spk_mfcc_fwd": _frontend_sig(True, False),
+    "spk_fbank_span_fwd": _frontend_sig(False, True),
+    "spk_mfcc_span_fwd": _frontend_sig(True, True),
     "spk_pcm16_to_f32": [_P, _P, _I, _L, _P, _P],
     "spk_fbank_dither_noise":[_P, _L, ctypes.c_ulonglong, _I, _I, _I, _P],
     "spk_vad_count": [_P, _P, _I, _I, _D, _D, _I, _D, _P, _P, _P, _P],

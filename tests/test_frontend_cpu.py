@@ -175,17 +175,68 @@ def test_wav_reader_refusals(tmp_path):
 
 
 # ---- C-ABI refusals (host-side checks, before any launch) ----
+_POINTERS = ("wave", "nsamp", "first", "total", "frame0", "nframes", "utt_ids", "window", "twiddle", "mel_w", "mel_lo", "mel_off", "dct",
+             "lifter", "feats", "log_energy", "T_out")
+
+
+def _frontend_call(lib, mfcc, span, null=(), F=40, C=13, P=512, L=400, S=160, dither=0.0):
+    """(export name, rc) of spk_{fbank,mfcc}[_span]_fwd on dummy pointers (`null`: the ones passed as NULL), B = 1, Nmax = 1000,
+    Tcap = 10; nothing is dereferenced as long as the call fails a host-side check"""
+    p = {k: None if k in null else ctypes.c_void_p(16) for k in _POINTERS}
+    name = "spk_%s%s_fwd" % ("mfcc" if mfcc else "fbank", "_span" if span else "")
+    args = ([p["wave"], p["nsamp"]] + ([p[k] for k in ("first", "total", "frame0", "nframes")] if span else [])
+            + [p["utt_ids"], 1, 1000] + [p[k] for k in ("window", "twiddle", "mel_w", "mel_lo", "mel_off")]
+            + ([p["dct"], p["lifter"]] if mfcc else []) + [L, S, P, F] + ([C] if mfcc else []) + [1, dither, 0.97, 1, 0.0]
+            + ([1, 0] if mfcc else []) + [0, p["feats"], p["log_energy"], p["T_out"], 10, None])
+    return name, getattr(lib, name)(*args)
+
+
+# (the forms a case applies to, arguments, the word its refusal carries)
+REFUSALS = [
+    ("all", dict(P=500), b"power of two"), ("all", dict(P=2048), b"power of two"),
+    ("all", dict(dither=1.0, null=("utt_ids",)), b"utt_ids"), ("all", dict(null=("mel_off",)), b"null"),
+    ("all", dict(L=1024, S=4000, P=1024), b"LDS"),
+    ("span", dict(null=("first",)), b"null"), ("span", dict(null=("total",)), b"null"), ("span", dict(null=("frame0",)), b"null"),
+    ("span", dict(null=("nframes",)), b"null"),
+    ("mfcc", dict(C=41), b"num_ceps"), ("mfcc", dict(C=0), b"num_ceps"), ("mfcc", dict(C=-3), b"num_ceps"),
+    ("mfcc", dict(null=("dct",)), b"null"), ("mfcc", dict(null=("lifter",)), b"null"), ("mfcc", dict(F=600, C=13), b"num_mel_bins"),
+    ("mfcc", dict(F=128, C=128), b"LDS"),
+    # F > P: the MFCC forms refuse it (the log-mels reuse the FFT buffer); fbank allows F <= 1024 and gets as far as the tile test
+    # (the shift of 4000 samples is there so that no tile fits: with the default shift a tile of 8 frames would, and launch)
+    ("mfcc", dict(F=600, S=4000), b"num_mel_bins"), ("fbank", dict(F=600, S=4000), b"LDS"),
+]
+
+
+@pytest.mark.parametrize("mfcc, span", [(False, False), (True, False), (False, True), (True, True)])
+def test_frontend_exports_refuse_bad_arguments_without_a_gpu(mfcc, span):
+    """one table over the four exports: each refusal returns rc < 0 and names the export that was called"""
+    lib = hip.lib()
+    applies = {"all": True, "span": span, "mfcc": mfcc, "fbank": not mfcc}
+    ran = 0
+    for forms, kw, word in REFUSALS:
+        if applies[forms]:
+            name, rc = _frontend_call(lib, mfcc, span, **kw)
+            err = lib.spk_last_error()
+            assert rc < 0 and name.encode() + b":" in err and word in err, (name, kw, rc, err)
+            ran += 1
+    assert ran == 5 + 4 * span + (8 if mfcc else 1)
+
+
+def test_frontend_argtypes_are_the_declared_parameter_lists():
+    """the ctypes signatures of the four exports, written out: include/spkhip.h's parameter lists, type by type"""
+    lib = hip.lib()
+    P, I, L, F, U = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong
+    assert lib.spk_fbank_fwd.argtypes == [P, P, P, I, L, P, P, P, P, P, I, I, I, I, I, F, F, I, F, U, P, P, P, I, P]
+    assert lib.spk_mfcc_fwd.argtypes == [P, P, P, I, L, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, I, F, I, I, U, P, P, P, I, P]
+    assert lib.spk_fbank_span_fwd.argtypes == [P, P, P, P, P, P, P, I, L, P, P, P, P, P, I, I, I, I, I, F, F, I, F, U, P, P, P, I, P]
+    assert lib.spk_mfcc_span_fwd.argtypes == [P, P, P, P, P, P, P, I, L, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, I, F, I, I, U, P,
+                                              P, P, I, P]
+
+
 def test_frontend_entries_refuse_bad_arguments_without_a_gpu():
+    """the other entries of csrc/frontend.hip (the four frame launches: the table above)"""
     lib = hip.lib()
     P = ctypes.c_void_p(16)      # never dereferenced: every call below fails its host-side checks
-    rc = lib.spk_fbank_fwd(P, P, P, 1, 1000, P, P, P, P, P, 400, 160, 500, 40, 1, 0.0, 0.97, 1, 0.0, 0, P, P, P, 10, None)
-    assert rc < 0 and b"power of two" in lib.spk_last_error()
-    rc = lib.spk_fbank_fwd(P, P, P, 1, 1000, P, P, P, P, P, 400, 160, 2048, 40, 1, 0.0, 0.97, 1, 0.0, 0, P, P, P, 10, None)
-    assert rc < 0 and b"spk_fbank_fwd" in lib.spk_last_error()
-    rc = lib.spk_fbank_fwd(P, P, None, 1, 1000, P, P, P, P, P, 400, 160, 512, 40, 1, 1.0, 0.97, 1, 0.0, 0, P, P, P, 10, None)
-    assert rc < 0 and b"utt_ids" in lib.spk_last_error()
-    rc = lib.spk_fbank_fwd(P, P, P, 1, 1000, P, P, P, P, None, 400, 160, 512, 40, 1, 0.0, 0.97, 1, 0.0, 0, P, P, P, 10, None)
-    assert rc < 0 and b"null" in lib.spk_last_error()
     assert lib.spk_fbank_tile_frames(400, 160, 512, 80) == 32
     assert lib.spk_fbank_tile_frames(1024, 4000, 1024, 80) == 0
     assert lib.spk_fbank_dither_noise(P, 0, 0, 0, 0, 400, None) < 0

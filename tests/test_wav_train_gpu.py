@@ -120,7 +120,7 @@ def test_span_frames_are_the_whole_utterance_frames_bit_for_bit(name, dither):
 
 
 def test_span_refusals_need_no_launch():
-    """the wrapper's refusals, checked on the host: nothing here reaches the kernel"""
+    """the wrapper's refusals, checked on the host: nothing here reaches the kernel but the last call, whose `out` is taken"""
     from pytorch_kaldi_resnet_amd import features
     opts = _configs()["fbank16k_f40_nosnip"]
     N = 16000
@@ -137,6 +137,13 @@ def test_span_refusals_need_no_launch():
         features.mfcc_span(w, *[ok[k] for k in ("nsamp", "first", "total", "frame0", "nframes")], opts)
     with pytest.raises(ValueError, match="float32 cuda"):
         features.fbank_span(w.cpu(), *[ok[k] for k in ("nsamp", "first", "total", "frame0", "nframes")], opts)
+    # out is [B, num_ceps, Tcap] exactly: a tensor one row short is refused, not written past its end
+    mo = features.MfccOptions(num_mel_bins=40, num_ceps=13, snip_edges=False, dither=0.0)
+    span = [ok[k] for k in ("nsamp", "first", "total", "frame0", "nframes")]
+    with pytest.raises(ValueError, match="out must be"):
+        features.mfcc_span(w, *span, mo, out=torch.empty(1, mo.num_ceps - 1, 100, device="cuda"))
+    out = torch.empty(1, mo.num_ceps, 100, device="cuda")
+    assert features.mfcc_span(w, *span, mo, out=out)[0] is out
 
 
 def test_pcm16_to_f32():
