@@ -18,6 +18,14 @@
 // are summed in two fp32 chains (the halves of the packed FMA), each in index order, and added at the end: a fixed order whatever
 // the alignment.  The zero tap of an odd K adds w = 0 times a finite sample: an output depends on its row's samples only, never
 // on the batch, the row index, the padding or the tile it falls in, bit for bit.  What bounds the kernel: DESIGN.md, same section.
+//
+// spkw_resample_span_fwd (include/spkwav.h): the same body on a span.  Row b holds samples [ifirst, ifirst + icount) of an utterance
+// of itotal samples and gets outputs [ofirst, ofirst + ocount) of that utterance's resampling: column i is output j = ofirst + i,
+// phase, unit and window start are those of j in the utterance, and only the staging moves the window into the row (- ifirst).  The
+// values read and the order of the sums are the whole form's, so the columns equal the whole-utterance launch bit for bit, whatever
+// the row-relative alignment of the window.  A staged sample is loaded only if the row holds it: one inside the utterance but
+// outside the row counts as 0, like one outside the utterance, and nothing at or past icount is read.  blockIdx.y indexes an optional
+// device list of rows, so the rows of one rate of a mixed batch take one launch; the other rows are not touched.
 #include "spk_common.h"
 
 namespace {
@@ -29,14 +37,24 @@ constexpr int RS_NT = 8;                      // at most this many tiles per wor
 
 struct ResampleArgs {
     const float* wave_in;      // [B][Nmax_in]
-    const int* nsamp_in;       // [B]
+    const int* nsamp_in;       // [B]                                                            (whole form)
     const int* first;          // [ou]
     const float2* wq;          // [K2][ou] pairs of taps (2m, 2m + 1)
     float* wave_out;           // [B][Nmax_out]
-    int* nsamp_out;            // [B]
+    int* nsamp_out;            // [B]                                                            (whole form)
     long long Nmax_in, Nmax_out;
     int iu, ou, K2, TO, NT, span, tab4, vec;    // K2 = ceil(K / 2); span: floats of one copy of the staged input (multiple of 4);
                                                 // tab4: floats before the first copy
+};
+
+// the span form: row b holds samples [ifirst, ifirst + icount) of an utterance of itotal samples and gets outputs
+// [ofirst, ofirst + ocount) of that utterance's resampled signal; rows: the rows this launch works on (NULL: all B of them).
+// Derived, so that the kernel arguments of the whole form keep their layout.
+struct ResampleSpanArgs : ResampleArgs {
+    const long long *ifirst, *itotal, *ofirst;    // [B]
+    const int *icount, *ocount;                   // [B]
+    const int* rows;                              // [gridDim.y] or NULL
+    int B;
 };
 
 // samples of the span per tile: f(j) = first[j % ou] + (j / ou) * iu = ceil(j * iu / ou - c) grows by at most
@@ -51,23 +69,45 @@ inline long long rs_lds_floats(int TO, int iu, int ou, int K) { return rs_table(
 
 typedef float rs_f2 __attribute__((ext_vector_type(2)));
 
-// NPT = TO / 256 outputs per thread and tile, summed side by side (independent chains hide the LDS latency of each other)
-template <int NPT>
-__global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
+// NPT = TO / 256 outputs per thread and tile, summed side by side (independent chains hide the LDS latency of each other).
+// One body for both forms.  The row holds samples [f, f + c) of an utterance of n samples and gets its outputs [o, o + n_out);
+// the whole form is f = o = 0, c = n, n_out = every output of the utterance: with SPAN = false the offsets fold away and the kernel
+// is the one it was, instruction for instruction.  A sample of
+// the utterance that the row does not hold reads as 0, like one outside the utterance: nothing outside [x, x + c) is loaded.
+template <int NPT, bool SPAN, class A>
+__device__ __forceinline__ void resample_body(const A& a) {
     extern __shared__ float4 rs_lds4[];
     float2* wq = (float2*)rs_lds4;                     // [K2][ou]
     int* first = (int*)(wq + (size_t)a.K2 * a.ou);     // [ou]
     float4* span4 = rs_lds4 + (a.tab4 >> 2);           // [span / 4]: the staged input, 16-byte aligned (tab4 is a multiple of 4)
     float* spano = (float*)(span4 + (a.span >> 2));    // [span]: the same shifted by one sample, spano[i] = span[i + 1]
-    const int b = blockIdx.y, tid = threadIdx.x;
-    // every index below fits 32 bits (the host checks Nmax_in, Nmax_out < 2^30 and iu * ou < 2^31): no 64-bit division on the device
-    const int n = min(max(a.nsamp_in[b], 0), (int)a.Nmax_in);
+    int b = blockIdx.y;
+    const int tid = threadIdx.x;
+    // every index below fits 32 bits (the host checks Nmax_in, Nmax_out, itotal < 2^30 and iu * ou < 2^31): no 64-bit division
+    // on the device
+    const int Nout = (int)a.Nmax_out;
+    // n: samples of the utterance; f, o: the row's first sample and first output in it; [0, vhi): the row's samples that exist
+    int n, f = 0, o = 0, vhi, want = Nout;
+    if constexpr (SPAN) {
+        if (a.rows) b = a.rows[blockIdx.y];
+        if (b < 0 || b >= a.B) return;                // a row list is device data: a bad entry is skipped, not followed
+        n = (int)min(max(a.itotal[b], 0ll), (1ll << 30) - 1);
+        f = (int)min(max(a.ifirst[b], 0ll), (long long)n);
+        o = (int)min(max(a.ofirst[b], 0ll), (1ll << 30) - 1);
+        vhi = min(min(max(a.icount[b], 0), (int)a.Nmax_in), n - f);
+        want = min(max(a.ocount[b], 0), Nout);
+    } else {
+        n = min(max(a.nsamp_in[b], 0), (int)a.Nmax_in);
+        vhi = n;
+    }
     // LinearResample::GetNumOutputSamples: the outputs j with j / fo < n / fi, i.e. ceil(n * ou / iu), split at whole units
     const unsigned nq = (unsigned)n / (unsigned)a.iu, nr = (unsigned)n - nq * (unsigned)a.iu;
     const long long n_out_ll = (long long)nq * a.ou + (nr * (unsigned)a.ou + (unsigned)a.iu - 1u) / (unsigned)a.iu;
-    const int Nout = (int)a.Nmax_out;
-    const int n_out = (int)min(n_out_ll, (long long)Nout);
-    if (blockIdx.x == 0 && tid == 0) a.nsamp_out[b] = n_out;
+    // the outputs of this row that exist: its first n_out columns
+    const int n_out = SPAN ? (int)min(max(n_out_ll - o, 0ll), (long long)want) : (int)min(n_out_ll, (long long)Nout);
+    if constexpr (!SPAN) {
+        if (blockIdx.x == 0 && tid == 0) a.nsamp_out[b] = n_out;
+    }
     const float* x = a.wave_in + (size_t)b * a.Nmax_in;
     float* y = a.wave_out + (size_t)b * a.Nmax_out;
     const int amod = (int)(((long long)b * a.Nmax_in) & 3);        // the row's first sample, modulo 16 bytes
@@ -86,8 +126,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
             continue;
         }
         __syncthreads();      // the table is in LDS; the previous tile's reads of the span are done
-        const unsigned u0 = (unsigned)j0 / (unsigned)a.ou, p0 = (unsigned)j0 - u0 * (unsigned)a.ou;
-        const int lo = first[p0] + (int)u0 * a.iu;    // first input sample of output j0 (may be negative at the row's start)
+        // column j0 is output o + j0 of the utterance (< 2^31: o < 2^30, j0 < n_out <= 2^30)
+        const unsigned u0 = (unsigned)(o + j0) / (unsigned)a.ou, p0 = (unsigned)(o + j0) - u0 * (unsigned)a.ou;
+        // first input sample of that output, counted from the row's first sample (may be negative)
+        const int lo = first[p0] + (int)u0 * a.iu - f;
         // row-relative start of the span: the element whose ABSOLUTE index in wave_in is the multiple of 4 at or below lo's
         const int s0 = lo - ((lo + amod) & 3);
         // four quads per thread at a time: the 16-byte loads of the quads that lie inside the row are all issued before the first
@@ -98,7 +140,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int s = s0 + 4 * (q0 + e * RS_THREADS);
-                in[e] = a.vec && q0 + e * RS_THREADS < a.span / 4 && s >= 0 && s + 4 <= n;
+                in[e] = a.vec && q0 + e * RS_THREADS < a.span / 4 && s >= 0 && s + 4 <= vhi;
                 if (in[e]) v[e] = *(const float4*)(x + s);
             }
 #pragma unroll
@@ -107,10 +149,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
                 if (q >= a.span / 4) break;
                 const int s = s0 + 4 * q;
                 if (!in[e]) {
-                    v[e].x = (s >= 0 && s < n) ? x[s] : 0.f;
-                    v[e].y = (s + 1 >= 0 && s + 1 < n) ? x[s + 1] : 0.f;
-                    v[e].z = (s + 2 >= 0 && s + 2 < n) ? x[s + 2] : 0.f;
-                    v[e].w = (s + 3 >= 0 && s + 3 < n) ? x[s + 3] : 0.f;
+                    v[e].x = (s >= 0 && s < vhi) ? x[s] : 0.f;
+                    v[e].y = (s + 1 >= 0 && s + 1 < vhi) ? x[s + 1] : 0.f;
+                    v[e].z = (s + 2 >= 0 && s + 2 < vhi) ? x[s + 2] : 0.f;
+                    v[e].w = (s + 3 >= 0 && s + 3 < vhi) ? x[s + 3] : 0.f;
                 }
                 span4[q] = v[e];
                 if (q > 0) spano[4 * q - 1] = v[e].x;
@@ -128,7 +170,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
             const unsigned i = (unsigned)(tid + c * RS_THREADS);
             const unsigned du = (p0 + i) / (unsigned)a.ou;                        // units past u0
             const int p = (int)(p0 + i - du * (unsigned)a.ou);
-            int r = first[p] + (int)(u0 + du) * a.iu - s0;
+            int r = first[p] + (int)(u0 + du) * a.iu - f - s0;
             // a table that is what the host builds keeps r in [0, span - 2 K2 - 1]; anything else stays inside the span
             r = min(max(r, 0), a.span - 2 * a.K2 - 1);
             // an odd start reads the shifted copy: its pair r >> 1 is (span[r], span[r + 1])
@@ -150,6 +192,24 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) {
     }
 }
 
+template <int NPT>
+__global__ __launch_bounds__(RS_THREADS) void resample_kernel(ResampleArgs a) { resample_body<NPT, false>(a); }
+
+template <int NPT>
+__global__ __launch_bounds__(RS_THREADS) void resample_span_kernel(ResampleSpanArgs a) { resample_body<NPT, true>(a); }
+
+// rows of a batch that pass through unchanged beside resampled ones: out[b][i] = in[b][i] for i < count[b], 0 up to Nmax_out
+__global__ __launch_bounds__(RS_THREADS) void copy_rows_kernel(const float* in, const int* count, const int* rows, int B, long long Nmax_in,
+                                                               long long Nmax_out, float* out) {
+    const int b = rows ? rows[blockIdx.y] : blockIdx.y;
+    if (b < 0 || b >= B) return;
+    const long long c = min((long long)max(count[b], 0), min(Nmax_in, Nmax_out));
+    const float* x = in + (size_t)b * Nmax_in;
+    float* y = out + (size_t)b * Nmax_out;
+    for (long long i = (long long)blockIdx.x * RS_THREADS + threadIdx.x; i < Nmax_out; i += (long long)gridDim.x * RS_THREADS)
+        y[i] = i < c ? x[i] : 0.f;
+}
+
 int rs_gcd(int a, int b) {
     while (b) {
         const int t = a % b;
@@ -169,38 +229,82 @@ extern "C" int spk_resample_tile(int iu, int ou, int K) {
     return 0;
 }
 
-extern "C" int spk_resample_fwd(const float* wave_in, const int* nsamp_in, int B, long long Nmax_in, const int* first,
-                                const float* wq, int fi, int fo, int K, float* wave_out, int* nsamp_out, long long Nmax_out,
-                                void* stream) {
-    SPK_REQUIRE(wave_in && nsamp_in && first && wq && wave_out && nsamp_out, "spk_resample_fwd: null pointer");
+// what the two forms share: the checks of the rates and sizes, the tile, the LDS layout and the grid (`gy` rows); < 0: refused
+static int rs_setup(const char* who, ResampleArgs& a, int gy, int B, long long Nmax_in, long long Nmax_out, int fi, int fo, int K,
+                    dim3& grid, int& lds) {
     SPK_REQUIRE(fi > 0 && fo > 0 && fi != fo && fi < (1 << 24) && fo < (1 << 24),
-                "spk_resample_fwd: rates %d -> %d Hz (positive, different, below 2^24)", fi, fo);
+                "%s: rates %d -> %d Hz (positive, different, below 2^24)", who, fi, fo);
     SPK_REQUIRE(B > 0 && B <= 65535 && Nmax_in > 0 && Nmax_out > 0 && Nmax_in < (1ll << 30) && Nmax_out < (1ll << 30) && K > 0,
-                "spk_resample_fwd: B=%d Nmax_in=%lld Nmax_out=%lld (< 2^30) K=%d", B, Nmax_in, Nmax_out, K);
+                "%s: B=%d Nmax_in=%lld Nmax_out=%lld (< 2^30) K=%d", who, B, Nmax_in, Nmax_out, K);
     const int g = rs_gcd(fi, fo), iu = fi / g, ou = fo / g;
-    SPK_REQUIRE((long long)iu * ou < (1ll << 31), "spk_resample_fwd: %d -> %d Hz: %d x %d samples per unit exceed 32-bit indexing",
-                fi, fo, iu, ou);
+    SPK_REQUIRE((long long)iu * ou < (1ll << 31), "%s: %d -> %d Hz: %d x %d samples per unit exceed 32-bit indexing", who, fi, fo, iu,
+                ou);
     const int TO = spk_resample_tile(iu, ou, K);
-    SPK_REQUIRE(TO > 0, "spk_resample_fwd: %d -> %d Hz needs a filter table of %d phases x %d taps (%lld bytes), which does not fit "
-                "the %d bytes of LDS the kernel is built for", fi, fo, ou, K, rs_table(ou, K) * 4, RS_LDS_LIMIT);
-    ResampleArgs a;
-    a.wave_in = wave_in; a.nsamp_in = nsamp_in; a.first = first; a.wq = (const float2*)wq; a.wave_out = wave_out; a.nsamp_out = nsamp_out;
+    SPK_REQUIRE(TO > 0, "%s: %d -> %d Hz needs a filter table of %d phases x %d taps (%lld bytes), which does not fit "
+                "the %d bytes of LDS the kernel is built for", who, fi, fo, ou, K, rs_table(ou, K) * 4, RS_LDS_LIMIT);
     a.Nmax_in = Nmax_in; a.Nmax_out = Nmax_out; a.iu = iu; a.ou = ou; a.K2 = (K + 1) / 2; a.TO = TO;
     a.span = (int)rs_span(TO, iu, ou, K);
     a.tab4 = (int)rs_table(ou, K);
-    a.vec = ((size_t)wave_in & 15) == 0 ? 1 : 0;       // 16-byte loads need an aligned base; otherwise element loads
+    a.vec = ((size_t)a.wave_in & 15) == 0 ? 1 : 0;     // 16-byte loads need an aligned base; otherwise element loads
     // tiles per workgroup: enough outputs to pay for loading the table once, as few as that allows (short rows keep the grid wide)
     const long long tiles = (Nmax_out + TO - 1) / TO;
     long long nt = (2ll * ou * K + TO - 1) / TO;
     nt = nt < 1 ? 1 : (nt > RS_NT ? RS_NT : nt);
     a.NT = (int)(nt > tiles ? tiles : nt);
     const long long gx = (tiles + a.NT - 1) / a.NT;
-    SPK_REQUIRE(gx < (1ll << 31), "spk_resample_fwd: Nmax_out=%lld exceeds the grid", Nmax_out);
-    const int lds = (a.tab4 + 2 * a.span) * 4;
-    const dim3 grid((unsigned)gx, (unsigned)B);
-    if (TO == 4 * RS_THREADS) hipLaunchKernelGGL(resample_kernel<4>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
-    else if (TO == 2 * RS_THREADS) hipLaunchKernelGGL(resample_kernel<2>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
+    SPK_REQUIRE(gx < (1ll << 31), "%s: Nmax_out=%lld exceeds the grid", who, Nmax_out);
+    lds = (a.tab4 + 2 * a.span) * 4;
+    grid = dim3((unsigned)gx, (unsigned)gy);
+    return 0;
+}
+
+extern "C" int spk_resample_fwd(const float* wave_in, const int* nsamp_in, int B, long long Nmax_in, const int* first,
+                                const float* wq, int fi, int fo, int K, float* wave_out, int* nsamp_out, long long Nmax_out,
+                                void* stream) {
+    SPK_REQUIRE(wave_in && nsamp_in && first && wq && wave_out && nsamp_out, "spk_resample_fwd: null pointer");
+    ResampleArgs a = {};
+    a.wave_in = wave_in; a.nsamp_in = nsamp_in; a.first = first; a.wq = (const float2*)wq; a.wave_out = wave_out; a.nsamp_out = nsamp_out;
+    dim3 grid;
+    int lds;
+    if (const int rc = rs_setup("spk_resample_fwd", a, B, B, Nmax_in, Nmax_out, fi, fo, K, grid, lds)) return rc;
+    if (a.TO == 4 * RS_THREADS) hipLaunchKernelGGL(resample_kernel<4>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
+    else if (a.TO == 2 * RS_THREADS) hipLaunchKernelGGL(resample_kernel<2>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(resample_kernel<1>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
     SPK_LAUNCH_CHECK("spk_resample_fwd");
+    return 0;
+}
+
+// ---- exports (include/spkwav.h) ----
+extern "C" int spkw_resample_span_fwd(const float* wave_in, const long long* ifirst, const int* icount, const long long* itotal,
+                                      const long long* ofirst, const int* ocount, const int* rows, int R, int B, long long Nmax_in,
+                                      const int* first, const float* wq, int fi, int fo, int K, float* wave_out, long long Nmax_out,
+                                      void* stream) {
+    SPK_REQUIRE(wave_in && ifirst && icount && itotal && ofirst && ocount && first && wq && wave_out,
+                "spkw_resample_span_fwd: null pointer");
+    SPK_REQUIRE(rows ? (R > 0 && R <= B) : R == B, "spkw_resample_span_fwd: R=%d rows of B=%d (R == B without a row list)", R, B);
+    ResampleSpanArgs a = {};
+    a.B = B;
+    a.wave_in = wave_in; a.first = first; a.wq = (const float2*)wq; a.wave_out = wave_out;
+    a.ifirst = ifirst; a.icount = icount; a.itotal = itotal; a.ofirst = ofirst; a.ocount = ocount; a.rows = rows;
+    dim3 grid;
+    int lds;
+    if (const int rc = rs_setup("spkw_resample_span_fwd", a, R, B, Nmax_in, Nmax_out, fi, fo, K, grid, lds)) return rc;
+    if (a.TO == 4 * RS_THREADS) hipLaunchKernelGGL(resample_span_kernel<4>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
+    else if (a.TO == 2 * RS_THREADS) hipLaunchKernelGGL(resample_span_kernel<2>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(resample_span_kernel<1>, grid, dim3(RS_THREADS), lds, (hipStream_t)stream, a);
+    SPK_LAUNCH_CHECK("spkw_resample_span_fwd");
+    return 0;
+}
+
+extern "C" int spkw_copy_rows_fwd(const float* wave_in, const int* count, const int* rows, int R, int B, long long Nmax_in,
+                                  float* wave_out, long long Nmax_out, void* stream) {
+    SPK_REQUIRE(wave_in && count && wave_out, "spkw_copy_rows_fwd: null pointer");
+    SPK_REQUIRE(B > 0 && B <= 65535 && (rows ? (R > 0 && R <= B) : R == B) && Nmax_in > 0 && Nmax_out > 0 && Nmax_in < (1ll << 30) &&
+                Nmax_out < (1ll << 30), "spkw_copy_rows_fwd: R=%d rows of B=%d, Nmax_in=%lld Nmax_out=%lld (< 2^30)", R, B, Nmax_in,
+                Nmax_out);
+    const long long gx = (Nmax_out + 4 * RS_THREADS - 1) / (4 * RS_THREADS);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)gx, (unsigned)R), dim3(RS_THREADS), 0, (hipStream_t)stream, wave_in, count,
+                       rows, B, Nmax_in, Nmax_out, wave_out);
+    SPK_LAUNCH_CHECK("spkw_copy_rows_fwd");
     return 0;
 }

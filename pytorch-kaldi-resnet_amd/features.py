@@ -8,7 +8,9 @@ The kernels are csrc/frontend.hip (include/spkhip.h: spk_fbank_fwd, spk_mfcc_fwd
 config files, builds the window / twiddle / mel / resampling tables in fp64 and runs the launches.  Semantics and numerics: DESIGN.md "Feature front end".
 Training from audio adds the span form of the two frame kernels (fbank_span / mfcc_span: the frames of a part of
 an utterance, bit for bit the frames of the whole), pcm16_to_f32, AugmentPool (the device-resident form of WavAugmentation) and
-ChunkFrontend, which ingest.WavTrainLoader runs on its copy stream.
+ChunkFrontend, which ingest.WavTrainLoader runs on its copy stream.  Speed-perturbed entries (`sox ... speed F` lines of a wav.scp)
+add the span form of the resampler (include/spkwav.h: resample_span, check_resample_spans - a span of the resampled signal from a
+span of the file, bit for bit the samples of resample() on the whole file) and SpeedBatch, ChunkFrontend's per-batch speed plan.
 Speech segments: SegmentOptions, vad_segments (spk_vad_segments: the VAD decisions of a batch -> speech segments, on
 the device) and Frontend(..., segments=): all frames kept, the segments in frames of the recording - the front of the diarization chain.
 The one deliberate difference from Kaldi: dither is a counter-based N(0,1) draw keyed by (seed, utt_id, frame, position), and the VAD
@@ -20,6 +22,7 @@ import collections
 import ctypes
 import hashlib
 import math
+import re
 import shlex
 
 import numpy as np
@@ -544,6 +547,105 @@ def resample(wave, nsamp, fi, fo):
     return out, n_out
 
 
+# ---- the span form of the resampler (include/spkwav.h; DESIGN.md sections 6e "Resampling" and 6k) ----
+def check_speed_table(what, fi, fo):
+    """refuse, before any launch, a resampling whose filter table exceeds the LDS budget of the kernel (`what` names the entry)"""
+    iu, ou, K = _resample_first(fi, fo)[:3]
+    if hip.lib().spk_resample_tile(iu, ou, K) == 0:
+        raise ValueError("%s: resampling %d -> %d Hz needs a filter table of %d phases x %d taps, beyond the LDS budget of the kernel "
+                         "(rates with a larger common divisor have fewer phases)" % (what, fi, fo, ou, K))
+
+
+def check_resample_spans(what, fi, fo, icount, ifirst, itotal, ofirst, ocount, Nmax_in, Nmax_out, rows=None):
+    """the refusals of resample_span, on host arrays, before any launch: every row (of `rows`: the others are not looked at) is a
+    part of its utterance, its outputs exist, and the row holds every sample of the utterance that ingest.resample_input_span
+    names for those outputs - the union of their windows with its margin.  Returns the five arrays as int64."""
+    from . import ingest
+    c, f, N, o, m = (_host_ints(v) for v in (icount, ifirst, itotal, ofirst, ocount))
+    B = c.size
+    if not (f.size == N.size == o.size == m.size == B):
+        raise ValueError("%s: icount, ifirst, itotal, ofirst and ocount must have one entry per row (%d rows)" % (what, B))
+    sel = np.arange(B) if rows is None else _host_ints(rows)
+    if sel.size == 0 or (sel < 0).any() or (sel >= B).any() or np.unique(sel).size != sel.size:
+        raise ValueError("%s: the row list must name distinct rows in [0, %d)" % (what, B))
+
+    def bad(mask, msg):
+        if mask[sel].any():
+            b = int(sel[np.nonzero(mask[sel])[0][0]])
+            raise ValueError("%s: row %d (samples %d .. +%d of an utterance of %d, outputs %d .. +%d): %s"
+                             % (what, b, int(f[b]), int(c[b]), int(N[b]), int(o[b]), int(m[b]), msg))
+    bad((N < 1) | (N >= 2 ** 30), "utterance length outside [1, 2^30)")
+    n_out = num_resampled(np.where((N < 1) | (N >= 2 ** 30), 1, N), fi, fo)
+    bad(n_out >= 2 ** 30, "the resampled utterance has 2^30 samples or more")
+    bad((c < 1) | (c > Nmax_in), "sample count outside [1, Nmax_in %d]" % Nmax_in)
+    bad((f < 0) | (f + c > N), "the row is not a part of the utterance")
+    bad((m < 1) | (m > Nmax_out), "output count outside [1, Nmax_out %d]" % Nmax_out)
+    bad((o < 0) | (o + m > n_out), "outputs outside the resampled utterance's")
+    need_first, need_count = ingest.resample_input_span(np.where(o < 0, 0, o), np.maximum(m, 1), N, fi, fo)
+    bad((need_first < f) | (need_first + need_count > f + c), "an output needs a sample of the utterance outside the row")
+    return c, f, N, o, m
+
+
+def _resample_span_launch(wave, ifirst, icount, itotal, ofirst, ocount, rows, fi, fo, out):
+    """the span launch on device arguments alone (no check of their values, nothing read back): wave [B, Nmax_in] and out
+    [B, Nmax_out] float32, ifirst / itotal / ofirst int64 [B], icount / ocount int32 [B], rows int32 [R] or None"""
+    B, Nmax_in = wave.shape
+    tab = _resample_cached(fi, fo, wave.device)
+    hip.call("spkw_resample_span_fwd", hip.ptr(wave), hip.ptr(ifirst), hip.ptr(icount), hip.ptr(itotal), hip.ptr(ofirst),
+             hip.ptr(ocount), hip.ptr(rows), B if rows is None else rows.numel(), B, Nmax_in, hip.ptr(tab.first_dev),
+             hip.ptr(tab.wq_dev), fi, fo, tab.K, hip.ptr(out), out.shape[1], hip.stream())
+    return out
+
+
+def _copy_rows_launch(wave, count, rows, out):
+    """rows of a batch that are not resampled: wave[b, :count[b]] into out[b], zeros behind (device arguments alone)"""
+    B, Nmax_in = wave.shape
+    hip.call("spkw_copy_rows_fwd", hip.ptr(wave), hip.ptr(count), hip.ptr(rows), B if rows is None else rows.numel(), B, Nmax_in,
+             hip.ptr(out), out.shape[1], hip.stream())
+    return out
+
+
+def resample_span(wave, icount, ifirst, itotal, ofirst, ocount, fi, fo, rows=None, out=None):
+    """A span of the resampled signal from a span of the utterance, equal bit for bit to the same samples of resample() on the
+    whole utterance.  Row b of wave (float32 cuda [B, Nmax_in], contiguous or a view whose rows are) holds samples ifirst[b] ..
+    ifirst[b] + icount[b] - 1 of an utterance of itotal[b] samples; written are outputs ofirst[b] .. ofirst[b] + ocount[b] - 1 of
+    that utterance resampled from fi to fo Hz, zeros behind them.  All five are host integers per row.  rows: the rows to work on
+    (host ints; the others are neither checked nor touched); out: float32 cuda [B, Nmax_out] to write into (default: a new
+    tensor with Nmax_out = the largest ocount of the rows, zero in the other rows).  Refused before any launch
+    (check_resample_spans): outputs that the resampled utterance does not have, a row that lacks a sample its outputs need
+    (ingest.resample_input_span gives the samples an output range needs), lengths at or above 2^30, a table beyond the kernel's
+    LDS budget."""
+    fi, fo = _int_rate(fi, "resample_span"), _int_rate(fo, "resample_span")
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+        raise ValueError("resample_span: wave must be a float32 cuda tensor [B, Nmax_in]")
+    if fi == fo:
+        raise ValueError("resample_span: %d -> %d Hz is no resampling" % (fi, fo))
+    B, Nmax_in = wave.shape
+    if B == 0 or Nmax_in == 0:
+        raise ValueError("resample_span: empty batch [%d, %d]" % (B, Nmax_in))
+    check_speed_table("resample_span", fi, fo)
+    sel = None if rows is None else _host_ints(rows)
+    m = _host_ints(ocount)
+    if out is None:
+        Nmax_out = int(m.max() if sel is None else m[sel[(sel >= 0) & (sel < m.size)]].max()) if m.size else 0
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or not out.is_cuda \
+            or not out.is_contiguous():
+        raise ValueError("resample_span: out must be a contiguous float32 cuda tensor [%d, Nmax_out]" % B)
+    else:
+        Nmax_out = out.shape[1]
+    c, f, N, o, m = check_resample_spans("resample_span", fi, fo, icount, ifirst, itotal, ofirst, ocount, Nmax_in, max(Nmax_out, 1), sel)
+    if not wave.is_contiguous():
+        wave = wave.contiguous()
+    dev = wave.device
+
+    def dv(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+    if out is None:
+        out = torch.zeros(B, Nmax_out, device=dev)
+    return _resample_span_launch(wave, dv(f, np.int64), dv(c, np.int32), dv(N, np.int64), dv(o, np.int64), dv(m, np.int32),
+                                 None if sel is None else dv(sel, np.int32), fi, fo, out)
+
+
 # ---- augmentation (the recipe's wav-reverberate entries; csrc/augment.hip, DESIGN.md section 6f) ----
 AUGMENT_FFT = 2048              # FFT size of the partitioned convolution (blocks of 1024 samples)
 _AUG_TWIDDLE = {}
@@ -679,9 +781,10 @@ def augment(wave, nsamp, rir=None, noises=None, quantize=False, sample_rate=1600
     return out, clipped.cpu().numpy()
 
 
-WavEntry = collections.namedtuple("WavEntry", "path rir_path noises augmented")
+WavEntry = collections.namedtuple("WavEntry", "path rir_path noises augmented speed", defaults=(None,))
 WavEntry.__doc__ = """one wav.scp entry: the speech file, the impulse-response file or None, the additive signals
-[(path, duration or None, start seconds, snr dB)], and whether anything is applied at all"""
+[(path, duration or None, start seconds, snr dB)], whether any of these is applied at all, and the speed factor of a `sox ... speed F`
+entry as the decimal string F (None: the file as it is; such an entry is never augmented)"""
 
 
 def _pipe_error(text, why):
@@ -716,7 +819,9 @@ def parse_wav_entry(text):
                                       (steps/data/reverberate_data_dir.py:345,365; augment_data_dir.py:116 on such a `cat` entry)
         wav-reverberate --shift-output=true --additive-signals='ITEM,..' --start-times='..' --snrs='..' PATH - |
                                                                             (steps/data/augment_data_dir.py:112)
-    with ITEM a plain path or `wav-reverberate --duration=D "PATH" - |` (augment_data_dir.py:87-88).  Everything else - another
+    with ITEM a plain path or `wav-reverberate --duration=D "PATH" - |` (augment_data_dir.py:87-88), and the speed-perturbed copy
+        sox -t wav PATH -t wav - speed F |                 (local/perturb_data_dir_speed.sh:83,95 on a plain path)
+    with F a decimal string, kept as a string in WavEntry.speed (a factor equal to 1 is the plain file).  Everything else - another
     command, another pipe in front, --shift-output=false, a top-level --duration, an impulse response inside an item, an unknown
     option, lists of unequal length - is a ValueError that says `pipe` and quotes the entry."""
     text = text.strip()
@@ -734,6 +839,13 @@ def parse_wav_entry(text):
         path, opts = tok[-3], _reverberate_options(tok[1:-3], text, True)
         if "impulse-response" in opts or "additive-signals" not in opts:
             raise _pipe_error(text, "expected --additive-signals and no --impulse-response")
+    elif len(tok) == 10 and tok[:3] == ["sox", "-t", "wav"] and tok[4:8] == ["-t", "wav", "-", "speed"] and tok[9] == "|":
+        path, factor = tok[3], tok[8]
+        if "|" in path or not path or path.startswith("-"):
+            raise _pipe_error(text, "speech file %r" % path)
+        if not re.fullmatch(r"[0-9]+(\.[0-9]*)?|\.[0-9]+", factor) or fractions.Fraction(factor) <= 0:
+            raise _pipe_error(text, "speed factor %r" % factor)
+        return WavEntry(path, None, [], False, None if fractions.Fraction(factor) == 1 else factor)
     else:
         raise _pipe_error(text, "not one of the wav-reverberate forms of the recipe")
     if "|" in path or not path:
@@ -1017,6 +1129,19 @@ class AugmentPool:
         return out
 
 
+class SpeedBatch:
+    """what ChunkFrontend needs for a batch with speed-perturbed rows.  Device tensors made by the caller: ofirst, ototal int64 [B]
+    and ocount int32 [B] - row b of the resampled buffer holds samples [ofirst, ofirst + ocount) of the perturbed utterance of
+    ototal samples (a plain row: what was read) - and rows int32 [B], the batch's rows grouped by factor.  Host values: groups
+    [(fi, fo, lo, hi)]: rows[lo:hi] are resampled from fi to fo Hz; plain (lo, hi): rows[lo:hi] are copied; Nmax_out: the width of
+    the resampled buffer (>= every ocount)."""
+    __slots__ = ("ofirst", "ototal", "ocount", "rows", "groups", "plain", "Nmax_out")
+
+    def __init__(self, ofirst, ototal, ocount, rows, groups, plain, Nmax_out):
+        self.ofirst, self.ototal, self.ocount, self.rows = ofirst, ototal, ocount, rows
+        self.groups, self.plain, self.Nmax_out = groups, plain, int(Nmax_out)
+
+
 class ChunkFrontend:
     """Audio of a batch of training chunks -> the chunks, on the current stream: spk_pcm16_to_f32, the augmentation of the rows
     that have one (AugmentPool), the span fbank / MFCC (fbank_opts: FbankOptions or MfccOptions) and spk_cmn_select with
@@ -1026,14 +1151,19 @@ class ChunkFrontend:
         pcm int16 [B, Nmax]: row b = samples first[b] .. + count[b] of an utterance of total[b] samples (int32 / int64 / int64 [B])
         frame0, nframes int32 [B]: the frames of the utterance that are computed; rel int32 [B, Tcap], Tcap >= max nframes: in its
         first T columns the T selected frames, counted from frame0; plan: AugmentPool.plan of the batch or None
-    times: None, or a dict that gets (start, end) event pairs per stage ("convert", "augment", "frontend", "cmn")."""
+    times: None, or a dict that gets (start, end) event pairs per stage ("convert", "augment", "resample", "frontend", "cmn").
+    speed: None, or the SpeedBatch of a batch with speed-perturbed rows (`sox ... speed F` entries).  pcm, count, first and total
+    then describe what was read from the FILE, and frame0 / nframes / rel count frames of the PERTURBED utterance: after the
+    conversion (and the augmentation of the plain rows that have one) every group of rows of one factor goes through one
+    spkw_resample_span_fwd launch and the plain rows through spkw_copy_rows_fwd, all into one [B, Nmax_out] buffer, which the
+    span front end reads with first = speed.ofirst, total = speed.ototal and count = speed.ocount."""
 
     def __init__(self, fbank_opts, cmn=None, seed=0, pool=None):
         self.opts, self.cmn, self.seed, self.pool = fbank_opts, cmn, seed, pool
         self.mfcc = isinstance(fbank_opts, MfccOptions)
         self.dim = fbank_opts.num_ceps if self.mfcc else fbank_opts.num_mel_bins
 
-    def __call__(self, pcm, count, first, total, frame0, nframes, rel, T, utt_ids=None, plan=None, times=None):
+    def __call__(self, pcm, count, first, total, frame0, nframes, rel, T, utt_ids=None, plan=None, times=None, speed=None):
         B, Nmax = pcm.shape
         Tcap = rel.shape[1]
         dev = pcm.device
@@ -1060,6 +1190,16 @@ class ChunkFrontend:
                 wave.index_copy_(0, rows, self.pool.apply(wave.index_select(0, rows), count.index_select(0, rows), plan))
                 return wave
             wave = stage("augment", aug)
+        if speed is not None:
+            def resample_rows():
+                out = torch.empty(B, speed.Nmax_out, device=dev)
+                for fi, fo, lo, hi in speed.groups:
+                    _resample_span_launch(wave, first, count, total, speed.ofirst, speed.ocount, speed.rows[lo:hi], fi, fo, out)
+                if speed.plain[1] > speed.plain[0]:
+                    _copy_rows_launch(wave, count, speed.rows[speed.plain[0]:speed.plain[1]], out)
+                return out
+            wave = stage("resample", resample_rows)
+            count, first, total = speed.ocount, speed.ofirst, speed.ototal
         feats, _ = stage("frontend", lambda: _launch(self.mfcc, self.opts, wave, count, utt_ids, self.seed, Tcap,
                                                      span=(first, total, frame0, nframes)))
         W = int(self.cmn.cmn_window) if self.cmn is not None else 0
@@ -1389,7 +1529,8 @@ def options_from_configs(fbank_config=None, vad_config=None, cmn_window=0, mfcc_
     return fb, vad_opts, cmn
 
 
-def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsample=False, speed=None, augment=False):
+def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsample=False, speed=None, augment=False,
+                    speed_entries=False):
     """(keys, ingest.WavTable, batches [(indices, Nmax)], indices shorter than one frame) of a wav.scp ('key path' lines; pipe
     entries are refused, except - with augment=True, for a caller that applies them - the wav-reverberate entries that
     parse_wav_entry accepts): length-sorted by the speech file's sample count, at most 10 % padded samples per batch.  With such
@@ -1399,15 +1540,27 @@ def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsam
 
     A file whose header rate is above / below fb.sample_frequency is refused, naming it, unless allow_downsample / allow_upsample
     is set (compute-fbank-feats' flags).  With them every batch holds files of ONE rate, table.rate[indices[0]]: files are grouped
-    by rate, then sorted and padded within a rate.  `short` is judged on the length after resampling (and after `speed`)."""
+    by rate, then sorted and padded within a rate.  `short` is judged on the length after resampling (and after `speed`).
+
+    speed_entries=True, for a caller that applies them: the `sox ... speed F` entries of a speed-perturbed data directory are
+    taken (without it they are refused like any other pipe).  table.speed[i] is then entry i's factor (the decimal string, or None)
+    and no batch mixes (file rate, factor): batch b is resampled from speed_rates(table.speed[i], fo, table.rate[i])[0] to fo
+    for i = indices[0].  Such entries do not combine with the `speed` argument, and a factor whose filter table exceeds the LDS
+    budget of the resampler is refused here, naming the key."""
     from . import ingest
     keys, entries = read_wav_scp(wav_scp) if isinstance(wav_scp, str) else wav_scp
     augmented = any(e.augmented for e in entries)
     if augmented and not augment:
         raise ValueError("wav.scp pipe entries are not applied here: %r" % [e for e in entries if e.augmented][0].path)
+    perturbed = [i for i, e in enumerate(entries) if e.speed is not None]
+    if perturbed and not speed_entries:
+        raise ValueError("wav.scp pipe entries are not applied here: %r (a `sox ... speed` entry)" % entries[perturbed[0]].path)
+    if perturbed and speed is not None:
+        raise ValueError("speed %s does not combine with the `sox ... speed` entries of the wav.scp (%s)" % (speed, keys[perturbed[0]]))
     table = ingest.WavTable([e.path for e in entries], 0)
     if augmented:
         table.augmentation = WavAugmentation(table, entries)
+    table.speed = [e.speed for e in entries]
     fo = _int_rate(fb.sample_frequency, "wav_scp_batches")
     for i in np.nonzero(table.rate != fo)[0]:
         r = int(table.rate[i])
@@ -1416,16 +1569,24 @@ def wav_scp_batches(wav_scp, fb, batch_size, allow_downsample=False, allow_upsam
         if r < fo and not allow_upsample:
             raise ValueError("%s: sample rate %d is below sample_frequency %d (--allow-upsample resamples it)" % (table.paths[i], r, fo))
     n_eff = np.zeros(len(keys), dtype=np.int64)
+    # the factor of every entry as a group number: 0 = none, then the distinct factors in order of their value
+    factors = sorted({e.speed for e in entries if e.speed is not None}, key=fractions.Fraction)
+    group = np.asarray([0 if e.speed is None else 1 + factors.index(e.speed) for e in entries], dtype=np.int64)
     for r in np.unique(table.rate):
-        sel = table.rate == r
-        fi = speed_rates(speed, fo, int(r))[0] if speed is not None else int(r)
-        n_eff[sel] = num_resampled(table.nsamp[sel], fi, fo)
+        for g in np.unique(group[table.rate == r]):
+            sel = (table.rate == r) & (group == g)
+            f = speed if g == 0 else factors[g - 1]
+            fi = speed_rates(f, fo, int(r))[0] if f is not None else int(r)
+            if g:
+                check_speed_table("%s (speed %s)" % (keys[int(np.nonzero(sel)[0][0])], f), fi, fo)
+            n_eff[sel] = num_resampled(table.nsamp[sel], fi, fo)
     good = n_eff >= fb.frame_len
     short = np.nonzero(~good)[0]
     batches = []
     for r in np.unique(table.rate[good]):
-        ok = np.nonzero(good & (table.rate == r))[0]
-        batches += [(ok[b], int(n)) for b, n in ingest.pad_batches(table.nsamp[ok], batch_size, quantum=1)]
+        for g in np.unique(group[good & (table.rate == r)]):
+            ok = np.nonzero(good & (table.rate == r) & (group == g))[0]
+            batches += [(ok[b], int(n)) for b, n in ingest.pad_batches(table.nsamp[ok], batch_size, quantum=1)]
     return keys, table, batches, short
 
 

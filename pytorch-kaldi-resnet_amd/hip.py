@@ -186,6 +186,13 @@ _CAL_SIGS = {
     "spk_cal_pav": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
 }
 
+# training from audio with speed perturbation (include/spkwav.h, csrc/resample.hip): the fourth header; its names are spkw_*, so the
+# set of spk_* exports that the other three tables pin is as it was
+_WAV_SIGS = {
+    "spkw_resample_span_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P, _P, _I, _I, _I, _P, _L, _P],
+    "spkw_copy_rows_fwd": [_P, _P, _P, _I, _I, _L, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -224,7 +231,7 @@ def lib():
         l.spk_error_sweep_workspace.argtypes = [_I, _I]
         l.spk_scatter_f64_workspace.restype = ctypes.c_size_t
         l.spk_scatter_f64_workspace.argtypes = [_L, _I]
-        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()) + list(_CAL_SIGS.items()):
+        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()) + list(_CAL_SIGS.items()) + list(_WAV_SIGS.items()):
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
@@ -258,6 +265,11 @@ def der_symbols():
 def cal_symbols():
     """the exports include/spkcal.h declares"""
     return list(_CAL_SIGS)
+
+
+def wav_symbols():
+    """the exports include/spkwav.h declares"""
+    return list(_WAV_SIGS)
 
 
 def ptr(t):

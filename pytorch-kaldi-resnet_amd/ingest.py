@@ -596,6 +596,29 @@ def plan_spans(voiced_idx, v0, T, W, total_frames, opts, nsamp):
     return SpanPlan(lo, hi, first, last - first, (sel - lo[:, None]).astype(np.int32))
 
 
+RESAMPLE_SPAN_MARGIN = 1        # samples resample_input_span adds at either end of the windows' union (before the cut to the file)
+
+
+def resample_input_span(ofirst, ocount, nsamp, fi, fo):
+    """The samples of an utterance of nsamp samples that outputs [ofirst, ofirst + ocount) of its resampling from fi to fo Hz read
+    (numpy only; integers or integer arrays, ocount >= 1): (first, count).  With features.resample_tables' (iu, ou, K, first),
+    output j reads the window [a(j), a(j) + K), a(j) = first[j % ou] + (j // ou) * iu.  The span is
+        [a(ofirst) - MARGIN, a(ofirst + ocount - 1) + K + MARGIN)   cut to [0, nsamp),   MARGIN = RESAMPLE_SPAN_MARGIN = 1
+    which holds the union of the windows of the range: a(j) is ceil(x_j) of a value x_j that grows with j, computed in fp64 with an
+    error far below 1/2, so a later window can start before an earlier one by at most one sample - hence
+    the margin, instead of an assumption that a(j) is monotone across a unit boundary.  The span is never longer than the union
+    plus 2 MARGIN, and it is never empty (at least one sample, inside the file)."""
+    from . import features
+    t = features._resample_cached(features._int_rate(fi, "resample_input_span"), features._int_rate(fo, "resample_input_span"), None)
+    o, m, n = (np.asarray(v, dtype=np.int64) for v in (ofirst, ocount, nsamp))
+    last = o + m - 1
+    a0 = t.first[o % t.ou] + (o // t.ou) * t.iu
+    a1 = t.first[last % t.ou] + (last // t.ou) * t.iu
+    lo = np.minimum(np.maximum(a0 - RESAMPLE_SPAN_MARGIN, 0), np.maximum(n - 1, 0))
+    hi = np.maximum(np.minimum(a1 + t.K + RESAMPLE_SPAN_MARGIN, n), lo + 1)
+    return lo, hi - lo
+
+
 class WavTrainLoader:
     """NativeTrainLoader for audio: iterable over (chunks [B, F, T] cuda float32, labels [B] cuda int64) of one epoch for this
     rank, the chunks computed from 16-bit PCM WAV files as they are drawn.  Same class balancing, permutation, sharding, chunk
@@ -604,7 +627,11 @@ class WavTrainLoader:
     length T), and the chunk is columns v0 .. v0 + T - 1 of that entry's matrix, to one fp32 ulp.
 
     wav_scp: the recipe's wav.scp - plain paths and the wav-reverberate entries features.parse_wav_entry accepts, which are
-    applied to the span that is read (features.AugmentPool); vad_scp: the 0/1 vector per key (None: every frame is voiced);
+    applied to the span that is read (features.AugmentPool), and the `sox -t wav PATH -t wav - speed F |` entries of a
+    speed-perturbed copy (local/perturb_data_dir_speed.sh), which are resampled on the GPU: frames, voiced frames and the VAD
+    vector of such an entry are those of the PERTURBED utterance, of num_resampled(nsamp, *speed_rates(F, rate)) samples - the
+    archive compute_fbank.py writes for the same wav.scp - and the reader reads the span of the file that the span of the perturbed
+    signal needs (resample_input_span); vad_scp: the 0/1 vector per key (None: every frame is voiced);
     opts: FbankOptions or MfccOptions, cmn: CmnOptions or None, feat_seed: the dither seed (compute_fbank.py --seed).
     The reader thread plans the spans (plan_spans) and reads them (WavTable.read_span) into a ring of pinned int16 slots; the
     consumer copies a slot and its numbers on the loader's copy stream and runs features.ChunkFrontend there, behind the previous
@@ -633,11 +660,36 @@ class WavTrainLoader:
             raise ValueError("%s (--sample-frequency is %d: resample the file offline, compute_fbank.py --allow-downsample / "
                              "--allow-upsample)" % (e, fs))
         n = len(keys)
-        short = np.nonzero(self.table.nsamp < opts.frame_len)[0]
+        short = np.nonzero((self.table.nsamp < opts.frame_len) & np.asarray([e.speed is None for e in entries]))[0]
         if short.size:
             raise ValueError("%s: %d samples, shorter than one frame (%d)" % (self.table.paths[short[0]],
                                                                               int(self.table.nsamp[short[0]]), opts.frame_len))
-        self.frames = np.asarray([opts.num_frames(int(v)) for v in self.table.nsamp], dtype=np.int64)
+        # speed-perturbed entries: the rates of their resampling and their length on the perturbed clock; a plain entry has its own
+        self.speed = [e.speed for e in entries]
+        self.has_speed = any(v is not None for v in self.speed)
+        self.nsamp_out = self.table.nsamp.astype(np.int64).copy()
+        self.group = np.zeros(n, dtype=np.int64)        # 0: plain, g > 0: rates[g - 1]
+        self.rates = []
+        for i, e in enumerate(entries):
+            if e.speed is None:
+                continue
+            if e.augmented:
+                raise ValueError("%s: speed %s does not combine with wav-reverberate entries" % (keys[i], e.speed))
+            fi, fo = features.speed_rates(e.speed, fs)
+            if (fi, fo) not in self.rates:
+                features.check_speed_table("%s (speed %s)" % (keys[i], e.speed), fi, fo)
+                self.rates.append((fi, fo))
+            self.group[i] = 1 + self.rates.index((fi, fo))
+            self.nsamp_out[i] = features.num_resampled(int(self.table.nsamp[i]), fi, fo)
+            if self.table.nsamp[i] >= 2 ** 30 or self.nsamp_out[i] >= 2 ** 30:
+                raise ValueError("%s: %s has %d samples (%d at speed %s): the span resampler takes fewer than 2^30"
+                                 % (keys[i], self.table.paths[i], int(self.table.nsamp[i]), int(self.nsamp_out[i]), e.speed))
+        short = np.nonzero(self.nsamp_out < opts.frame_len)[0]
+        if short.size:
+            raise ValueError("%s: %s has %d samples at speed %s, shorter than one frame (%d)"
+                             % (keys[short[0]], self.table.paths[short[0]], int(self.nsamp_out[short[0]]), self.speed[short[0]],
+                                opts.frame_len))
+        self.frames = np.asarray([opts.num_frames(int(v)) for v in self.nsamp_out], dtype=np.int64)
         self.voiced = [None] * n
         self.rows = self.frames.copy()
         if vad_scp is not None:
@@ -692,21 +744,40 @@ class WavTrainLoader:
                            self.sample_to_row, self.rows)
 
     def plan(self, rows, starts, T):
+        """the span plan of a batch, on the clock the frames are counted on (the perturbed one for a speed entry)"""
         r = np.asarray(rows, dtype=np.int64)
-        return plan_spans([self.voiced[i] for i in r], starts, T, self.W, self.frames[r], self.opts, self.table.nsamp[r])
+        return plan_spans([self.voiced[i] for i in r], starts, T, self.W, self.frames[r], self.opts, self.nsamp_out[r])
+
+    def input_spans(self, rows, p):
+        """(first, count) of the samples of each row's FILE that the plan p of the batch needs: p's own for a plain row,
+        resample_input_span of p's output samples for a speed row"""
+        r = np.asarray(rows, dtype=np.int64)
+        first, count = p.first.astype(np.int64).copy(), p.count.astype(np.int64).copy()
+        for g in np.unique(self.group[r]):
+            if g:
+                m = self.group[r] == g
+                first[m], count[m] = resample_input_span(p.first[m], p.count[m], self.table.nsamp[r[m]], *self.rates[g - 1])
+        return first, count
 
     def __iter__(self):
         import time
+        from . import features
         draws = self.draws()
         dev, bs, S = self.device, self.bs, self.opts.frame_sh
         nslot = self.prefetch + 2
         # a row of the ring: the samples of T + W + SLACK frames; a batch that needs more (sparse voiced frames) gets its own buffer
-        ring_n = -(-((self.T + self.W + self.SLACK) * S + self.opts.frame_len) // 8) * 8
+        ring_n = (self.T + self.W + self.SLACK) * S + self.opts.frame_len
+        # a speed row reads fi / fo input samples per sample of the span, the filter's taps and the margin: sized for the largest
+        ring_n = max([ring_n] + [-(-ring_n * fi // fo) + features.resample_tables(fi, fo)[2] + 2 * RESAMPLE_SPAN_MARGIN + 1
+                                 for fi, fo in self.rates])
+        ring_n = -(-ring_n // 8) * 8
         ring_t = self.T + 2 * self.W + self.SLACK
         ring = [torch.empty(bs * ring_n, dtype=torch.int16).pin_memory() for _ in range(nslot)]
-        # the numbers of a batch: int64 [3][B] (first, total, utt id), int32 [3][B] (count, frame0, nframes) + rel [B][Tcap]
-        iring = [(torch.empty(3 * bs, dtype=torch.int64).pin_memory(), torch.empty(bs * (3 + ring_t), dtype=torch.int32).pin_memory())
-                 for _ in range(nslot)]
+        # the numbers of a batch: int64 [3][B] (first, total, utt id), int32 [3][B] (count, frame0, nframes) + rel [B][Tcap]; with
+        # speed entries two more rows each: (ofirst, ototal) and (ocount, the rows grouped by factor)
+        n64, n32 = (5, 5) if self.has_speed else (3, 3)
+        iring = [(torch.empty(n64 * bs, dtype=torch.int64).pin_memory(),
+                  torch.empty(bs * (n32 + ring_t), dtype=torch.int32).pin_memory()) for _ in range(nslot)]
         copied = [None] * nslot
         q = queue.Queue(maxsize=self.prefetch)
 
@@ -716,7 +787,8 @@ class WavTrainLoader:
                     t0 = time.perf_counter()
                     B = len(sel)
                     p = self.plan(rows, starts, T)
-                    Nmax = -(-int(p.count.max()) // 8) * 8
+                    ifirst, icount = self.input_spans(rows, p) if self.has_speed else (p.first, p.count)
+                    Nmax = -(-int(icount.max()) // 8) * 8
                     Tcap = int((p.frame_hi - p.frame_lo).max())
                     slot = k % nslot
                     ev = copied[slot]
@@ -724,18 +796,28 @@ class WavTrainLoader:
                         ev.synchronize()            # the device has finished reading this slot's pinned buffers
                     fits = Nmax <= ring_n and Tcap <= ring_t
                     pcm = (ring[slot][:B * Nmax] if fits else torch.empty(B * Nmax, dtype=torch.int16).pin_memory()).view(B, Nmax)
-                    m64 = iring[slot][0][:3 * B].view(3, B)
-                    m32 = (iring[slot][1][:B * (3 + Tcap)] if fits else torch.empty(B * (3 + Tcap), dtype=torch.int32).pin_memory())
-                    self.table.read_span(rows, p.first, p.count, Nmax, pcm, self.threads)
+                    m64 = iring[slot][0][:n64 * B].view(n64, B)
+                    m32 = (iring[slot][1][:B * (n32 + Tcap)] if fits else torch.empty(B * (n32 + Tcap), dtype=torch.int32).pin_memory())
+                    self.table.read_span(rows, ifirst, icount, Nmax, pcm, self.threads)
                     m64n, m32n = m64.numpy(), m32.numpy()
-                    m64n[0], m64n[1], m64n[2] = p.first, self.table.nsamp[rows], self.utt_ids[rows]
-                    m32n[:B], m32n[B:2 * B], m32n[2 * B:3 * B] = p.count, p.frame_lo, p.frame_hi - p.frame_lo
-                    rel = m32n[3 * B:].reshape(B, Tcap)
+                    m64n[0], m64n[1], m64n[2] = ifirst, self.table.nsamp[rows], self.utt_ids[rows]
+                    m32n[:B], m32n[B:2 * B], m32n[2 * B:3 * B] = icount, p.frame_lo, p.frame_hi - p.frame_lo
+                    sp = None
+                    if self.has_speed:
+                        g = self.group[rows]
+                        order = np.argsort(g, kind="stable")
+                        lo = np.searchsorted(g[order], np.arange(len(self.rates) + 2))
+                        m64n[3], m64n[4] = p.first, self.nsamp_out[rows]
+                        m32n[3 * B:4 * B], m32n[4 * B:5 * B] = p.count, order
+                        if lo[1] < B:       # a batch without a speed row takes the plain chain
+                            sp = ([self.rates[j - 1] + (int(lo[j]), int(lo[j + 1])) for j in range(1, len(self.rates) + 1)
+                                   if lo[j + 1] > lo[j]], (0, int(lo[1])), -(-int(p.count.max()) // 4) * 4)
+                    rel = m32n[n32 * B:].reshape(B, Tcap)
                     rel[:, :T] = p.rel
                     rel[:, T:] = 0
                     aplan = self.pool.plan(rows) if self.pool is not None else None
                     self.reader_seconds.append(time.perf_counter() - t0)
-                    q.put((slot, pcm, m64, m32, T, Tcap, aplan, torch.from_numpy(self.labels[sel])))
+                    q.put((slot, pcm, m64, m32, T, Tcap, aplan, sp, torch.from_numpy(self.labels[sel])))
                 q.put(None)
             except BaseException as e:      # surface reader errors in the training loop
                 q.put(e)
@@ -749,7 +831,7 @@ class WavTrainLoader:
                 break
             if isinstance(item, BaseException):
                 raise item
-            slot, pcm, m64, m32, T, Tcap, aplan, lab = item
+            slot, pcm, m64, m32, T, Tcap, aplan, sp, lab = item
             B = pcm.shape[0]
             cur = torch.cuda.current_stream(dev)
             with torch.cuda.stream(copy_stream):
@@ -764,8 +846,10 @@ class WavTrainLoader:
                 if times is not None:
                     h1.record()
                     times["h2d"] = (h0, h1)
-                xg = self.frontend(pg, g32[:B], g64[0], g64[1], g32[B:2 * B], g32[2 * B:3 * B], g32[3 * B:].view(B, Tcap), T,
-                                   g64[2], aplan, times)
+                if sp is not None:
+                    sp = features.SpeedBatch(g64[3], g64[4], g32[3 * B:4 * B], g32[4 * B:5 * B], *sp)
+                xg = self.frontend(pg, g32[:B], g64[0], g64[1], g32[B:2 * B], g32[2 * B:3 * B], g32[n32 * B:].view(B, Tcap), T,
+                                   g64[2], aplan, times, sp)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)
             if times is not None:

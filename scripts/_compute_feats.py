@@ -61,6 +61,9 @@ def main(kind):
         parser.error(str(e))
     if augmented and args.speed:
         parser.error("--speed does not combine with wav-reverberate entries in %s" % args.wav_scp)
+    if args.speed and any(e.speed is not None for e in parsed[1]):
+        parser.error("--speed does not combine with the `sox ... speed` entries in %s: their keys and factors are the wav.scp's own"
+                     % args.wav_scp)
     torch.cuda.set_device(args.gpu)
     cmn_window = args.cmn_window if args.egs else 0
     if kind == "fbank":
@@ -74,7 +77,7 @@ def main(kind):
         if args.speed:
             features.speed_rates(args.speed, fo)
         keys, table, batches, short = features.wav_scp_batches(parsed, fb, args.batch_size, args.allow_downsample,
-                                                               args.allow_upsample, args.speed, augment=True)
+                                                               args.allow_upsample, args.speed, augment=True, speed_entries=True)
     except ValueError as e:
         parser.error(str(e))
     vad_scp = dict(l.split(None, 1) for l in open(args.vad_scp) if l.strip()) if args.vad_scp else None
@@ -83,11 +86,12 @@ def main(kind):
         orig = keys
         keys = [features.speed_key(args.speed, k) for k in orig]
 
-    def rate_in(r):             # the rate a file of header rate r is resampled FROM (to fo)
-        return features.speed_rates(args.speed, fo, int(r))[0] if args.speed else int(r)
+    def rate_in(i):             # the rate entry i is resampled FROM (to fo): --speed, or the factor of its own `sox ... speed` line
+        f = args.speed or table.speed[i]
+        return features.speed_rates(f, fo, int(table.rate[i]))[0] if f else int(table.rate[i])
     for i in short:
         print(name + ": skipping %s: %d samples at %d Hz, shorter than one frame (%d)" % (
-            keys[i], features.num_resampled(int(table.nsamp[i]), rate_in(table.rate[i]), fo), fo, fb.frame_len))
+            keys[i], features.num_resampled(int(table.nsamp[i]), rate_in(i), fo), fo, fb.frame_len))
     os.makedirs(args.out_dir, exist_ok=True)
     ark = os.path.abspath(os.path.join(args.out_dir, "feats.ark"))
     vark = os.path.abspath(os.path.join(args.out_dir, "vad.ark"))
@@ -112,7 +116,7 @@ def main(kind):
                 except ValueError as e:
                     sys.exit(name + ": %s" % e)
                 clipped += int(nclip.sum())
-            wave, nsamp = features.resample(wave, table.nsamp[idx], rate_in(table.rate[idx[0]]), fo)     # one rate per batch
+            wave, nsamp = features.resample(wave, table.nsamp[idx], rate_in(idx[0]), fo)     # one (rate, speed) per batch
             feats, T, loge = compute(wave, nsamp, fb, ids, args.seed)
             v = None
             if vad_scp is not None:

@@ -14,7 +14,10 @@ Files at another sample rate than --sample-frequency of the fbank config are an 
 speed-perturbed copy of the set as the reference's local/perturb_data_dir_speed.sh lays it out: keys sp<F>-<utt>, and with --utt2spk
 the files utt2spk (sp<F>-<utt> sp<F>-<spk>) and utt2uniq (sp<F>-<utt> <utt>); one factor per run.  The audio is resampled from
 F x rate to rate (LinearResample, where the shell script runs `sox speed`), the VAD sees the perturbed audio, and the dither is keyed
-by the written key, so the copies of an utterance get different noise.
+by the written key, so the copies of an utterance get different noise.  The wav.scp of a directory that
+perturb_data_dir_speed.sh made (or of train plus its copies combined) is read as it stands: a `sox -t wav PATH -t wav - speed F |` line
+is resampled by its own factor and written under its own key, so one command writes the archive, vad.scp and utt2num_frames that
+train_resnet.py --wav-scp on the same wav.scp is compared against; --speed does not combine with such lines.
 
 Entries that are the recipe's wav-reverberate commands (feature_pre.sh:109-167: the reverb, noise, music and babble copies that
 steps/data/reverberate_data_dir.py and steps/data/augment_data_dir.py write; the grammar: features.parse_wav_entry) are applied on

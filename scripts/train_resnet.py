@@ -75,8 +75,9 @@ parser.add_argument("--no-graph", action="store_true",
                     help="launch kernels eagerly instead of replaying the step as hipGraph(s); both forms overlap the "
                          "stage-bucketed gradient all-reduce with backward")
 parser.add_argument("--wav-scp", type=str,
-                    help="train from audio: the recipe's wav.scp of train_combined (16-bit PCM mono WAV paths and its wav-reverberate "
-                         "entries) instead of --train-list; the chunks are computed on the GPU as they are drawn and equal the columns "
+                    help="train from audio: the recipe's wav.scp of train_combined (16-bit PCM mono WAV paths, its wav-reverberate "
+                         "entries and the `sox -t wav PATH -t wav - speed F |` entries of speed-perturbed copies, whose --vad-scp "
+                         "vectors are those of the perturbed audio) instead of --train-list; the chunks are computed on the GPU as they are drawn and equal the columns "
                          "of the archive compute_fbank.py / compute_mfcc.py --egs --vad-scp --cmn-window writes; --dataset v1 only")
 parser.add_argument("--vad-scp", type=str, help="with --wav-scp: vad.scp of 0/1 vectors per key (without it every frame is voiced)")
 parser.add_argument("--fbank-config", type=str, help="with --wav-scp: Kaldi config file of compute-fbank-feats options")
