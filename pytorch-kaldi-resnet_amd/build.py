@@ -10,7 +10,7 @@ SOURCES = ["err.cpp", "conv_mfma.hip", "conv_wgrad.hip", "stem.hip", "bn.hip", "
            "sgd.hip", "score.hip", "conv_split.hip", "conv_wgrad_split.hip", "pack.hip", "conv_pipe.hip", "conv_wgrad_1x1.hip",
            "conv_wgrad_wm.hip", "conv_wgrad_wm16.hip", "conv1x1_stream.hip", "conv3x3_c32_stream.hip",
            "frontend.hip", "resample.hip", "augment.hip", "cm.hip", "eval.hip", "se.hip", "plda.hip", "half.hip",
-           "window.hip", "diar.hip", "pca.hip", "der.hip", "cal.hip"]
+           "window.hip", "diar.hip", "pca.hip", "der.hip", "cal.hip", "boot.hip"]
 # kernel forms that were measured and did not pay: producer / consumer convolution and weight gradient,
 # in-wave pipelined weight gradient, in-wave pipelined fused-BatchNorm-backward data gradient.  Kept as source for reference and
 # for the bit-identity tests; compiled only with SPK_EXPERIMENTAL=1 (-DSPK_EXPERIMENTAL; spk_build_flags() & 1)

@@ -193,6 +193,16 @@ _WAV_SIGS = {
     "spkw_copy_rows_fwd": [_P, _P, _P, _I, _I, _L, _P, _L, _P],
 }
 
+# speaker-level bootstrap of the error-rate sweep (include/spkboot.h, csrc/boot.hip): the fifth header; its names are spkb_*
+_BOOT_SIGS = {
+    "spkb_limit": [_I],
+    "spkb_pitch": [_I],
+    "spkb_group": [_I],
+    "spkb_pack": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P],
+    "spkb_sweep_ws_elems": [_I, _I, _I, _I],            # host only; returns long long
+    "spkb_sweep": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _L, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -231,7 +241,8 @@ def lib():
         l.spk_error_sweep_workspace.argtypes = [_I, _I]
         l.spk_scatter_f64_workspace.restype = ctypes.c_size_t
         l.spk_scatter_f64_workspace.argtypes = [_L, _I]
-        for name, sig in list(_SIGS.items()) + list(_DER_SIGS.items()) + list(_CAL_SIGS.items()) + list(_WAV_SIGS.items()):
+        for name, sig in (list(_SIGS.items()) + list(_DER_SIGS.items()) + list(_CAL_SIGS.items()) + list(_WAV_SIGS.items())
+                          + list(_BOOT_SIGS.items())):
             fn = getattr(l, name)
             fn.argtypes = sig
             fn.restype = ctypes.c_int
@@ -239,7 +250,7 @@ def lib():
         l.spk_syevj_ws_elems.restype = ctypes.c_longlong
         l.spk_pca_plda_ws_elems.restype = ctypes.c_longlong
         l.spk_der_ws_elems.restype = ctypes.c_longlong
-        for name in ("spk_cal_cllr_ws_elems", "spk_cal_train_ws_elems", "spk_cal_pav_ws_elems"):
+        for name in ("spk_cal_cllr_ws_elems", "spk_cal_train_ws_elems", "spk_cal_pav_ws_elems", "spkb_sweep_ws_elems"):
             getattr(l, name).restype = ctypes.c_longlong
         if os.environ.get("SPK_POOL_ROWS", "1") == "0":      # A/B: the serial two-pass pooling forward at every width
             l.spk_stats_pool_row_form(0)
@@ -270,6 +281,11 @@ def cal_symbols():
 def wav_symbols():
     """the exports include/spkwav.h declares"""
     return list(_WAV_SIGS)
+
+
+def boot_symbols():
+    """the exports include/spkboot.h declares"""
+    return list(_BOOT_SIGS)
 
 
 def ptr(t):

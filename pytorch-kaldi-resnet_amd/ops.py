@@ -1758,3 +1758,70 @@ def cal_pav(score, label, order, upto=0):
     call("spk_cal_pav", ptr(score), ptr(label), ptr(order), ptr(r["tie"]), ptr(r["pools"]), ptr(r["counts"]), ptr(r["pool_of"]),
          ptr(r["min_cllr"]), ptr(ws), need, T, int(upto), stream(), nbytes=13.0 * T)
     return r
+
+
+# ---- speaker-level bootstrap of the error-rate sweep (csrc/boot.hip) -----------------------------------------------
+BOOT_WS_BYTES = 128 << 20      # workspace of one chunk of replicates at most (one group of replicates always runs)
+
+
+def boot_sizes(U=None):
+    """(positions per workgroup, largest U, largest count, cost triples per call, replicates per workgroup at most, threads) of
+    csrc/boot.hip; with U: (replicates per workgroup, entries per row of the device count table) for that many units"""
+    l = hip.lib()
+    if U is None:
+        return tuple(l.spkb_limit(i) for i in range(6))
+    return l.spkb_group(int(U)), l.spkb_pitch(int(U))
+
+
+def boot_pack(score, label, order, ua, ub, eta, U):
+    """score [T] float64, label [T] uint8, order [T] from sort_trials, ua / ub [T] int32 in [0, U) (device); eta: P <= 8 thresholds
+    (host) -> (rec: int64 [T], one record per sorted position; q: int64 [P], the sorted scores below each threshold) (spkb_pack)"""
+    T, P = score.numel(), len(eta)
+    assert score.dtype == torch.float64 and label.dtype == torch.uint8 and order.dtype == torch.int32
+    assert ua.dtype == torch.int32 and ub.dtype == torch.int32
+    assert label.numel() == T and order.numel() == T and ua.numel() == T and ub.numel() == T
+    ed = np.ascontiguousarray(eta, dtype=np.float64).reshape(P)
+    rec = torch.empty(T, device=score.device, dtype=torch.int64)
+    q = torch.zeros(max(P, 1), device=score.device, dtype=torch.int64)
+    call("spkb_pack", ptr(score), ptr(label), ptr(order), ptr(ua), ptr(ub), ed.ctypes.data if P else None, P, ptr(rec), ptr(q), T, int(U),
+         stream(), nbytes=25.0 * T)
+    return rec, q[:P]
+
+
+def boot_table(counts, device):
+    """counts [R][U] of integers in [0, 65 535] (host) -> the device table uint16 [R][pitch] (viewed as int16) spkb_sweep reads"""
+    c = np.asarray(counts)
+    R, U = c.shape
+    pitch = boot_sizes(U)[1]
+    tab = np.zeros((R, pitch), dtype=np.uint16)
+    tab[:, :U] = c
+    return torch.from_numpy(tab.view(np.int16)).to(device)
+
+
+def boot_sweep(rec, q, table, U, cmax, costs, act_costs, chunk=None, upto=0):
+    """rec, q from boot_pack, table from boot_table, cmax: the largest count; costs: P <= 8 triples of the minimum costs, act_costs:
+    len(q) triples of the actual costs -> (out_d [R][1 + P + Pa] float64, out_i [R][4 + P + 2 Pa] int64) on the device, laid out as
+    include/spkboot.h says.  The replicates run in chunks of `chunk` (default: what BOOT_WS_BYTES of workspace hold, whole groups).
+    upto: 1 / 2 / 3 stop every chunk after that phase (tools/boot_bench.py: the differences are the phases); the outputs are then not
+    written."""
+    T, R, P, Pa = rec.numel(), table.shape[0], len(costs), len(act_costs)
+    assert rec.dtype == torch.int64 and table.dtype == torch.int16 and table.is_contiguous() and q.numel() == Pa
+    G, pitch = boot_sizes(U)
+    assert table.shape[1] == pitch, "the table of boot_table for U"
+    cd = np.ascontiguousarray([[float(v) for v in c] for c in costs], dtype=np.float64).reshape(P, 3)
+    ad = np.ascontiguousarray([[float(v) for v in c] for c in act_costs], dtype=np.float64).reshape(Pa, 3)
+    per = hip.lib().spkb_sweep_ws_elems(T, P, Pa, 1)
+    if per < 0:
+        raise ValueError("spkb_sweep_ws_elems(%d, %d, %d, 1): a shape the bootstrap kernels refuse" % (T, P, Pa))
+    if chunk is None:
+        chunk = max(1, BOOT_WS_BYTES // (8 * per) // G) * G
+    chunk = max(1, min(int(chunk), R))
+    out_d = torch.empty(R, 1 + P + Pa, device=rec.device, dtype=torch.float64)
+    out_i = torch.empty(R, 4 + P + 2 * Pa, device=rec.device, dtype=torch.int64)
+    ws = torch.empty(per * chunk, device=rec.device, dtype=torch.int64)
+    for r0 in range(0, R, chunk):
+        n = min(chunk, R - r0)
+        call("spkb_sweep", ptr(rec), ptr(table[r0:r0 + n]), int(U), n, int(cmax), cd.ctypes.data if P else None, P,
+             ad.ctypes.data if Pa else None, ptr(q) if Pa else None, Pa, ptr(out_d[r0:r0 + n]), ptr(out_i[r0:r0 + n]), ptr(ws),
+             per * chunk, T, int(upto), stream(), nbytes=2.0 * 8 * T * -(-n // G), flops=2.0 * T * n)
+    return out_d, out_i

@@ -362,15 +362,43 @@ def _calibrated(report, scores, labels, costs, calibration, backend):
     return report
 
 
+def _trial_pairs(trials_path):
+    return [tuple(line.split()[:2]) for line in open(trials_path)]
+
+
+def _bootstrap_ci(pairs, scores, labels, costs, calibration, backend, options):
+    """score_and_report's 'ci': {'eer', 'min_dcf', 'act_dcf' (of the calibrated scores; empty without a model), 'replicates',
+    'degenerate', 'alpha', 'units'}, each entry {'value', 'lo', 'hi', 'mean', 'std'}"""
+    from . import bootstrap as boot
+    opt = dict(options)
+    ua, ub, names = boot.trial_units(pairs, opt.pop("utt2spk", None))
+    if opt.get("counts") is None:
+        opt["counts"] = boot.bootstrap_counts(len(names), opt.pop("replicates", 1000), opt.pop("seed", 0))
+    opt.pop("replicates", None)
+    opt.pop("seed", None)
+    ci = boot.bootstrap_report(scores, labels, ua, ub, costs, (), backend=backend, units=len(names), **opt)
+    if calibration is not None:
+        from . import calibration as cal
+        model = cal.load(calibration) if isinstance(calibration, str) else calibration
+        act = boot.bootstrap_report(cal.apply(model, scores, backend), labels, ua, ub, (), costs, backend=backend, units=len(names), **opt)
+        ci["act_dcf"], ci["act_costs"] = act["act_dcf"], act["act_costs"]
+    del ci["values"]
+    return ci
+
+
 def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_stats=None, costs=DEFAULT_COSTS, backend="host",
-                     score_path=None, plda=None, transform=None, num_utts=None, calibration=None):
+                     score_path=None, plda=None, transform=None, num_utts=None, calibration=None, bootstrap=None):
     """The whole scoring stage in one process: cosine per trial, adaptive S-norm when both statistics tables are given
     (utt -> (mean, std), topk_mean_std / read_mean_std), error-rate sweep.  -> the error_rates report.  On `hip` the embeddings
     and the index arrays go up and only the report comes down (and the scores, if score_path asks for them).
     plda = (mean, transform, psi) with the LDA `transform` (and optionally num_utts: utt -> enrolment count) scores the trials with
     the PLDA back end instead of the cosine (plda.plda_score); S-norm does not apply to it.
     calibration: a one-system calibration.Model (or its file): the report gains 'cllr', 'min_cllr' and 'act_dcf' of the calibrated
-    scores (section 6s); without it the report is what it was."""
+    scores (section 6s); without it the report is what it was.
+    bootstrap: a dict of bootstrap_report's options (replicates, seed, alpha, max_degenerate, counts) and `utt2spk` (a dict or a file:
+    the speakers that are resampled; without it every id is its own unit): the report gains 'ci', the speaker-level bootstrap
+    intervals of the EER and every minDCF - and of every actDCF when `calibration` is given (section 6t); without it the report is
+    what it was."""
     if plda is not None:
         from . import plda as plda_mod
         assert transform is not None, "the plda back end needs the LDA transform"
@@ -383,7 +411,11 @@ def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_st
         else:
             scores = scores.astype(np.float64)
         report = error_rates(scores, labels, costs, backend)
-        return report if calibration is None else _calibrated(report, scores, labels, costs, calibration, backend)
+        if calibration is not None:
+            report = _calibrated(report, scores, labels, costs, calibration, backend)
+        if bootstrap is not None:
+            report["ci"] = _bootstrap_ci(_trial_pairs(trials_path), scores, labels, costs, calibration, backend, bootstrap)
+        return report
     pairs, labels, ia, ib, me, mt = _read_trials(trials_path, enroll, test, mean)
     snorm = enroll_stats is not None or test_stats is not None
     if snorm:
@@ -404,9 +436,16 @@ def score_and_report(enroll, test, trials_path, mean, enroll_stats=None, test_st
     report = error_rates(scores, labels, costs, backend)
     if calibration is not None:
         report = _calibrated(report, scores, labels, costs, calibration, backend)
+    if bootstrap is not None:
+        report["ci"] = _bootstrap_ci(pairs, scores, labels, costs, calibration, backend, bootstrap)
     if score_path:
         host = scores.cpu().numpy() if backend == "hip" else scores
         with open(score_path, "w") as f:
             for (a, b), v in zip(pairs, host.tolist()):
                 f.write("{} {} {}\n".format(a, b, v))
     return report
+
+
+# ---- speaker-level bootstrap intervals of the report (bootstrap.py) ------------------------------------------
+from .bootstrap import (bootstrap_compare, bootstrap_counts, bootstrap_replicates, bootstrap_report, match_scores,  # noqa: E402,F401
+                        trial_units)

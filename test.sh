@@ -8,6 +8,8 @@
 #   scores to the rounding of its float32 stages).
 #   SPK_CALIBRATION=<model> (scripts/calibrate.py train, one system): stage 12 also writes the calibrated scores <scores>_cal and
 #   stage 13 the report <eer file>_cal: Cllr, minCllr and actDCF at p-target 0.01 and 0.001.
+#   SPK_BOOTSTRAP=<R> (optionally SPK_BOOTSTRAP_UTT2SPK=<utt2spk>: resample speakers, not utterance ids): stage 13 also writes
+#   <eer file>_ci, the report with a speaker-level bootstrap interval behind each number (scripts/bootstrap_ci.py).
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
 
@@ -82,5 +84,10 @@ if [ $stage -le 13 ]; then
   if [ -n "$SPK_CALIBRATION" ]; then
     python $here/scripts/compute_cllr.py --backend $impl $dir/${score_file}_cal $voxceleb1_trials > $dir/${eer_file}_cal 2> /dev/null
     cat $dir/${eer_file}_cal
+  fi
+  if [ -n "$SPK_BOOTSTRAP" ]; then
+    python $here/scripts/bootstrap_ci.py --backend $impl --replicates $SPK_BOOTSTRAP \
+        ${SPK_BOOTSTRAP_UTT2SPK:+--utt2spk $SPK_BOOTSTRAP_UTT2SPK} $dir/$score_file $voxceleb1_trials > $dir/${eer_file}_ci 2> /dev/null
+    cat $dir/${eer_file}_ci
   fi
 fi
